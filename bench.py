@@ -4,13 +4,18 @@
 A "step" is one whole proof (reference src/groth16.cpp:48-254) of a synthetic BN254 key with n = domainSize = nVars = 2^k
 (default k = 22: BASELINE configs[2]; --log2n 20 = configs[1]).  Every step has its own witness in pageable HOST memory, as
 the reference's Prover::prove(FrElement *wtns) contract has it (src/groth16.hpp:101): the upload is INSIDE the timed region
-(zk_prove_submit).  The rate with witnesses resident in HBM is measured too (`resident_witness`).
+(zk_prove_submit).  With --dump-outputs every step's r and s are seeded (the same arguments give the same proofs).
 
-  python bench.py --gpus 1 --steps K --warmup W                                  (N = 1)
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]    (N = 1)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (N > 1: one proof split across the ranks,
       MSM tables sharded by point range, the chain partitioned, four RCCL all_to_all per proof; "scaling": "strong")
 
-ONE JSON line on rank 0.  Besides the contract's keys:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs (the proof of the last timed step) and prints the line:
+the contract's keys, config, stage_ms, setup_s and the roofline with its counters replayed from profiles/.  Everything below
+that is not the headline — the other witness placement, the one-at-a-time latencies, cpu_baseline, the also_* legs, the counter
+passes, and for N > 1 the check against an unsharded prover and the replicas leg — runs with --full only.
+
+ONE JSON line on rank 0.  Besides the contract's keys (with --full):
   roofline      flat: the dominant kernel k_msm_accum_l1<Fq> against HBM (algorithmic bytes 96*n per G1 MSM / launch time, SURVEY
                 section 8d), its measured HBM traffic and random-gather rate against the chip's gather ceiling, the G2 launch (g2_*),
                 and the path's own bound — VALU issue (issue_*: instructions per proof x 4 cycles / (SIMDs x sampled clock)).
@@ -27,6 +32,7 @@ ONE JSON line on rank 0.  Besides the contract's keys:
 Definitions of every field: DESIGN.md section 6.
 """
 import argparse
+import collections
 import json
 import os
 import sys
@@ -83,6 +89,12 @@ def parse():
     ap.add_argument("--no-2p24", action="store_true", help="skip the also_2p24 leg of a default run (configs[3]'s size on one GPU, and its rank share of eight)")
     ap.add_argument("--no-shard8", action="store_true", help="skip the also_shard8 probes of a default run (one rank's share of a proof split across eight GPUs)")
     ap.add_argument("--no-server", action="store_true", help="skip the also_server leg of a default run (proverServer over REST on a Semaphore-class key)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the other witness placement, one-at-a-time latencies, cpu_baseline, the other "
+                         "configurations (also_*), the counter passes, the multi-GPU check and replicas (the --no-* switches apply here)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps: the proof(s) of the last timed step as DIR/proof_{a,b,c}.npy (float32, one byte of the "
+                         "zk_proof record per element); every step's r and s are then seeded, so the same arguments give the same files")
     ap.add_argument("--counters-child", default="", help=argparse.SUPPRESS)      # internal: the process rocprofv3 wraps (rapidsnark_old_amd.counters)
     ap.add_argument("--counters-proofs", type=int, default=2, help=argparse.SUPPRESS)
     return ap.parse_args()
@@ -99,7 +111,10 @@ def main():
     out = run(args)
     if out is None:                       # ranks > 0
         return
-    default_run = args.gpus == 1 and args.log2n == 22 and not args.no_cpu and args.batch <= 1 and args.witness == "uniform" and args.shape == "dense"
+    last = out.pop("last_step_proofs")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    default_run = args.full and args.gpus == 1 and args.log2n == 22 and not args.no_cpu and args.batch <= 1 and args.witness == "uniform" and args.shape == "dense"
     legs = {LEG_OF.get((args.shape, args.log2n), "headline"): out}
     import copy
     shard8 = []
@@ -137,7 +152,7 @@ def main():
     # ---- counters: measured by this run where rocprofv3 can wrap a child of it, else replayed from profiles/
     from rapidsnark_old_amd import counters
     measured, how = {}, None
-    why_not = counters.available() if not args.no_counters else "--no-counters"
+    why_not = "plain run (--full runs them)" if not args.full else counters.available() if not args.no_counters else "--no-counters"
     can = [leg for leg in legs if leg in LEG_OF.values()]
     if why_not is None and args.gpus == 1 and can:
         try:
@@ -253,10 +268,23 @@ def run(args):
     # the same for the resident-witness leg
     nw = args.steps + args.warmup
     n_wits = max(1, min(nw, (8 << 30) // (32 << k)))      # one per step while they fit 8 GiB of host memory (2^22: all 33), else cycled
-    wits_host = [synth.make_witness(k, seed=i, kind=args.witness, n_vars=wl["nVars"]) for i in range(n_wits)]
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(16, effective_cores()))) as ex:      # (each witness has its own seeded generator: same bytes)
+        made = ex.map(lambda i: synth.make_witness(k, seed=i, kind=args.witness, n_vars=wl["nVars"]), range(n_wits))
+        # copied into pages this thread touches first, as when it generated them itself: the timed uploads read them
+        wits_host = [np.copy(w) for w in made]
+    headline_hbm = args.witness_in == "hbm"
     wits_dev = [torch.from_numpy(w).to(dev) for w in wits_host]
     torch.cuda.synchronize()
     pipelined = bool(args.pipeline)
+    # --dump-outputs: r and s of submission i (warm-up included) seeded, so that the same arguments give the same proofs;
+    # otherwise the library draws them for every proof, like the reference
+    rs_of = [(None, None)]
+    if args.dump_outputs:
+        from rapidsnark_old_amd.synth import R_MOD
+        import random
+        rs_rng = random.Random(0x5EED5 + 1000003 * k)
+        rs_of = [(rs_rng.randrange(1, R_MOD), rs_rng.randrange(1, R_MOD)) for _ in range(max(nw, ZK_DEPTH_MAX) * max(1, args.batch))]
 
     leg_prefix = "2p%d%s" % (args.log2n, "" if args.shape == "dense" else "_" + args.shape)
 
@@ -266,33 +294,43 @@ def run(args):
         forms (a marker launch in front of it when ZK_BENCH_LEG_MARKERS=1; nothing in a normal run)."""
         units = args.batch if (args.batch > 1 and world == 1 and not in_hbm) else 1     # proofs per submission
         nsub = steps // units
+        pending = collections.deque()                        # (r, s) of the submissions not yet collected, oldest first
+        last = []                                            # the proof(s) of the latest collect
 
         def submit(i):
             j = i % len(wits_host)
+            r, s = rs_of[(i * units) % len(rs_of)]
             if units > 1:                                    # zk_prove_batch_submit: `units` witnesses, one set of launches
-                prover.submit_batch([wits_host[(i * units + t) % len(wits_host)] for t in range(units)])
+                prover.submit_batch([wits_host[(i * units + t) % len(wits_host)] for t in range(units)],
+                                    rs=[rs_of[(i * units + t) % len(rs_of)] for t in range(units)] if args.dump_outputs else None)
                 return
+            pending.append((r, s))
             if chain is not None:                            # phases + four rounds of all_to_all (RCCL over xGMI)
                 if in_hbm:
-                    chain.submit(d_wtns=wits_dev[j].data_ptr())
+                    chain.submit(d_wtns=wits_dev[j].data_ptr(), r=r, s=s)
                 elif sliced_upload:                          # 1/N of the witness over PCIe per rank + all_gather over xGMI
-                    chain.submit_host_sliced(wits_host[j])
+                    chain.submit_host_sliced(wits_host[j], r=r, s=s)
                 else:
-                    chain.submit(wtns=wits_host[j])
-            elif in_hbm:
+                    chain.submit(wtns=wits_host[j], r=r, s=s)
+            elif in_hbm and r is None:
                 prover.submit_dev(wits_dev[j].data_ptr())
+            elif in_hbm:                                     # zk_prove_dev_submit with this submission's seeded r and s
+                ra, sa = prover._k32(r), prover._k32(s)
+                prover.L.check(prover.lib.zk_prove_dev_submit(prover.h, prover.C.c_void_p(wits_dev[j].data_ptr()), ra.ctypes.data, sa.ctypes.data))
             else:
-                prover.submit_host(wits_host[j])             # pageable -> pinned staging -> HBM, all inside the call / its stream
+                prover.submit_host(wits_host[j], r, s)       # pageable -> pinned staging -> HBM, all inside the call / its stream
 
         def collect():
             if units > 1:
-                prover.collect_batch(units)
+                last[:] = prover.collect_batch(units)
             elif world == 1:
-                prover.collect()
+                pending.popleft()
+                last[:] = [prover.collect()]
             else:                                            # this rank's partial sums -> all ranks -> rank 0 assembles
+                r, s = pending.popleft()
                 parts = zk.gather_partials(prover.collect_msm(), dist, xdev)     # RCCL all_gather over xGMI: 384 B per rank
                 if rank == 0:
-                    prover.prove_finish(parts)
+                    last[:] = [prover.prove_finish(parts, r, s)]
 
         stage = {}
 
@@ -394,16 +432,17 @@ def run(args):
             t = torch.tensor([dt], dtype=torch.float64, device=xdev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt, {kk: v / nsub for kk, v in stage.items()}
+        return dt, {kk: v / nsub for kk, v in stage.items()}, list(last)
 
-    headline_hbm = args.witness_in == "hbm"
     from rapidsnark_old_amd.telemetry import ClockSampler
     leg_marker(zk, torch, leg_prefix + "_warmup")
     with ClockSampler(local_rank, enabled=os.environ.get("ZK_BENCH_CLOCK", "1") != "0") as clock:   # shader clock + socket power WHILE the headline runs (issue-bound roofline)
-        elapsed, stage = timed_run(headline_hbm, args.steps, args.warmup, leg=leg_prefix + "_headline")
-    # the other witness placement, same K (outside the headline's timed region)
-    leg_marker(zk, torch, leg_prefix + "_between")
-    other_elapsed, other_stage = timed_run(not headline_hbm, args.steps, 1, leg=leg_prefix + "_other_witness_placement")
+        elapsed, stage, last_proofs = timed_run(headline_hbm, args.steps, args.warmup, leg=leg_prefix + "_headline")
+    other_elapsed = None
+    if args.full:
+        # the other witness placement, same K (outside the headline's timed region)
+        leg_marker(zk, torch, leg_prefix + "_between")
+        other_elapsed, _, _ = timed_run(not headline_hbm, args.steps, 1, leg=leg_prefix + "_other_witness_placement")
 
     def one_proof(i):
         return prover.prove_dev(wits_dev[i % len(wits_dev)].data_ptr())
@@ -412,7 +451,7 @@ def run(args):
     # key on rank 0's GPU (tables as in the zkey, whole chain on one GPU): the multi-GPU path must
     # reproduce the single-GPU proof bit for bit.  Outside the timed region.
     verified = None
-    if world > 1 and args.verify:
+    if world > 1 and args.verify and args.full:
         vr, vs = 0x1234567, 0x7654321
         if chain is not None:
             chain.submit(wtns=wits_host[0], r=vr, s=vs)
@@ -429,12 +468,12 @@ def run(args):
     # unsharded prover, no collective in the data path (what proverServer's throughput mode runs; "replicas
     # only").  Same timing rules: barrier + synchronize on both sides, max over ranks; value = N * K proofs / that time.
     replicas = None
-    if world > 1 and not args.no_replicas:
+    if world > 1 and not args.no_replicas and args.full:
         replicas = replicas_leg(zk, wl, local_rank, k, wits_host, args.steps, args.precomp, dist, xdev, torch, world)
 
     latency_ms = latency_host_ms = None
     lone = {}
-    if world == 1:                        # outside the timed region: strictly one proof at a time
+    if world == 1 and args.full:          # outside the timed region: strictly one proof at a time
         torch.cuda.synchronize()
         leg_marker(zk, torch, leg_prefix + "_lone_resident")
         t1 = time.perf_counter()
@@ -502,15 +541,17 @@ def run(args):
         "roofline": roofline,
         "stage_ms": {kk: round(v, 3) for kk, v in stage.items()},
         "setup_s": {"generate": round(t_gen, 2), "create": round(t_create, 2)},
+        "last_step_proofs": last_proofs,          # (taken out by main: --dump-outputs)
     }
-    other = {"value": round(args.steps / other_elapsed, 4), "unit": "proofs/s", "ms_per_step": round(other_elapsed / args.steps * 1e3, 3), "steps": args.steps}
-    out["host_witness" if headline_hbm else "resident_witness"] = other
+    if other_elapsed is not None:
+        other = {"value": round(args.steps / other_elapsed, 4), "unit": "proofs/s", "ms_per_step": round(other_elapsed / args.steps * 1e3, 3), "steps": args.steps}
+        out["host_witness" if headline_hbm else "resident_witness"] = other
     if verified is not None:
         out["multi_gpu_proof_equals_single_gpu_proof"] = verified
     if latency_ms is not None:
         out["latency_ms_one_at_a_time"] = {"witness_in_hbm": round(latency_ms, 3), "witness_in_host_memory": round(latency_host_ms, 3)}
         out["ms_per_proof_sync"] = round(latency_host_ms, 3)       # SURVEY 8(d)'s ms/proof: one synchronous zk_prove, witness in host RAM
-    if world == 1 and not args.no_cpu:
+    if world == 1 and not args.no_cpu and args.full:
         out["cpu_baseline"] = cpu_baseline(wl, k, synth, prover, wits_host[0], wits_dev[0], args.cpu_budget_s)
     if world > 1:
         out["first_contact"] = first_contact_info
@@ -532,7 +573,7 @@ def run(args):
 
 
 def want_shard8(args):
-    return not args.no_shard8 and args.log2n in (22, 24) and args.batch <= 1 and not args.window_bits
+    return args.full and not args.no_shard8 and args.log2n in (22, 24) and args.batch <= 1 and not args.window_bits
 
 
 def shard8_leg(zk, torch, wl, k, w_dev, single_ms, single_lone_ms, precomp, ranks=8):
@@ -587,6 +628,16 @@ def shard8_leg(zk, torch, wl, k, w_dev, single_ms, single_lone_ms, precomp, rank
             "window_bits_h": plan["window_bits_h"], "additions_per_point_h": plan["windows_h"],
             "window_bits_w": plan["window_bits_w"], "additions_per_point_w": plan["windows_w"],
             "stage_ms_one_at_a_time": stage}
+
+
+def dump_outputs(d, proofs):
+    """--dump-outputs DIR: the proof(s) the last timed step handed back — zk_proof records (A | B | C, affine, Montgomery form, 32-byte
+    little-endian coordinates, include/zkhip.h) — as DIR/proof_a.npy [P, 64], proof_b.npy [P, 128], proof_c.npy [P, 64] in float32,
+    one byte per element (exact), P = proofs of that step (the witnesses of a --batch submission)."""
+    os.makedirs(d, exist_ok=True)
+    raw = np.frombuffer(b"".join(proofs), dtype=np.uint8).reshape(len(proofs), 256).astype(np.float32)
+    for name, lo, hi in (("proof_a", 0, 64), ("proof_b", 64, 192), ("proof_c", 192, 256)):
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(raw[:, lo:hi]))
 
 
 def finish_roofline(out, cs, source, ceiling):

@@ -438,6 +438,29 @@ int zk_prover_reserve(zk_prover *p, uint32_t in_flight, uint32_t host_witnesses)
             p->slot[i].release_memory();
         for (int lane = nslots < 1 ? 1 : nslots; lane < p->lanes; lane++)
             if (p->extra[lane - 1]) p->extra[lane - 1]->release_memory();
+        // What the reservation adds must fit the free HBM BEFORE anything is allocated: a reservation that ran out of memory
+        // part-way left the prover to the shallower retry (Groth16::makeProver) half-allocated, and proverServer died in that
+        // retry (SIGSEGV) where a 2^20 key met a GPU with 7 GiB free.  Every slot and lane has the size of slot 0 / lane 0,
+        // which create allocated; the margin covers the allocator's rounding and the queues of the lanes' new streams.
+        {
+            const size_t slot_b = p->slot[0].device_bytes(), wtns_b = (size_t)p->nVars * sizeof(Fr) * p->batch;
+            const size_t lane_b = p->abc.bytes() + p->h.bytes() + p->sort_h.bytes();
+            size_t need = 0;
+            for (int i = 0; i < nslots; i++) {
+                if (!p->slot[i].allocated) need += slot_b;
+                if (host_witnesses && !p->slot[i].wtns_dev.p) need += wtns_b;
+            }
+            for (int lane = 1; lane < p->lanes && lane < nslots; lane++)
+                if (!p->extra[lane - 1]->ready) need += lane_b;
+            if (need) {
+                size_t fr = 0, tot = 0;
+                HIP_TRY(hipMemGetInfo(&fr, &tot));
+                const size_t margin = need / 32 + ((size_t)256 << 20);
+                if (fr < need + margin)
+                    throw HipError("zk_prover_reserve: out of memory (" + std::to_string(in_flight) + " in flight need " +
+                                   std::to_string((need + margin) >> 20) + " MiB of HBM, " + std::to_string(fr >> 20) + " MiB free)");
+            }
+        }
         // Every slot of the ring is allocated NOW (device workspace, and for host witnesses the HBM witness buffer and its
         // pinned staging copy), so that out-of-memory is a start-up error and the first `depth` proofs do not pay for it.
         for (int i = 0; i < nslots; i++) {

@@ -57,6 +57,7 @@ struct DevBuf {
     void upload(const void *src, size_t count, hipStream_t s) {
         if (count) HIP_TRY(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s));
     }
+    size_t bytes() const { return n * sizeof(T); }      // what alloc(n) asked for
 };
 
 // Host image -> HBM for the big zkey sections (src/binfile_utils.cpp:28-33 copies the whole file into a
@@ -157,6 +158,10 @@ struct SortBufs {
         lo.release(); counts.release(); starts.release(); offsets.release(); entries.release();
         codes.release(); val.release(); bin_counts.release(); bin_starts.release();
         n = 0; ran = false;
+    }
+    size_t bytes() const {
+        return lo.bytes() + counts.bytes() + starts.bytes() + offsets.bytes() + entries.bytes() + codes.bytes() + val.bytes()
+             + bin_counts.bytes() + bin_starts.bytes();
     }
     bool ran = false;
     void run(const Fr *scalars, hipStream_t s) {
@@ -260,6 +265,11 @@ struct zk_prover {
         const Fr *graph_wtns = nullptr;
         hipEvent_t ev_gdone = nullptr;      // recorded behind the graph launch: what a collect waits for
         bool via_graph = false;
+        // HBM of the slot's proof workspace (the witness buffer aside), as alloc_slot made it
+        size_t device_bytes() const {
+            return sort_w.bytes() + buckets_g1.bytes() + buckets_g2.bytes() + scratch_g1.bytes() + acc_ws_g1_all.bytes() + acc_key_all.bytes()
+                 + acc_flag_all.bytes() + scratch_g2.bytes() + acc_ws_g2.bytes() + wsum_g1.bytes() + wsum_g2.bytes();
+        }
         // Give the slot's device and pinned memory back (events stay).  Only for a slot no proof is using: zk_prover_reserve
         // does this to the slots beyond a ring that a failed, deeper reservation left allocated.
         void release_memory() {

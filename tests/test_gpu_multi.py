@@ -162,7 +162,7 @@ def test_bench_multi_rank_path_on_one_gpu(ranks, k):
         port = sock.getsockname()[1]
         sock.close()
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
-               "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "4", "--warmup", "1",
+               "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(ranks), "--steps", "4", "--warmup", "1",
                "--log2n", str(k), "--no-cpu"]
         try:
             res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)

@@ -4,6 +4,6 @@ pick='import json,sys; d=json.loads(sys.stdin.readlines()[-1]); r=d["roofline"];
 for k in ${@:-22 20}; do
   for cm in 128 160 320; do
     echo "2^$k ZKHIP_ACC_CHUNK_MAX=$cm"
-    ZKHIP_ACC_CHUNK_MAX=$cm python bench.py --no-cpu --log2n $k 2>/dev/null | python -c "$pick"
+    ZKHIP_ACC_CHUNK_MAX=$cm python bench.py --full --no-cpu --log2n $k 2>/dev/null | python -c "$pick"
   done
 done

@@ -6,7 +6,7 @@ for rep in 1 2 3; do
 for which in new old; do
   if [ $which = old ]; then export ZKHIP_LIB=$old; else unset ZKHIP_LIB; fi
   for k in 22 20; do
-  python bench.py --steps 12 --warmup 3 --no-cpu --log2n $k 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$which 2^$k: period host', d['ms_per_step'], 'resident', d['resident_witness']['ms_per_step'], '| one at a time: resident', d['latency_ms_one_at_a_time']['witness_in_hbm'], 'SYNC host witness', d['ms_per_proof_sync'])"
+  python bench.py --full --steps 12 --warmup 3 --no-cpu --log2n $k 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$which 2^$k: period host', d['ms_per_step'], 'resident', d['resident_witness']['ms_per_step'], '| one at a time: resident', d['latency_ms_one_at_a_time']['witness_in_hbm'], 'SYNC host witness', d['ms_per_proof_sync'])"
   done
 done
 done

@@ -9,7 +9,7 @@ for k in ${@:-22 20 18 16}; do
     for t in 2 0; do
       echo -n "2^$k ZKHIP_TAIL=$t"
       st=20; [ $k -le 18 ] && st=100
-      ZKHIP_TAIL=$t python bench.py --no-cpu --log2n $k --steps $st --warmup 4 2>/dev/null | python -c "$pick"
+      ZKHIP_TAIL=$t python bench.py --full --no-cpu --log2n $k --steps $st --warmup 4 2>/dev/null | python -c "$pick"
     done
   done
 done

@@ -2,7 +2,7 @@
 # Instruction-cache behaviour of the level-1 kernels (their loops are 18 KB (G1) and 58 KB (G2) of code; the
 # I-cache is 64 KB per two CUs).  tools/icache_probe.sh <tag>
 tag=$1; out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
-cmd="python bench.py --steps 3 --warmup 1 --in-flight 1 --no-cpu"
+cmd="python bench.py --full --steps 3 --warmup 1 --in-flight 1 --no-cpu"
 i=0
 for grp in "SQC_ICACHE_REQ SQC_ICACHE_HITS" "SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "SQ_INSTS_VALU SQ_IFETCH" "SQ_WAIT_INST_ANY SQ_IFETCH_LEVEL"; do
   i=$((i+1))

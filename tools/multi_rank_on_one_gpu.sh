@@ -6,7 +6,7 @@ for n in 2 4 8; do
   for chain in partitioned replicated; do
     echo "== $n ranks, chain $chain, 2^$k"
     ZK_BENCH_SHARE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-      bench.py --gpus $n --steps 4 --warmup 1 --log2n $k --no-cpu --chain $chain 2>/dev/null | python -c "
+      bench.py --full --gpus $n --steps 4 --warmup 1 --log2n $k --no-cpu --chain $chain 2>/dev/null | python -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Shader clock, power and temperature while bench.py runs 2^22 proofs (rocm-smi samples every 1.5 s): bash tools/power_probe.sh
-python bench.py --no-cpu --no-2p20 --steps 120 --warmup 3 > /tmp/b.json 2>/dev/null &
+python bench.py --full --no-cpu --no-2p20 --steps 120 --warmup 3 > /tmp/b.json 2>/dev/null &
 BP=$!
 sleep 22
 for i in 1 2 3 4 5 6; do

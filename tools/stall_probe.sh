@@ -7,7 +7,7 @@ tag=$1
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-cmd="python bench.py --steps 3 --warmup 1 --in-flight 1 --no-cpu"
+cmd="python bench.py --full --steps 3 --warmup 1 --in-flight 1 --no-cpu"
 i=0
 for grp in "GRBM_GUI_ACTIVE SQ_WAVES" "SQ_BUSY_CYCLES SQ_WAVE_CYCLES" "SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" "SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_ANY" \
            "SQ_WAIT_INST_ANY SQ_WAIT_ANY" "SQ_ACTIVE_INST_SCA SQ_INSTS_SALU" "SQ_ACTIVE_INST_LDS SQ_INSTS_LDS" "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM" \
