@@ -295,6 +295,41 @@ size_t zk_proof_to_json(const zk_proof *proof, char *buf, size_t cap);
 /* public.json: ["w1",...,"wN"], or null when nPublic == 0 (reference quirk Q7). */
 size_t zk_public_to_json(const uint8_t *wtns, uint32_t nPublic, char *buf, size_t cap);
 
+/* ---- R1CS: check a witness against the circuit's constraints before proving ------------- */
+/* Nothing in the reference corresponds to these entry points: Prover::prove (src/groth16.cpp:48-254) trusts its witness
+ * and never looks at C, so a witness that breaks a constraint still yields a proof that only the verifier rejects.  The
+ * counterpart is snarkjs `wtns check <circuit.r1cs> <witness.wtns>`.  A checker holds circom's .r1cs on one device and
+ * runs on a stream of its own (it synchronises that stream only); calls on one checker are serialised.
+ * zk_r1cs_view: the .r1cs header and section 2 (constraints) exactly as in the file; the caller has checked the prime
+ * (BN254 r).  create range-checks every term: a wire id >= nWires or a coefficient >= r is an error naming the constraint. */
+typedef struct zk_r1cs zk_r1cs;
+typedef struct zk_r1cs_view {
+    uint32_t nWires, nPubOut, nPubIn, nPrvIn, nConstraints;
+    const void *constraints;                /* section 2 as in the file */
+    uint64_t constraints_bytes;
+} zk_r1cs_view;
+/* Set rep->size = sizeof(zk_r1cs_report) before a check (as zk_prover_plan: only `size` bytes are written). */
+typedef struct zk_r1cs_report {
+    uint32_t size;
+    uint64_t failed;                        /* constraints with (A.w)(B.w) != C.w */
+    uint32_t first_failed;                  /* lowest such constraint; UINT32_MAX: none */
+    uint8_t a[32], b[32], c[32];            /* A.w, B.w, C.w of first_failed, standard form LE (zero when none fails) */
+    uint32_t one_ok;                        /* w[0] == 1 (the verifier assumes it) */
+    uint32_t first_unreduced;               /* lowest index of a witness value >= r; UINT32_MAX: none */
+} zk_r1cs_report;
+int zk_r1cs_create(zk_r1cs **out, const zk_r1cs_view *v, int32_t device);      /* device -1: the current one */
+void zk_r1cs_destroy(zk_r1cs *r);
+/* wtns: nVars x 32 B standard form in host memory / in HBM on the checker's device.  nVars != nWires is an error, not a
+ * report.  A device witness must be complete when the call is made (the checker's stream does not wait for others). */
+int zk_r1cs_check(zk_r1cs *r, const uint8_t *wtns, uint32_t nVars, zk_r1cs_report *rep);
+int zk_r1cs_check_dev(zk_r1cs *r, const void *d_wtns, uint32_t nVars, zk_r1cs_report *rep);
+/* Was this .zkey made from this circuit?  Sizes first (nVars == nWires, nPublic == nPubOut + nPubIn, domainSize >=
+ * nConstraints + nPublic + 1: a mismatch is an error), then A and B as linear maps: A.x and B.x for one random x from
+ * the zkey's coefficient records and from the .r1cs, compared row by row — rows below nConstraints equal, zkey row
+ * nConstraints + i = (x_i, 0) for i <= nPublic (snarkjs's public-input rows), later rows 0.  A difference goes
+ * undetected with probability ~1/r.  C is not in a .zkey, so the match cannot cover it.  first_row: UINT32_MAX = none. */
+int zk_r1cs_match_zkey(zk_r1cs *r, const zk_zkey_view *zkey, uint64_t *rows_differing, uint32_t *first_row);
+
 #ifdef __cplusplus
 }
 #endif

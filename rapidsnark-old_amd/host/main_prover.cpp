@@ -4,7 +4,9 @@
 // exit codes (-1 on usage / any error, 0 on success), same output bytes (compact JSON, no
 // trailing newline).  The hot path runs on the MI355X through libzkhip.so.
 // Extras via the environment, so argv stays identical: ZKHIP_FIXED_R / ZKHIP_FIXED_S = 64 hex
-// digits (32-byte little-endian scalars) make the proof deterministic for parity tests.
+// digits (32-byte little-endian scalars) make the proof deterministic for parity tests;
+// ZKHIP_R1CS=<circuit.r1cs> checks, before proving, that the .zkey was made from that circuit and
+// that the witness satisfies every constraint (on failure: one line, exit -1, no output files).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +19,7 @@
 #include <unistd.h>
 
 #include "groth16.hpp"
+#include "r1cs_check.hpp"
 #include "zkfile.hpp"
 
 namespace {
@@ -80,6 +83,32 @@ struct Lap {
     }
 };
 
+// ZKHIP_R1CS: the .r1cs must be the zkey's circuit (A and B as linear maps, zk_r1cs_match_zkey) and the witness must
+// satisfy it (zk_r1cs_check), on the device the prover will use; the checker is gone before the prover is created
+void check_against_r1cs(const char *r1csPath, BinFileUtils::BinFile &zkey, const ZKeyUtils::Header &zh, const uint8_t *witness) {
+    int32_t device = -1;
+    if (const char *dev = getenv("ZKHIP_DEVICE")) device = atoi(dev);
+    else if (const char *devs = getenv("ZKHIP_DEVICES")) {
+        const std::vector<int32_t> list = Groth16::parseDeviceList(devs);
+        if (!list.empty()) device = list[0];
+    }
+    R1csCheck::Checker checker(r1csPath, device);
+    zk_zkey_view v{};
+    v.nVars = zh.nVars;
+    v.nPublic = zh.nPublic;
+    v.domainSize = zh.domainSize;
+    v.nCoefs = zh.nCoefs;
+    v.coefs = zkey.getSectionData(4);
+    v.coefs_bytes = zkey.getSectionSize(4);
+    uint64_t differ = 0;
+    uint32_t first = 0;
+    if (zk_r1cs_match_zkey(checker.h, &v, &differ, &first) != 0) throw std::runtime_error(zk_last_error());
+    if (differ)
+        throw std::runtime_error("r1cs does not match the zkey: row " + std::to_string(first) + " differs (" + std::to_string(differ) + " rows)");
+    const zk_r1cs_report rep = checker.check(witness, zh.nVars);
+    if (!R1csCheck::passed(rep)) throw std::runtime_error(R1csCheck::first_problem(rep, checker.header->nConstraints));
+}
+
 int run(const std::string &zkeyPath, const std::string &wtnsPath, const std::string &proofPath, const std::string &publicPath) {
     Lap lap;
     auto zkey = BinFileUtils::openExisting(zkeyPath, "zkey", 1);
@@ -94,6 +123,10 @@ int run(const std::string &zkeyPath, const std::string &wtnsPath, const std::str
         throw std::invalid_argument("witness does not match the zkey (nVars)");
 
     lap("open zkey + wtns");
+    if (const char *r1csPath = getenv("ZKHIP_R1CS")) {
+        check_against_r1cs(r1csPath, *zkey, *zh, static_cast<const uint8_t *>(wtns->getSectionData(2)));
+        lap("r1cs check");
+    }
     uint64_t bytes[6];
     for (uint32_t sec = 4; sec <= 9; sec++) bytes[sec - 4] = zkey->getSectionSize(sec);
     auto prover = Groth16::makeProver(zh->nVars, zh->nPublic, zh->domainSize, zh->nCoefs, zh->vk_alpha1, zh->vk_beta1, zh->vk_beta2,

@@ -168,3 +168,24 @@ std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f) {
 }
 
 }   // namespace WtnsUtils
+
+namespace R1csUtils {
+
+std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f) {
+    static constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
+                                            0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
+    if (f->hasSection(4) || f->hasSection(5)) throw std::invalid_argument("r1cs custom gates are not supported: Groth16 cannot use them");
+    auto h = std::make_unique<Header>();
+    f->startReadSection(1);
+    h->n8 = read_field_modulus(*f, h->prime, "r1cs");
+    if (memcmp(h->prime.data(), kBn254R, sizeof kBn254R) != 0) throw std::invalid_argument("r1cs curve not supported");
+    for (uint32_t *dst : {&h->nWires, &h->nPubOut, &h->nPubIn, &h->nPrvIn}) *dst = f->readU32LE();
+    h->nLabels = f->readU64LE();
+    h->nConstraints = f->readU32LE();
+    f->endReadSection();
+    h->constraints = f->getSectionData(2);
+    h->constraintsBytes = f->getSectionSize(2);
+    return h;
+}
+
+}   // namespace R1csUtils

@@ -40,6 +40,7 @@ public:
     // random access
     void *getSectionData(uint32_t sectionId, uint32_t sectionPos = 0);
     uint64_t getSectionSize(uint32_t sectionId, uint32_t sectionPos = 0);
+    bool hasSection(uint32_t sectionId) const { return index_.count(sectionId) != 0; }
 
 private:
     struct Extent {
@@ -92,3 +93,21 @@ public:
 std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f);
 
 }   // namespace WtnsUtils
+
+namespace R1csUtils {
+
+// circom .r1cs section 1 + the extent of section 2 (constraints, left encoded: libzkhip decodes it on the device).
+// Not read by the reference; refuses other primes ("r1cs curve not supported") and custom gates (sections 4 / 5).
+class Header {
+public:
+    uint32_t n8 = 0;
+    std::array<uint8_t, 32> prime{};
+    uint32_t nWires = 0, nPubOut = 0, nPubIn = 0, nPrvIn = 0;
+    uint64_t nLabels = 0;
+    uint32_t nConstraints = 0;
+    const void *constraints = nullptr;
+    uint64_t constraintsBytes = 0;
+};
+std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f);
+
+}   // namespace R1csUtils

@@ -52,6 +52,16 @@ class zk_prover_plan(C.Structure):
                 ("bucket_sets_h", C.c_uint32), ("bucket_sets_w", C.c_uint32)]
 
 
+class zk_r1cs_view(C.Structure):
+    _fields_ = [("nWires", C.c_uint32), ("nPubOut", C.c_uint32), ("nPubIn", C.c_uint32), ("nPrvIn", C.c_uint32),
+                ("nConstraints", C.c_uint32), ("constraints", C.c_void_p), ("constraints_bytes", C.c_uint64)]
+
+
+class zk_r1cs_report(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("failed", C.c_uint64), ("first_failed", C.c_uint32), ("a", C.c_uint8 * 32),
+                ("b", C.c_uint8 * 32), ("c", C.c_uint8 * 32), ("one_ok", C.c_uint32), ("first_unreduced", C.c_uint32)]
+
+
 def prover_info(lib, handle):
     """zk_prover_info -> dict: the launch plan zk_prover_create chose (window bits, A|B1|C in one launch, lanes, depths)."""
     plan = zk_prover_plan()
@@ -83,7 +93,8 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_fq_mul_vec", "zk_fr_coef_accumulate", "zk_fr_ntt", "zk_fr_abc_to_h", "zk_msm_g1", "zk_msm_g2", "zk_proof_to_json",
            "zk_public_to_json", "zk_synth_chain_g1", "zk_synth_chain_g2", "zk_fixed_base_g1", "zk_fixed_base_g2", "zk_g1_mul", "zk_g2_mul", "zk_assemble",
            "zk_multi_prover_create", "zk_multi_prover_destroy", "zk_multi_prove", "zk_multi_prove_submit", "zk_multi_prove_collect",
-           "zk_multi_prover_info", "zk_shard_info", "zk_shard_set_exchange", "zk_shard_begin", "zk_shard_step"]
+           "zk_multi_prover_info", "zk_shard_info", "zk_shard_set_exchange", "zk_shard_begin", "zk_shard_step",
+           "zk_r1cs_create", "zk_r1cs_destroy", "zk_r1cs_check", "zk_r1cs_check_dev", "zk_r1cs_match_zkey"]
 
 
 def load_library():
@@ -158,6 +169,13 @@ def load_library():
     lib.zk_proof_to_json.restype = C.c_size_t
     lib.zk_public_to_json.argtypes = [u8p, C.c_uint32, C.c_char_p, C.c_size_t]
     lib.zk_public_to_json.restype = C.c_size_t
+    if hasattr(lib, "zk_r1cs_create"):
+        lib.zk_r1cs_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(zk_r1cs_view), C.c_int32]
+        lib.zk_r1cs_destroy.argtypes = [C.c_void_p]
+        lib.zk_r1cs_destroy.restype = None
+        lib.zk_r1cs_check.argtypes = [C.c_void_p, u8p, C.c_uint32, C.POINTER(zk_r1cs_report)]
+        lib.zk_r1cs_check_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(zk_r1cs_report)]
+        lib.zk_r1cs_match_zkey.argtypes = [C.c_void_p, C.POINTER(zk_zkey_view), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     _LIB = lib
     return lib
 

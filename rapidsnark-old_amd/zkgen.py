@@ -264,7 +264,7 @@ def generate(k, n_public=2, seed=0, circuit_like=False, semaphore_like=False):
         "pointsC": L.fixed_base_g1(g1, c_sc), "pointsH": L.fixed_base_g1(g1, hs), "pointsIC": L.fixed_base_g1(g1, ic_sc),
         "vk_alpha1": u8(L.g1_mul(g1, alpha)), "vk_beta1": u8(L.g1_mul(g1, beta)), "vk_beta2": u8(L.g2_mul(g2, beta)),
         "vk_gamma2": u8(L.g2_mul(g2, gamma)), "vk_delta1": u8(L.g1_mul(g1, delta)), "vk_delta2": u8(L.g2_mul(g2, delta)),
-        "witness": w,
+        "witness": w, "nConstraints": m, "nInputs": n_in,
         "trap": {"toxic": (tau, alpha, beta, gamma, delta), "At": at, "Bt": bt, "Ct": ct.reshape(-1), "K": kk},
     }
     return out
@@ -318,6 +318,30 @@ def write_wtns(key, path):
     with open(path, "wb") as f:
         for p in _binfile(b"wtns", 2, [(1, sec1), (2, key["witness"])]):
             f.write(p)
+
+
+def write_r1cs(key, path):
+    """The key's circuit as circom's .r1cs (rapidsnark-old_amd/r1cs.py): A and B from the coefficient records (value * R^2 ->
+    standard on the GPU, snarkjs's public-input rows dropped), C = the one output signal each constraint defines."""
+    from . import r1cs
+    m, n_in, n_vars = key["nConstraints"], key["nInputs"], key["nVars"]
+    rec = np.frombuffer(np.ascontiguousarray(key["coefs"]).tobytes()[4:], dtype=synth.COEF_DTYPE)
+    rec = rec[rec["c"] < m]
+    one = _const(1, rec.size)
+    std = _mul(_mul(np.ascontiguousarray(rec["v"]).reshape(-1), one), one).reshape(-1, 32)
+    mats = []
+    for mat in (0, 1):
+        sel = np.nonzero(rec["m"] == mat)[0]
+        sel = sel[np.argsort(rec["c"][sel], kind="stable")]
+        rowptr = np.zeros(m + 1, dtype=np.int64)
+        np.cumsum(np.bincount(rec["c"][sel], minlength=m), out=rowptr[1:])
+        mats.append((rowptr, rec["s"][sel], std[sel]))
+    c_coef = np.zeros((m, 32), dtype=np.uint8)
+    c_coef[:, 0] = 1
+    mats.append((np.arange(m + 1, dtype=np.int64), (1 + n_in + np.arange(m)).astype(np.uint32), c_coef))
+    data = r1cs.write_r1cs(mats[0], mats[1], mats[2], n_vars, 0, key["nPublic"], n_in - key["nPublic"])
+    with open(path, "wb") as f:
+        f.write(data)
 
 
 def _fq_std(mont_bytes):

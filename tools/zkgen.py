@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """zkgen — write a trapdoor-VALID Groth16 key at a benchmark size (needs a GPU).
 
-    python tools/zkgen.py <log2n> <outdir> [--npublic N] [--seed S] [--circuit-like | --semaphore-like] [--prove]
+    python tools/zkgen.py <log2n> <outdir> [--npublic N] [--seed S] [--circuit-like | --semaphore-like] [--r1cs] [--prove]
 
 Writes <outdir>/circuit.zkey, witness.wtns, verification_key.json, toxic.json (see
-rapidsnark-old_amd/zkgen.py).  --prove also runs the one-shot CLI `prover` on the written files with a
+rapidsnark-old_amd/zkgen.py); --r1cs also the circuit as circom's circuit.r1cs (for `wtnscheck` / ZKHIP_R1CS).  --prove also runs the one-shot CLI `prover` on the written files with a
 fixed (r, s), writes proof.json / public.json, and checks the proof against the discrete logs
 computed from the toxic waste (pairing-free trapdoor check).  Off-box:
     snarkjs groth16 verify verification_key.json public.json proof.json
@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--npublic", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--prove", action="store_true")
+    ap.add_argument("--r1cs", action="store_true", help="also write the circuit as circuit.r1cs (zkgen.write_r1cs)")
     ap.add_argument("--circuit-like", action="store_true", help="nVars = 3/4 of the domain + 5, 80 %% boolean signals, all-zero table rows (zkgen.generate)")
     ap.add_argument("--semaphore-like", action="store_true", help="the shape class of Semaphore / iden3 auth: chains of x^5 S-box rounds between Merkle-style muxes, "
                                                                   "nearly every signal full-size (zkgen.generate; use --npublic 4)")
@@ -37,6 +38,8 @@ def main():
     t_gen = time.time() - t
     t = time.time()
     zkgen.write_all(key, args.outdir)
+    if args.r1cs:
+        zkgen.write_r1cs(key, os.path.join(args.outdir, "circuit.r1cs"))
     print("generated 2^%d key in %.1f s (nVars %d, nCoefs %d), wrote files in %.1f s" % (args.log2n, t_gen, key["nVars"], key["nCoefs"], time.time() - t))
     if args.prove:
         r, s = 0x0123456789ABCDEF, (1 << 200) + 12345
