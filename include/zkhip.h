@@ -330,6 +330,49 @@ int zk_r1cs_check_dev(zk_r1cs *r, const void *d_wtns, uint32_t nVars, zk_r1cs_re
  * undetected with probability ~1/r.  C is not in a .zkey, so the match cannot cover it.  first_row: UINT32_MAX = none. */
 int zk_r1cs_match_zkey(zk_r1cs *r, const zk_zkey_view *zkey, uint64_t *rows_differing, uint32_t *first_row);
 
+/* ---- Groth16 setup: a .zkey from circom's .r1cs and a prepared Powers of Tau file -------- */
+/* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
+ * counterpart is snarkjs `groth16 setup circuit.r1cs pot.ptau circuit_0000.zkey` (alias `zkey new`): the phase-2 starting
+ * key, gamma = delta = 1.  zk_ptau_view: the .ptau's power, alpha1 (section 4 point 0), beta1 (section 5 point 0), beta2
+ * (section 6) and the Lagrange-basis sections 12 (tauG1), 13 (tauG2), 14 (alphaTauG1), 15 (betaTauG1) that `powersoftau
+ * prepare phase2` writes, as pointers and byte sizes into the mapped file: points as in a .zkey, level p of a section
+ * (2^p points) starts at point 2^p - 1; section 12 holds levels 0 .. power + 1, the others 0 .. power.  NULL section
+ * pointers: the file is not prepared for phase 2.  Only levels k and k + 1 of section 12 and level k of the others are
+ * read (2^k: the circuit's domain), never a whole section. */
+typedef struct zk_ptau_view {
+    uint32_t power;
+    const void *alpha1, *beta1, *beta2;     /* G1, G1, G2 */
+    const void *lagrange_g1, *lagrange_g2, *lagrange_alpha_g1, *lagrange_beta_g1;   /* sections 12, 13, 14, 15 */
+    uint64_t lagrange_g1_bytes, lagrange_g2_bytes, lagrange_alpha_g1_bytes, lagrange_beta_g1_bytes;
+} zk_ptau_view;
+/* What the key of this circuit holds: nVars = nWires, nPublic = nPubOut + nPubIn, domainSize = 2^k (the smallest power
+ * of two >= nConstraints + nPublic + 1, at least 2), nCoefs = A and B terms of the .r1cs + nPublic + 1 public-input rows. */
+typedef struct zk_setup_sizes {
+    uint32_t nVars, nPublic, domainSize, log_domain;
+    uint64_t nCoefs;
+} zk_setup_sizes;
+/* Caller buffers of zkey sections 3 to 9, sized from zk_setup_sizes.  Section 4 holds the records in a fixed order: the A
+ * terms constraint by constraint (file order within a constraint), then the public-input rows (A, constraint
+ * nConstraints + i, wire i, value 1, i = 0 .. nPublic), then the B terms constraint by constraint. */
+typedef struct zk_setup_out {
+    uint8_t *coefs;          /* section 4: 4 + nCoefs x 44 bytes, its leading u32 count included (values: value * R^2 mod r) */
+    uint8_t *pointsIC;       /* section 3: (nPublic + 1) x 64 */
+    uint8_t *pointsA;        /* section 5: nVars x 64 */
+    uint8_t *pointsB1;       /* section 6: nVars x 64 */
+    uint8_t *pointsB2;       /* section 7: nVars x 128 */
+    uint8_t *pointsC;        /* section 8: (nVars - nPublic - 1) x 64 */
+    uint8_t *pointsH;        /* section 9: domainSize x 64 */
+} zk_setup_out;
+/* Checks both files against each other without touching a device: the circuit needs 2^k and the .ptau holds 2^power
+ * (k > power), k > 27 (the prover's limit), a .ptau not prepared for phase 2, a Lagrange section shorter than its power
+ * needs, a .r1cs section that does not walk.  Returns 0 and the sizes, or an error with its message. */
+int zk_groth16_setup_sizes(const zk_r1cs_view *r1cs, const zk_ptau_view *ptau, zk_setup_sizes *sizes);
+/* The key's sections 3 to 9 on `device` (-1: the current one).  Section 2 is the caller's: nVars, nPublic, domainSize,
+ * alpha1, beta1, beta2 from the .ptau, gamma2 = delta2 = the G2 generator, delta1 = the G1 generator.  Free HBM is
+ * checked before anything is allocated (out of memory is an error, never a half-made key).  Wire ids and coefficients are
+ * range-checked as by zk_r1cs_create. */
+int zk_groth16_setup(const zk_r1cs_view *r1cs, const zk_ptau_view *ptau, int32_t device, zk_setup_out *out);
+
 #ifdef __cplusplus
 }
 #endif

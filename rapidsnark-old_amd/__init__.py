@@ -14,5 +14,6 @@ from .lib import (ZkHipError, load_library, library_path, fr_mul_vec, fq_mul_vec
                   synth_chain_g1, synth_chain_g2, fixed_base_g1, fixed_base_g2, g1_mul, g2_mul, assemble, PinnedBuffer)
 from .prover import Prover, MultiProver, prove_files                 # noqa: F401
 from .r1cs import R1cs, R1csReport, write_r1cs                      # noqa: F401
+from .ptau import PtauFile, groth16_setup, write_trapdoor_ptau      # noqa: F401
 from . import synth                                     # noqa: F401
 from .dist import gather_partials, ShardedChain                        # noqa: F401

@@ -476,4 +476,17 @@ struct DirectProof {
 void collect_sums(zk_prover *p, zk_msm_sums *out, SubmittedRS *rs = nullptr, const DirectProof *direct = nullptr);
 void prove_finish(zk_prover *p, const zk_msm_sums *parts, uint32_t nparts, const uint8_t *r32, const uint8_t *s32, zk_proof *out);
 
+// ---- r1cs.hip, shared with setup.hip: the one host pass over a .r1cs constraints section and the segment plan of the
+// cut-into-segments sums (rows of any length -> segments of at most SEG_TERMS inputs, one lane each, pass after pass)
+constexpr uint32_t SEG_TERMS = 16;
+constexpr uint64_t SEG_FINAL = 1ull << 63;          // segment destination: a row value, not a partial of the next pass
+struct SegPass {
+    DevBuf<uint64_t> lo, dest;                      // nseg + 1 bounds into this pass's input, nseg destinations
+    uint64_t nseg = 0;
+};
+// word offset of every linear combination (3m: A rows, then B, then C) and the row offsets of their terms (3m + 1)
+void walk_constraints(const zk_r1cs_view *v, std::vector<uint64_t> &lc_off, std::vector<uint64_t> &rowptr);
+// the passes over rows with the given offsets; max_part: partials the even / odd passes write
+void plan_segments(const std::vector<uint64_t> &rowptr, std::vector<std::unique_ptr<SegPass>> &passes, uint64_t max_part[2]);
+
 }   // namespace zkp

@@ -26,9 +26,9 @@
 
 namespace {
 
-constexpr uint32_t SEG = 16;                 // terms (or partials) one lane sums
+constexpr uint32_t SEG = SEG_TERMS;          // terms (or partials) one lane sums
 constexpr uint32_t LAZY = 7;                 // additions between two reductions (bound above)
-constexpr uint64_t FINAL = 1ull << 63;       // segment destination: a row value, not a partial of the next pass
+constexpr uint64_t FINAL = SEG_FINAL;        // segment destination: a row value, not a partial of the next pass
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
 __device__ __forceinline__ Fr r_load(const Fr *p) {
@@ -196,10 +196,7 @@ __global__ __launch_bounds__(256) void k_r1cs_match(unsigned long long *differ, 
 inline uint32_t blocks(uint64_t n) { return (uint32_t)((n + 255) / 256); }
 inline uint32_t strided(uint64_t n) { return n < 256ull * 1024 ? blocks(n) : 1024; }     // the three reporting kernels
 
-struct Pass {                                  // one pass of the segmented sum
-    DevBuf<uint64_t> lo, dest;
-    uint64_t nseg = 0;
-};
+typedef SegPass Pass;                          // one pass of the segmented sum
 
 }   // namespace
 
@@ -259,7 +256,7 @@ struct zk_r1cs {
     }
 };
 
-namespace {
+namespace zkp {
 
 // The one host pass over section 2: word offset and term count of every linear combination, checked against the section size
 void walk_constraints(const zk_r1cs_view *v, std::vector<uint64_t> &lc_off, std::vector<uint64_t> &rowptr) {
@@ -284,15 +281,15 @@ void walk_constraints(const zk_r1cs_view *v, std::vector<uint64_t> &lc_off, std:
     for (uint64_t r = 0; r < 3 * m; r++) rowptr[r + 1] = rowptr[r] + len[r];
 }
 
-// Segments of every pass (host, create time).  Pass 0's input is the terms of all 3m rows in order; a row of L inputs
+// Segments of every pass (host, create time).  Pass 0's input is the terms of all rows in order; a row of L inputs
 // gets max(1, ceil(L / SEG)) segments; the rows with several go on to the next pass with one input per segment.
-void plan_passes(zk_r1cs *r, const std::vector<uint64_t> &rowptr) {
+void plan_segments(const std::vector<uint64_t> &rowptr, std::vector<std::unique_ptr<SegPass>> &passes, uint64_t max_part[2]) {
     struct Open {
         uint32_t row;
         uint64_t base, len;
     };
     std::vector<Open> cur, nxt;
-    uint64_t max_part[2] = {0, 0};
+    max_part[0] = max_part[1] = 0;
     for (int level = 0;; level++) {
         std::vector<uint64_t> lo, dest;
         uint64_t npos = 0, end = 0;
@@ -325,11 +322,20 @@ void plan_passes(zk_r1cs *r, const std::vector<uint64_t> &rowptr) {
         p->dest.alloc(dest.size());
         HIP_TRY(hipMemcpy(p->lo.p, lo.data(), lo.size() * 8, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(p->dest.p, dest.data(), dest.size() * 8, hipMemcpyHostToDevice));
-        r->passes.push_back(std::move(p));
+        passes.push_back(std::move(p));
         if (npos > max_part[level & 1]) max_part[level & 1] = npos;
         if (nxt.empty()) break;
         cur.swap(nxt);
     }
+}
+
+}   // namespace zkp
+
+namespace {
+
+void plan_passes(zk_r1cs *r, const std::vector<uint64_t> &rowptr) {
+    uint64_t max_part[2];
+    plan_segments(rowptr, r->passes, max_part);
     for (int k = 0; k < 2; k++) r->part[k].alloc(max_part[k] ? max_part[k] : 1);
 }
 

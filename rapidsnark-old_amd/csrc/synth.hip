@@ -116,6 +116,18 @@ void launch_fixed_base_g2(G2Affine *d_out, G2XYZZ *d_tmp, Fq2 *d_pref, const G2A
     fixed_base<Fq2>(d_out, d_tmp, d_pref, B, d_scalars, n, s);
 }
 
+// XYZZ -> affine (all-zero for infinity) of n points another kernel left in d_tmp: the chains' batched normalisation
+void launch_normalize_g1(G1Affine *d_out, const G1XYZZ *d_tmp, Fq *d_pref, uint64_t n, hipStream_t s) {
+    const uint64_t segs = (n + CHAIN_SEG - 1) / CHAIN_SEG;
+    if (segs) ZK_LAUNCH(k_chain_normalize<Fq>, dim3((uint32_t)((segs + 63) / 64)), dim3(64), 0, s, d_out, d_tmp, d_pref, n);
+    ZK_LAUNCH_OK("normalize g1");
+}
+void launch_normalize_g2(G2Affine *d_out, const G2XYZZ *d_tmp, Fq2 *d_pref, uint64_t n, hipStream_t s) {
+    const uint64_t segs = (n + CHAIN_SEG - 1) / CHAIN_SEG;
+    if (segs) ZK_LAUNCH(k_chain_normalize<Fq2>, dim3((uint32_t)((segs + 63) / 64)), dim3(64), 0, s, d_out, d_tmp, d_pref, n);
+    ZK_LAUNCH_OK("normalize g2");
+}
+
 void launch_chain_g1(G1Affine *d_out, G1XYZZ *d_tmp, Fq *d_pref, const G1Affine &P0, const G1Affine &Q, uint64_t n, hipStream_t s) {
     chain<Fq>(d_out, d_tmp, d_pref, P0, Q, n, s);
 }

@@ -1,0 +1,175 @@
+// zkeynew <circuit.r1cs> <pot.ptau> <circuit.zkey> [verification_key.json]
+//
+// The phase-2 starting key of a circom circuit from a prepared Powers of Tau file, on the GPU (libzkhip
+// zk_groth16_setup): what snarkjs `groth16 setup` (alias `zkey new`) writes, gamma = delta = 1, with section 10 (csHash and
+// contributions) all zero.  The reference has no such program.  Both files are read and checked against each other
+// before the device is touched; the outputs are written to temporary names and renamed at the end, so that a failure
+// leaves no file behind.  Exit codes: 0, or 255 with a message on stderr (as `prover`).  ZKHIP_DEVICE=<n> picks the device.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/zkhip.h"
+#include "../csrc/common.hpp"
+#include "../csrc/field64.hpp"
+#include "zkfile.hpp"
+
+namespace {
+
+constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
+                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
+
+// Montgomery bytes of a standard-form Fq constant given as little-endian 64-bit limbs
+void fq_mont(uint8_t *out, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+    zk::Fq64 x;
+    x.v[0] = a; x.v[1] = b; x.v[2] = c; x.v[3] = d;
+    x = zk::Fq64::to_mont(x);
+    memcpy(out, x.v, 32);
+}
+// the generators of G1, (1, 2), and of G2 (EIP-197), affine Montgomery: gamma2 = delta2 = G2, delta1 = G1
+void generators(uint8_t g1[64], uint8_t g2[128]) {
+    fq_mont(g1, 1, 0, 0, 0);
+    fq_mont(g1 + 32, 2, 0, 0, 0);
+    fq_mont(g2, 0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull);
+    fq_mont(g2 + 32, 0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull);
+    fq_mont(g2 + 64, 0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
+    fq_mont(g2 + 96, 0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
+}
+
+// a file written under a temporary name, renamed by commit(), removed otherwise
+struct OutFile {
+    std::string path, tmp;
+    std::ofstream f;
+    bool done = false;
+    explicit OutFile(const std::string &p) : path(p), tmp(p + ".partial") {
+        f.open(tmp, std::ios::binary | std::ios::trunc);
+        if (!f) throw std::runtime_error("cannot write " + path);
+    }
+    void write(const void *p, uint64_t n) { f.write(static_cast<const char *>(p), (std::streamsize)n); }
+    void u32(uint32_t v) { write(&v, 4); }
+    void section(uint32_t id, uint64_t size) {
+        u32(id);
+        write(&size, 8);
+    }
+    void commit() {
+        f.close();
+        if (!f) throw std::runtime_error("cannot write " + path);
+        if (rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("cannot write " + path);
+        done = true;
+    }
+    ~OutFile() {
+        if (!done) {
+            f.close();
+            remove(tmp.c_str());
+        }
+    }
+};
+
+std::string g1_json(const uint8_t *p) {
+    return "[\"" + zk::HostTail::fq_mont_to_dec(p) + "\", \"" + zk::HostTail::fq_mont_to_dec(p + 32) + "\", \"1\"]";
+}
+std::string g2_json(const uint8_t *p) {
+    auto d = [&](int i) { return "\"" + zk::HostTail::fq_mont_to_dec(p + 32 * i) + "\""; };
+    return "[[" + d(0) + ", " + d(1) + "], [" + d(2) + ", " + d(3) + "], [\"1\", \"0\"]]";
+}
+
+int run(const std::string &r1csPath, const std::string &ptauPath, const std::string &zkeyPath, const std::string &vkPath) {
+    // both files are read and checked against each other before the device is touched
+    auto r1cs = BinFileUtils::openExisting(r1csPath, "r1cs", 1);
+    auto rh = R1csUtils::loadHeader(r1cs.get());
+    auto ptau = BinFileUtils::openExisting(ptauPath, "ptau", 1);
+    auto ph = PtauUtils::loadHeader(ptau.get());
+    zk_r1cs_view rv{rh->nWires, rh->nPubOut, rh->nPubIn, rh->nPrvIn, rh->nConstraints, rh->constraints, rh->constraintsBytes};
+    zk_ptau_view pv{};
+    pv.power = ph->power;
+    pv.alpha1 = ph->alpha1;
+    pv.beta1 = ph->beta1;
+    pv.beta2 = ph->beta2;
+    pv.lagrange_g1 = ph->lagrange[0];
+    pv.lagrange_g2 = ph->lagrange[1];
+    pv.lagrange_alpha_g1 = ph->lagrange[2];
+    pv.lagrange_beta_g1 = ph->lagrange[3];
+    pv.lagrange_g1_bytes = ph->lagrangeBytes[0];
+    pv.lagrange_g2_bytes = ph->lagrangeBytes[1];
+    pv.lagrange_alpha_g1_bytes = ph->lagrangeBytes[2];
+    pv.lagrange_beta_g1_bytes = ph->lagrangeBytes[3];
+    zk_setup_sizes sz{};
+    if (zk_groth16_setup_sizes(&rv, &pv, &sz) != 0) throw std::invalid_argument(zk_last_error());
+
+    const uint64_t nv = sz.nVars, np1 = (uint64_t)sz.nPublic + 1, n = sz.domainSize;
+    std::vector<uint8_t> coefs(4 + 44 * sz.nCoefs), ic(np1 * 64), a(nv * 64), b1(nv * 64), b2(nv * 128), c((nv - np1) * 64), h(n * 64);
+    zk_setup_out out{coefs.data(), ic.data(), a.data(), b1.data(), b2.data(), c.empty() ? nullptr : c.data(), h.data()};
+    const char *dev = getenv("ZKHIP_DEVICE");
+    if (zk_groth16_setup(&rv, &pv, dev ? atoi(dev) : -1, &out) != 0) throw std::runtime_error(zk_last_error());
+
+    uint8_t g1[64], g2[128];
+    generators(g1, g2);
+    OutFile z(zkeyPath);
+    z.write("zkey", 4);
+    z.u32(1);
+    z.u32(10);
+    z.section(1, 4);
+    z.u32(1);                                             // Groth16
+    z.section(2, 4 + 32 + 4 + 32 + 12 + 64 + 64 + 128 + 128 + 64 + 128);
+    z.u32(32);
+    z.write(ph->q.data(), 32);
+    z.u32(32);
+    z.write(kBn254R, 32);
+    z.u32(sz.nVars);
+    z.u32(sz.nPublic);
+    z.u32(sz.domainSize);
+    z.write(ph->alpha1, 64);
+    z.write(ph->beta1, 64);
+    z.write(ph->beta2, 128);
+    z.write(g2, 128);                                     // gamma2
+    z.write(g1, 64);                                      // delta1
+    z.write(g2, 128);                                     // delta2
+    const struct {
+        uint32_t id;
+        const std::vector<uint8_t> &v;
+    } secs[] = {{3, ic}, {4, coefs}, {5, a}, {6, b1}, {7, b2}, {8, c}, {9, h}};
+    for (const auto &s : secs) {
+        z.section(s.id, s.v.size());
+        z.write(s.v.data(), s.v.size());
+    }
+    const uint8_t sec10[68] = {};                          // csHash + 0 contributions (not computed: see INTEGRATION.md)
+    z.section(10, sizeof sec10);
+    z.write(sec10, sizeof sec10);
+
+    std::unique_ptr<OutFile> vk;
+    if (!vkPath.empty()) {
+        vk.reset(new OutFile(vkPath));
+        std::string j = "{\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\",\n \"nPublic\": " + std::to_string(sz.nPublic) + ",\n";
+        j += " \"vk_alpha_1\": " + g1_json(static_cast<const uint8_t *>(ph->alpha1)) + ",\n";
+        j += " \"vk_beta_2\": " + g2_json(static_cast<const uint8_t *>(ph->beta2)) + ",\n";
+        j += " \"vk_gamma_2\": " + g2_json(g2) + ",\n \"vk_delta_2\": " + g2_json(g2) + ",\n \"IC\": [";
+        for (uint64_t i = 0; i < np1; i++) j += std::string(i ? ",\n  " : "\n  ") + g1_json(ic.data() + 64 * i);
+        j += "\n ]\n}";
+        vk->write(j.data(), j.size());
+    }
+    z.commit();
+    if (vk) vk->commit();
+    std::cerr << "zkeynew: 2^" << sz.log_domain << " domain, " << sz.nVars << " wires, " << sz.nCoefs << " coefficients\n";
+    return 0;
+}
+
+}   // namespace
+
+int main(int argc, char **argv) {
+    if (argc != 4 && argc != 5) {
+        std::cerr << "Invalid number of parameters:\n";
+        std::cerr << "Usage: zkeynew <circuit.r1cs> <pot.ptau> <circuit.zkey> [verification_key.json]\n";
+        return -1;
+    }
+    try {
+        return run(argv[1], argv[2], argv[3], argc == 5 ? argv[4] : "");
+    } catch (std::exception &e) {
+        std::cerr << e.what() << '\n';
+        return -1;
+    }
+}

@@ -1,5 +1,8 @@
 #include "zkfile.hpp"
 
+#include "../csrc/field64.hpp"         // libzkhip's host field: the .ptau header's curve-membership check
+#include "../csrc/curve.hpp"
+
 #include <cerrno>
 #include <cstring>
 #include <fcntl.h>
@@ -189,3 +192,80 @@ std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f) {
 }
 
 }   // namespace R1csUtils
+
+namespace PtauUtils {
+
+namespace {
+
+typedef zk::Fp2T<zk::Fq64> Fq2h;
+
+zk::Fq64 fq_load(const uint8_t *p) {
+    zk::Fq64 x;
+    memcpy(x.v, p, 32);
+    return x;
+}
+// a standard-form constant as little-endian 64-bit limbs -> Montgomery
+zk::Fq64 fq_mont(uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+    zk::Fq64 x;
+    x.v[0] = a; x.v[1] = b; x.v[2] = c; x.v[3] = d;
+    return zk::Fq64::to_mont(x);
+}
+bool below_q(const uint8_t *p) {
+    uint64_t v[4];
+    memcpy(v, p, 32);
+    return !zk::Fq64::geq_p(v);
+}
+
+// y^2 = x^3 + b with b = 3 (G1) or 3 / (9 + u) (the G2 twist); the all-zero encoding (infinity) is refused
+template <class F>
+bool on_curve(const F &x, const F &y, const F &b) {
+    return F::sqr(y) == F::add(F::mul(F::sqr(x), x), b);
+}
+bool g1_ok(const uint8_t *p) {
+    if (!below_q(p) || !below_q(p + 32)) return false;
+    const zk::Fq64 x = fq_load(p), y = fq_load(p + 32);
+    if (x.is_zero() && y.is_zero()) return false;
+    return on_curve(x, y, fq_mont(3, 0, 0, 0));
+}
+bool g2_ok(const uint8_t *p) {
+    for (int i = 0; i < 4; i++)
+        if (!below_q(p + 32 * i)) return false;
+    const Fq2h x{fq_load(p), fq_load(p + 32)}, y{fq_load(p + 64), fq_load(p + 96)};
+    if (x.is_zero() && y.is_zero()) return false;
+    // 3 / (9 + u) = 19485874751759354771024239261021720505790618469301721065564631296452457478373
+    //             + 266929791119991161246907387137283842545076965332900288569378510910307636690 u
+    const Fq2h b{fq_mont(0x3267e6dc24a138e5ull, 0xb5b4c5e559dbefa3ull, 0x81be18991be06ac3ull, 0x2b149d40ceb8aaaeull),
+                 fq_mont(0xe4a2bd0685c315d2ull, 0xa74fa084e52d1852ull, 0xcd2cafadeed8fdf4ull, 0x009713b03af0fed4ull)};
+    return on_curve(x, y, b);
+}
+
+}   // namespace
+
+std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f) {
+    static constexpr uint8_t kBn254Q[32] = {0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
+                                            0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
+    auto h = std::make_unique<Header>();
+    f->startReadSection(1);
+    h->n8 = read_field_modulus(*f, h->q, "ptau");
+    if (memcmp(h->q.data(), kBn254Q, sizeof kBn254Q) != 0) throw std::invalid_argument("ptau curve not supported (q is not BN254's)");
+    h->power = f->readU32LE();
+    h->ceremonyPower = f->readU32LE();
+    f->endReadSection(false);
+    struct { int id; uint64_t bytes; const void **slot; const char *name; } const pts[] = {
+        {4, 64, &h->alpha1, "alphaTauG1[0]"}, {5, 64, &h->beta1, "betaTauG1[0]"}, {6, 128, &h->beta2, "betaG2"}};
+    for (const auto &p : pts) {
+        if (!f->hasSection(p.id)) throw std::invalid_argument("ptau has no section " + std::to_string(p.id));
+        if (f->getSectionSize(p.id) < p.bytes) throw std::invalid_argument("ptau section " + std::to_string(p.id) + " is short");
+        *p.slot = f->getSectionData(p.id);
+        const uint8_t *b = static_cast<const uint8_t *>(*p.slot);
+        if (!(p.bytes == 64 ? g1_ok(b) : g2_ok(b))) throw std::invalid_argument(std::string("ptau ") + p.name + " is not a point of the curve");
+    }
+    for (int i = 0; i < 4; i++)
+        if (f->hasSection(12 + i)) {
+            h->lagrangeBytes[i] = f->getSectionSize(12 + i);
+            h->lagrange[i] = h->lagrangeBytes[i] ? f->getSectionData(12 + i) : nullptr;
+        }
+    return h;
+}
+
+}   // namespace PtauUtils

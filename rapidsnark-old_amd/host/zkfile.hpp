@@ -111,3 +111,23 @@ public:
 std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f);
 
 }   // namespace R1csUtils
+
+namespace PtauUtils {
+
+// A Powers of Tau file (snarkjs .ptau, magic "ptau", version 1): section 1 (n8, q, power, ceremonyPower), the points
+// alpha1 = alphaTauG1[0] (section 4), beta1 = betaTauG1[0] (section 5), beta2 (section 6), and the extents of the
+// Lagrange-basis sections 12 to 15 (`powersoftau prepare phase2`; NULL / 0 when the file is not prepared), left in the
+// mapping: only the levels a setup needs are ever read.  Refuses other fields / curves, and alpha1 / beta1 / beta2 that
+// are not points of BN254's G1 / G2 curve (checked here, on the host).
+class Header {
+public:
+    uint32_t n8 = 0;
+    std::array<uint8_t, 32> q{};
+    uint32_t power = 0, ceremonyPower = 0;
+    const void *alpha1 = nullptr, *beta1 = nullptr, *beta2 = nullptr;
+    const void *lagrange[4] = {nullptr, nullptr, nullptr, nullptr};      // sections 12, 13, 14, 15
+    uint64_t lagrangeBytes[4] = {0, 0, 0, 0};
+};
+std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f);
+
+}   // namespace PtauUtils

@@ -62,6 +62,22 @@ class zk_r1cs_report(C.Structure):
                 ("b", C.c_uint8 * 32), ("c", C.c_uint8 * 32), ("one_ok", C.c_uint32), ("first_unreduced", C.c_uint32)]
 
 
+class zk_ptau_view(C.Structure):
+    _fields_ = [("power", C.c_uint32), ("alpha1", C.c_void_p), ("beta1", C.c_void_p), ("beta2", C.c_void_p),
+                ("lagrange_g1", C.c_void_p), ("lagrange_g2", C.c_void_p), ("lagrange_alpha_g1", C.c_void_p), ("lagrange_beta_g1", C.c_void_p),
+                ("lagrange_g1_bytes", C.c_uint64), ("lagrange_g2_bytes", C.c_uint64), ("lagrange_alpha_g1_bytes", C.c_uint64),
+                ("lagrange_beta_g1_bytes", C.c_uint64)]
+
+
+class zk_setup_sizes(C.Structure):
+    _fields_ = [("nVars", C.c_uint32), ("nPublic", C.c_uint32), ("domainSize", C.c_uint32), ("log_domain", C.c_uint32), ("nCoefs", C.c_uint64)]
+
+
+class zk_setup_out(C.Structure):
+    _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
+                ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
+
+
 def prover_info(lib, handle):
     """zk_prover_info -> dict: the launch plan zk_prover_create chose (window bits, A|B1|C in one launch, lanes, depths)."""
     plan = zk_prover_plan()
@@ -94,7 +110,8 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_public_to_json", "zk_synth_chain_g1", "zk_synth_chain_g2", "zk_fixed_base_g1", "zk_fixed_base_g2", "zk_g1_mul", "zk_g2_mul", "zk_assemble",
            "zk_multi_prover_create", "zk_multi_prover_destroy", "zk_multi_prove", "zk_multi_prove_submit", "zk_multi_prove_collect",
            "zk_multi_prover_info", "zk_shard_info", "zk_shard_set_exchange", "zk_shard_begin", "zk_shard_step",
-           "zk_r1cs_create", "zk_r1cs_destroy", "zk_r1cs_check", "zk_r1cs_check_dev", "zk_r1cs_match_zkey"]
+           "zk_r1cs_create", "zk_r1cs_destroy", "zk_r1cs_check", "zk_r1cs_check_dev", "zk_r1cs_match_zkey",
+           "zk_groth16_setup_sizes", "zk_groth16_setup"]
 
 
 def load_library():
@@ -176,6 +193,9 @@ def load_library():
         lib.zk_r1cs_check.argtypes = [C.c_void_p, u8p, C.c_uint32, C.POINTER(zk_r1cs_report)]
         lib.zk_r1cs_check_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(zk_r1cs_report)]
         lib.zk_r1cs_match_zkey.argtypes = [C.c_void_p, C.POINTER(zk_zkey_view), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    if hasattr(lib, "zk_groth16_setup"):
+        lib.zk_groth16_setup_sizes.argtypes = [C.POINTER(zk_r1cs_view), C.POINTER(zk_ptau_view), C.POINTER(zk_setup_sizes)]
+        lib.zk_groth16_setup.argtypes = [C.POINTER(zk_r1cs_view), C.POINTER(zk_ptau_view), C.c_int32, C.POINTER(zk_setup_out)]
     _LIB = lib
     return lib
 

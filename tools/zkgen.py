@@ -2,9 +2,12 @@
 """zkgen — write a trapdoor-VALID Groth16 key at a benchmark size (needs a GPU).
 
     python tools/zkgen.py <log2n> <outdir> [--npublic N] [--seed S] [--circuit-like | --semaphore-like] [--r1cs] [--prove]
+                          [--ptau POWER]
 
 Writes <outdir>/circuit.zkey, witness.wtns, verification_key.json, toxic.json (see
-rapidsnark-old_amd/zkgen.py); --r1cs also the circuit as circom's circuit.r1cs (for `wtnscheck` / ZKHIP_R1CS).  --prove also runs the one-shot CLI `prover` on the written files with a
+rapidsnark-old_amd/zkgen.py); --r1cs also the circuit as circom's circuit.r1cs (for `wtnscheck` / ZKHIP_R1CS); --ptau POWER
+also a prepared Powers of Tau file pot.ptau of that power with the key's own tau, alpha, beta (ptau.write_trapdoor_ptau: a
+test input for `zkeynew`, NOT a ceremony).  --prove also runs the one-shot CLI `prover` on the written files with a
 fixed (r, s), writes proof.json / public.json, and checks the proof against the discrete logs
 computed from the toxic waste (pairing-free trapdoor check).  Off-box:
     snarkjs groth16 verify verification_key.json public.json proof.json
@@ -30,6 +33,7 @@ def main():
     ap.add_argument("--circuit-like", action="store_true", help="nVars = 3/4 of the domain + 5, 80 %% boolean signals, all-zero table rows (zkgen.generate)")
     ap.add_argument("--semaphore-like", action="store_true", help="the shape class of Semaphore / iden3 auth: chains of x^5 S-box rounds between Merkle-style muxes, "
                                                                   "nearly every signal full-size (zkgen.generate; use --npublic 4)")
+    ap.add_argument("--ptau", type=int, metavar="POWER", help="also write pot.ptau of this power from the key's tau, alpha, beta (test input only)")
     args = ap.parse_args()
     import rapidsnark_old_amd as zk
     from rapidsnark_old_amd import zkgen, synth
@@ -41,6 +45,10 @@ def main():
     if args.r1cs:
         zkgen.write_r1cs(key, os.path.join(args.outdir, "circuit.r1cs"))
     print("generated 2^%d key in %.1f s (nVars %d, nCoefs %d), wrote files in %.1f s" % (args.log2n, t_gen, key["nVars"], key["nCoefs"], time.time() - t))
+    if args.ptau is not None:
+        t = time.time()
+        zk.write_trapdoor_ptau(args.ptau, *key["trap"]["toxic"][:3], os.path.join(args.outdir, "pot.ptau"))
+        print("wrote a trapdoor ptau of power %d in %.1f s" % (args.ptau, time.time() - t))
     if args.prove:
         r, s = 0x0123456789ABCDEF, (1 << 200) + 12345
         le = lambda x: int(x).to_bytes(32, "little").hex()
