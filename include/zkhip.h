@@ -373,6 +373,41 @@ int zk_groth16_setup_sizes(const zk_r1cs_view *r1cs, const zk_ptau_view *ptau, z
  * range-checked as by zk_r1cs_create. */
 int zk_groth16_setup(const zk_r1cs_view *r1cs, const zk_ptau_view *ptau, int32_t device, zk_setup_out *out);
 
+/* ---- Powers of Tau: prepare phase 2 (the Lagrange sections 12 to 15 of a .ptau) ---------- */
+/* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
+ * counterpart is snarkjs `powersoftau prepare phase2 pot.ptau pot_prepared.ptau`.
+ * An operator per group: out = the 2^log_n affine points (1 / n) sum_k w^(-jk) P_k, j < n = 2^log_n, the inverse DFT over
+ * group elements of the first n inputs in natural order (w: the n-th root of unity of zk_fr_ntt); inputs at index >=
+ * n_points count as infinity.  Points in the .zkey / .ptau encoding (affine Montgomery, all-zero = infinity), log_n <= 28.
+ * With P_k = [tau^k] G this is out_j = [L_j^(n)(tau)] G, one level of a Lagrange section.  Every input is checked against
+ * the curve equation (the twist's in G2; coordinates below q): a point that is not on the curve is an error that names
+ * its index.  Membership of the G2 subgroup is NOT checked (`powersoftau verify` does that).  device -1: the current one. */
+int zk_g1_lagrange(uint8_t *out, const uint8_t *points, uint64_t n_points, uint32_t log_n, int32_t device);
+int zk_g2_lagrange(uint8_t *out, const uint8_t *points, uint64_t n_points, uint32_t log_n, int32_t device);
+/* The whole file.  zk_ptau_powers_view: the .ptau's power and its sections 2 (tauG1, 2^(power+1) - 1 points), 3 (tauG2),
+ * 4 (alphaTauG1), 5 (betaTauG1) (2^power points each) as pointers and byte sizes into the mapped file. */
+typedef struct zk_ptau_powers_view {
+    uint32_t power;
+    const void *tau_g1, *tau_g2, *alpha_tau_g1, *beta_tau_g1;               /* sections 2, 3, 4, 5 */
+    uint64_t tau_g1_bytes, tau_g2_bytes, alpha_tau_g1_bytes, beta_tau_g1_bytes;
+} zk_ptau_powers_view;
+/* Byte sizes of sections 12 to 15 (levels 0 .. power + 1 of tauG1: (2^(power+2) - 1) x 64; levels 0 .. power of the
+ * others) and the HBM the computation holds at its peak (sections are done one after another: the largest one's). */
+typedef struct zk_ptau_lagrange_sizes {
+    uint64_t lagrange_g1_bytes, lagrange_g2_bytes, lagrange_alpha_g1_bytes, lagrange_beta_g1_bytes;
+    uint64_t device_bytes;
+} zk_ptau_lagrange_sizes;
+typedef struct zk_ptau_lagrange_out {
+    uint8_t *lagrange_g1, *lagrange_g2, *lagrange_alpha_g1, *lagrange_beta_g1;   /* sections 12, 13, 14, 15 */
+} zk_ptau_lagrange_out;
+/* Checks the view without touching a device: a power outside 1 .. 27 (level power + 1 needs a 2^(power+1)-th root of
+ * unity and Fr has roots up to 2^28), a missing section, "ptau section N is short: ... bytes, power P needs ...". */
+int zk_ptau_prepare_sizes(const zk_ptau_powers_view *ptau, zk_ptau_lagrange_sizes *sizes);
+/* Fills the four caller buffers (they may be a mapping of the output file; a section is written in two pieces, its top
+ * level and the levels below it, as each is finished).  Free HBM is checked before anything is allocated: too little
+ * is an error naming the bytes needed and free.  A point off the curve is an error naming its section and index. */
+int zk_ptau_prepare(const zk_ptau_powers_view *ptau, int32_t device, zk_ptau_lagrange_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@
 #include "../../include/zkhip.h"
 #include "../csrc/common.hpp"
 #include "../csrc/field64.hpp"
+#include "outfile.hpp"
 #include "zkfile.hpp"
 
 namespace {
@@ -40,35 +41,6 @@ void generators(uint8_t g1[64], uint8_t g2[128]) {
     fq_mont(g2 + 64, 0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
     fq_mont(g2 + 96, 0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
 }
-
-// a file written under a temporary name, renamed by commit(), removed otherwise
-struct OutFile {
-    std::string path, tmp;
-    std::ofstream f;
-    bool done = false;
-    explicit OutFile(const std::string &p) : path(p), tmp(p + ".partial") {
-        f.open(tmp, std::ios::binary | std::ios::trunc);
-        if (!f) throw std::runtime_error("cannot write " + path);
-    }
-    void write(const void *p, uint64_t n) { f.write(static_cast<const char *>(p), (std::streamsize)n); }
-    void u32(uint32_t v) { write(&v, 4); }
-    void section(uint32_t id, uint64_t size) {
-        u32(id);
-        write(&size, 8);
-    }
-    void commit() {
-        f.close();
-        if (!f) throw std::runtime_error("cannot write " + path);
-        if (rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("cannot write " + path);
-        done = true;
-    }
-    ~OutFile() {
-        if (!done) {
-            f.close();
-            remove(tmp.c_str());
-        }
-    }
-};
 
 std::string g1_json(const uint8_t *p) {
     return "[\"" + zk::HostTail::fq_mont_to_dec(p) + "\", \"" + zk::HostTail::fq_mont_to_dec(p + 32) + "\", \"1\"]";

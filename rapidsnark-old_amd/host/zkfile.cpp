@@ -265,6 +265,11 @@ std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f) {
             h->lagrangeBytes[i] = f->getSectionSize(12 + i);
             h->lagrange[i] = h->lagrangeBytes[i] ? f->getSectionData(12 + i) : nullptr;
         }
+    for (int i = 0; i < 4; i++)
+        if (f->hasSection(2 + i)) {
+            h->powersBytes[i] = f->getSectionSize(2 + i);
+            h->powers[i] = f->getSectionData(2 + i);
+        }
     return h;
 }
 

@@ -117,7 +117,8 @@ namespace PtauUtils {
 // A Powers of Tau file (snarkjs .ptau, magic "ptau", version 1): section 1 (n8, q, power, ceremonyPower), the points
 // alpha1 = alphaTauG1[0] (section 4), beta1 = betaTauG1[0] (section 5), beta2 (section 6), and the extents of the
 // Lagrange-basis sections 12 to 15 (`powersoftau prepare phase2`; NULL / 0 when the file is not prepared), left in the
-// mapping: only the levels a setup needs are ever read.  Refuses other fields / curves, and alpha1 / beta1 / beta2 that
+// mapping: only the levels a setup needs are ever read; and the extents of the powers themselves, sections 2 to 5, what
+// `ptauprepare` reads.  Refuses other fields / curves, and alpha1 / beta1 / beta2 that
 // are not points of BN254's G1 / G2 curve (checked here, on the host).
 class Header {
 public:
@@ -127,6 +128,8 @@ public:
     const void *alpha1 = nullptr, *beta1 = nullptr, *beta2 = nullptr;
     const void *lagrange[4] = {nullptr, nullptr, nullptr, nullptr};      // sections 12, 13, 14, 15
     uint64_t lagrangeBytes[4] = {0, 0, 0, 0};
+    const void *powers[4] = {nullptr, nullptr, nullptr, nullptr};        // sections 2, 3, 4, 5 (NULL: the file has none)
+    uint64_t powersBytes[4] = {0, 0, 0, 0};
 };
 std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f);
 

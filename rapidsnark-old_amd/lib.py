@@ -73,6 +73,20 @@ class zk_setup_sizes(C.Structure):
     _fields_ = [("nVars", C.c_uint32), ("nPublic", C.c_uint32), ("domainSize", C.c_uint32), ("log_domain", C.c_uint32), ("nCoefs", C.c_uint64)]
 
 
+class zk_ptau_powers_view(C.Structure):
+    _fields_ = [("power", C.c_uint32), ("tau_g1", C.c_void_p), ("tau_g2", C.c_void_p), ("alpha_tau_g1", C.c_void_p), ("beta_tau_g1", C.c_void_p),
+                ("tau_g1_bytes", C.c_uint64), ("tau_g2_bytes", C.c_uint64), ("alpha_tau_g1_bytes", C.c_uint64), ("beta_tau_g1_bytes", C.c_uint64)]
+
+
+class zk_ptau_lagrange_sizes(C.Structure):
+    _fields_ = [("lagrange_g1_bytes", C.c_uint64), ("lagrange_g2_bytes", C.c_uint64), ("lagrange_alpha_g1_bytes", C.c_uint64),
+                ("lagrange_beta_g1_bytes", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class zk_ptau_lagrange_out(C.Structure):
+    _fields_ = [("lagrange_g1", C.c_void_p), ("lagrange_g2", C.c_void_p), ("lagrange_alpha_g1", C.c_void_p), ("lagrange_beta_g1", C.c_void_p)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -111,7 +125,8 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_multi_prover_create", "zk_multi_prover_destroy", "zk_multi_prove", "zk_multi_prove_submit", "zk_multi_prove_collect",
            "zk_multi_prover_info", "zk_shard_info", "zk_shard_set_exchange", "zk_shard_begin", "zk_shard_step",
            "zk_r1cs_create", "zk_r1cs_destroy", "zk_r1cs_check", "zk_r1cs_check_dev", "zk_r1cs_match_zkey",
-           "zk_groth16_setup_sizes", "zk_groth16_setup"]
+           "zk_groth16_setup_sizes", "zk_groth16_setup",
+           "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare"]
 
 
 def load_library():
@@ -196,6 +211,11 @@ def load_library():
     if hasattr(lib, "zk_groth16_setup"):
         lib.zk_groth16_setup_sizes.argtypes = [C.POINTER(zk_r1cs_view), C.POINTER(zk_ptau_view), C.POINTER(zk_setup_sizes)]
         lib.zk_groth16_setup.argtypes = [C.POINTER(zk_r1cs_view), C.POINTER(zk_ptau_view), C.c_int32, C.POINTER(zk_setup_out)]
+    if hasattr(lib, "zk_ptau_prepare"):
+        lib.zk_g1_lagrange.argtypes = [u8p, u8p, C.c_uint64, C.c_uint32, C.c_int32]
+        lib.zk_g2_lagrange.argtypes = [u8p, u8p, C.c_uint64, C.c_uint32, C.c_int32]
+        lib.zk_ptau_prepare_sizes.argtypes = [C.POINTER(zk_ptau_powers_view), C.POINTER(zk_ptau_lagrange_sizes)]
+        lib.zk_ptau_prepare.argtypes = [C.POINTER(zk_ptau_powers_view), C.c_int32, C.POINTER(zk_ptau_lagrange_out)]
     _LIB = lib
     return lib
 
@@ -356,6 +376,29 @@ def fixed_base_g2(base, scalars):
     b = _buf(base).copy()
     check(load_library().zk_fixed_base_g2(_ptr(out), _ptr(b), _ptr(sc), n))
     return out
+
+
+def _lagrange(name, nb, points, log_n, device):
+    pts = _buf(points)
+    if pts.size % nb:
+        raise ValueError("points: a multiple of %d bytes expected" % nb)
+    out = np.zeros(nb << log_n, dtype=np.uint8)
+    fn = getattr(load_library(), name, None)
+    if fn is None:
+        raise ZkHipError("%s is not in this build of libzkhip.so" % name)
+    check(fn(_ptr(out), _ptr(pts) if pts.size else None, pts.size // nb, log_n, device))
+    return out
+
+
+def g1_lagrange(points, log_n, device=-1):
+    """The inverse DFT over G1 points (zk_g1_lagrange): the first 2^log_n of `points` (n x 64 B affine Montgomery; missing
+    ones count as infinity) -> numpy uint8 [2^log_n * 64], out_j = (1/n) sum_k w^(-jk) P_k.  With P_k = [tau^k]G this is
+    one level of a .ptau's Lagrange section.  Raises ZkHipError naming the index of a point that is not on the curve."""
+    return _lagrange("zk_g1_lagrange", 64, points, log_n, device)
+
+
+def g2_lagrange(points, log_n, device=-1):
+    return _lagrange("zk_g2_lagrange", 128, points, log_n, device)
 
 
 def g1_mul(p, k):

@@ -10,10 +10,14 @@ in G1 and 128 B in G2, all-zero = infinity.
                  being [L_j^(2^p)(tau)] (times alpha / beta in 14 / 15).  Section 12 runs to level power + 1 (built from the
                  2^(power+1) - 1 powers that exist: the missing top power counts as infinity), 13 to 15 to level power.
 
+prepare_phase2(src, dst) is `snarkjs powersoftau prepare phase2` on the GPU: sections 12 to 15 from sections 2 to 5, an
+inverse DFT over the points themselves (csrc/ptau_prepare.hip), for a ceremony's own output, whose tau nobody knows.
+
 groth16_setup(r1cs, ptau) makes the phase-2 starting key of snarkjs `groth16 setup` / `zkey new` from these sections on the
 GPU (gamma = delta = 1) as the key dict zkgen.write_zkey / zkgen.verification_key take."""
 import ctypes as C
 import mmap
+import os
 import struct
 
 import numpy as np
@@ -110,6 +114,18 @@ class PtauFile:
                 setattr(v, name + "_bytes", s.size)
         return v
 
+    def powers_view(self):
+        """-> zk_ptau_powers_view (sections 2 to 5 as pointers into this object's memory).  A missing section stays NULL:
+        the library names it."""
+        v = L.zk_ptau_powers_view()
+        v.power = self.power
+        for sid, name in zip((2, 3, 4, 5), ("tau_g1", "tau_g2", "alpha_tau_g1", "beta_tau_g1")):
+            if sid in self.sections:
+                s = self.section(sid)
+                setattr(v, name, s.ctypes.data if s.size else None)
+                setattr(v, name + "_bytes", s.size)
+        return v
+
     def close(self):
         self.raw = None
         if self._map is not None:
@@ -136,8 +152,9 @@ def _lagrange_level(powers, p, zero_top=False):
     return np.frombuffer(L.fr_ntt(x, inverse=True), dtype=np.uint8)
 
 
-def write_trapdoor_ptau(power, tau, alpha, beta, path):
-    """Write a prepared .ptau of `power` (sections 1 to 7 and 12 to 15) whose tau, alpha, beta are KNOWN.  NOT a
+def write_trapdoor_ptau(power, tau, alpha, beta, path, prepared=True):
+    """Write a prepared .ptau of `power` (sections 1 to 7 and 12 to 15; prepared=False: sections 1 to 7 only, as a
+    ceremony leaves the file, the input of prepare_phase2) whose tau, alpha, beta are KNOWN.  NOT a
     ceremony: anyone who has these numbers can forge proofs for every key made from the file.  It makes test and
     benchmark inputs only: keys whose trapdoor is known, so that proofs can be checked in Fr alone.  Needs a GPU: the
     Lagrange levels are inverse NTTs of the powers of tau (zk_fr_ntt), the points batch fixed-base multiplications
@@ -149,9 +166,6 @@ def write_trapdoor_ptau(power, tau, alpha, beta, path):
     n = 1 << power
     pw = zkgen._powers(tau, 2 * n)                                         # tau^0 .. tau^(2n - 1), standard
     a_k = lambda x, k: zkgen._scale(x, k, x.size // 32)
-    levels = [_lagrange_level(pw, p, zero_top=(p == power + 1)) for p in range(power + 2)]
-    lag = np.concatenate(levels)                                            # section 12's scalars
-    lag13 = lag[:((2 * n) - 1) * 32]                                        # levels 0 .. power
     sections = [
         (1, struct.pack("<I", 32) + int(Q_MOD).to_bytes(32, "little") + struct.pack("<II", power, power)),
         (2, L.fixed_base_g1(g1, pw[:(2 * n - 1) * 32])),
@@ -160,17 +174,91 @@ def write_trapdoor_ptau(power, tau, alpha, beta, path):
         (5, L.fixed_base_g1(g1, a_k(pw[:n * 32], beta))),
         (6, L.fixed_base_g2(g2, _fr_rows([beta]))),
         (7, struct.pack("<I", 0)),
-        (12, L.fixed_base_g1(g1, lag)),
-        (13, L.fixed_base_g2(g2, lag13)),
-        (14, L.fixed_base_g1(g1, a_k(lag13, alpha))),
-        (15, L.fixed_base_g1(g1, a_k(lag13, beta))),
     ]
+    if prepared:
+        levels = [_lagrange_level(pw, p, zero_top=(p == power + 1)) for p in range(power + 2)]
+        lag = np.concatenate(levels)                                        # section 12's scalars
+        lag13 = lag[:((2 * n) - 1) * 32]                                    # levels 0 .. power
+        sections += [
+            (12, L.fixed_base_g1(g1, lag)),
+            (13, L.fixed_base_g2(g2, lag13)),
+            (14, L.fixed_base_g1(g1, a_k(lag13, alpha))),
+            (15, L.fixed_base_g1(g1, a_k(lag13, beta))),
+        ]
     with open(path, "wb") as f:
         f.write(b"ptau" + struct.pack("<II", 1, len(sections)))
         for sid, payload in sections:
             payload = payload if isinstance(payload, bytes) else np.ascontiguousarray(payload).tobytes()
             f.write(struct.pack("<IQ", sid, len(payload)))
             f.write(payload)
+
+
+# ---------------------------------------------------------------- prepare phase 2
+def prepare_sizes(ptau):
+    """-> zk_ptau_prepare_sizes as a dict (the byte sizes of sections 12 to 15 and device_bytes); raises ZkHipError with the
+    library's message (unsupported power, missing or short section).  No device is touched."""
+    pf, own = _open_ptau(ptau)
+    try:
+        pv = pf.powers_view()
+        z = L.zk_ptau_lagrange_sizes()
+        L.check(L.load_library().zk_ptau_prepare_sizes(C.byref(pv), C.byref(z)))
+    finally:
+        if own:
+            pf.close()
+    return {name: int(getattr(z, name)) for name, _ in L.zk_ptau_lagrange_sizes._fields_}
+
+
+def prepare_phase2(src, dst, device=-1):
+    """`snarkjs powersoftau prepare phase2 src dst` on the GPU.  src: path, bytes or PtauFile; dst: path.  dst holds the
+    magic and version of src, its sections 1 to 7 byte for byte in src's order, then sections 12 to 15.  It is written as
+    dst + ".partial" through a mapping and renamed at the end: a failure (ZkHipError with the library's message,
+    ValueError for a file that is already prepared) leaves neither file."""
+    lib = L.load_library()
+    pf, own = _open_ptau(src)
+    tmp = dst + ".partial"
+    try:
+        if pf.prepared:
+            raise ValueError("the ptau file is already prepared for phase 2 (it has sections 12 to 15)")
+        pv = pf.powers_view()
+        z = L.zk_ptau_lagrange_sizes()
+        L.check(lib.zk_ptau_prepare_sizes(C.byref(pv), C.byref(z)))
+        keep = sorted((pos, size, sid) for sid, (pos, size) in pf.sections.items() if 1 <= sid <= 7)
+        new = [(sid, int(getattr(z, name + "_bytes"))) for sid, name in
+               zip(LAGRANGE, ("lagrange_g1", "lagrange_g2", "lagrange_alpha_g1", "lagrange_beta_g1"))]
+        total = 12 + sum(12 + size for _, size, _ in keep) + sum(12 + size for _, size in new)
+        try:
+            with open(tmp, "wb+") as f:
+                f.truncate(total)
+                m = mmap.mmap(f.fileno(), total)
+            try:
+                o = np.frombuffer(m, dtype=np.uint8)
+                o[:4] = pf.raw[:4]
+                o[4:8] = pf.raw[4:8]
+                o[8:12] = np.frombuffer(struct.pack("<I", len(keep) + len(new)), dtype=np.uint8)
+                at = 12
+                for pos, size, sid in keep:
+                    o[at:at + 12] = np.frombuffer(struct.pack("<IQ", sid, size), dtype=np.uint8)
+                    o[at + 12:at + 12 + size] = pf.raw[pos:pos + size]
+                    at += 12 + size
+                ptrs = []
+                for sid, size in new:
+                    o[at:at + 12] = np.frombuffer(struct.pack("<IQ", sid, size), dtype=np.uint8)
+                    ptrs.append(o[at + 12:at + 12 + size].ctypes.data)
+                    at += 12 + size
+                out = L.zk_ptau_lagrange_out(*ptrs)
+                L.check(lib.zk_ptau_prepare(C.byref(pv), device, C.byref(out)))
+                m.flush()
+            finally:
+                del o
+                m.close()
+            os.replace(tmp, dst)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            raise
+    finally:
+        if own:
+            pf.close()
 
 
 # ---------------------------------------------------------------- the setup

@@ -2,12 +2,12 @@
 """zkgen — write a trapdoor-VALID Groth16 key at a benchmark size (needs a GPU).
 
     python tools/zkgen.py <log2n> <outdir> [--npublic N] [--seed S] [--circuit-like | --semaphore-like] [--r1cs] [--prove]
-                          [--ptau POWER]
+                          [--ptau POWER [--unprepared]]
 
 Writes <outdir>/circuit.zkey, witness.wtns, verification_key.json, toxic.json (see
 rapidsnark-old_amd/zkgen.py); --r1cs also the circuit as circom's circuit.r1cs (for `wtnscheck` / ZKHIP_R1CS); --ptau POWER
 also a prepared Powers of Tau file pot.ptau of that power with the key's own tau, alpha, beta (ptau.write_trapdoor_ptau: a
-test input for `zkeynew`, NOT a ceremony).  --prove also runs the one-shot CLI `prover` on the written files with a
+test input for `zkeynew`, NOT a ceremony; --unprepared leaves its sections 12 to 15 out: an input for `ptauprepare`).  --prove also runs the one-shot CLI `prover` on the written files with a
 fixed (r, s), writes proof.json / public.json, and checks the proof against the discrete logs
 computed from the toxic waste (pairing-free trapdoor check).  Off-box:
     snarkjs groth16 verify verification_key.json public.json proof.json
@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--semaphore-like", action="store_true", help="the shape class of Semaphore / iden3 auth: chains of x^5 S-box rounds between Merkle-style muxes, "
                                                                   "nearly every signal full-size (zkgen.generate; use --npublic 4)")
     ap.add_argument("--ptau", type=int, metavar="POWER", help="also write pot.ptau of this power from the key's tau, alpha, beta (test input only)")
+    ap.add_argument("--unprepared", action="store_true", help="with --ptau: leave the Lagrange sections 12 to 15 out (an input for `ptauprepare`)")
     args = ap.parse_args()
     import rapidsnark_old_amd as zk
     from rapidsnark_old_amd import zkgen, synth
@@ -47,8 +48,8 @@ def main():
     print("generated 2^%d key in %.1f s (nVars %d, nCoefs %d), wrote files in %.1f s" % (args.log2n, t_gen, key["nVars"], key["nCoefs"], time.time() - t))
     if args.ptau is not None:
         t = time.time()
-        zk.write_trapdoor_ptau(args.ptau, *key["trap"]["toxic"][:3], os.path.join(args.outdir, "pot.ptau"))
-        print("wrote a trapdoor ptau of power %d in %.1f s" % (args.ptau, time.time() - t))
+        zk.write_trapdoor_ptau(args.ptau, *key["trap"]["toxic"][:3], os.path.join(args.outdir, "pot.ptau"), prepared=not args.unprepared)
+        print("wrote %s trapdoor ptau of power %d in %.1f s" % ("an unprepared" if args.unprepared else "a", args.ptau, time.time() - t))
     if args.prove:
         r, s = 0x0123456789ABCDEF, (1 << 200) + 12345
         le = lambda x: int(x).to_bytes(32, "little").hex()
