@@ -3,25 +3,9 @@
 #include "kernels.hpp"
 #include "hipcheck.hpp"
 #include "field29.hpp"
+#include "devmem.hpp"
 
 namespace zk {
-
-// 32-byte elements move as two 16-byte (dwordx4) accesses per lane: fully coalesced.
-template <class F>
-__device__ __forceinline__ F load_el(const F *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    uint4 lo = q[0], hi = q[1];
-    F r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void store_el(F *p, const F &r) {
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
 
 template <class F>
 __global__ __launch_bounds__(256) void k_mul_vec(F *out, const F *a, const F *b, uint64_t n) {

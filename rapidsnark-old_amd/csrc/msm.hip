@@ -24,6 +24,7 @@
 #include "common.hpp"
 #include "field29.hpp"
 #include "curve29.hpp"
+#include "devmem.hpp"
 #include <string.h>
 
 namespace zk {
@@ -90,15 +91,6 @@ MsmPlan make_msm_plan(uint64_t n, uint32_t window_bits, uint32_t precomp, uint32
     return p;
 }
 
-template <class F>
-__device__ __forceinline__ F load_el(const F *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    uint4 lo = q[0], hi = q[1];
-    F r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
 // a table row is read exactly once per MSM: ZK_L1_NT_GATHER (measurement builds) loads it with the non-temporal hint
 template <class F>
 __device__ __forceinline__ F load_row_el(const F *p) {
@@ -113,17 +105,6 @@ __device__ __forceinline__ F load_row_el(const F *p) {
 #else
     return load_el(p);
 #endif
-}
-template <class F>
-__device__ __forceinline__ void store_el(F *p, const F &r) {
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-__device__ __forceinline__ Fq2 load_el(const Fq2 *p) { return Fq2{load_el(&p->a), load_el(&p->b)}; }
-__device__ __forceinline__ void store_el(Fq2 *p, const Fq2 &r) {
-    store_el(&p->a, r.a);
-    store_el(&p->b, r.b);
 }
 
 // Register representation of the MSM kernels: 9x29-bit signed limbs (field29.hpp).  HBM keeps

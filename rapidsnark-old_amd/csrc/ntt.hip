@@ -12,6 +12,7 @@
 #include "hipcheck.hpp"
 #include "common.hpp"
 #include "field29.hpp"
+#include "devmem.hpp"
 
 namespace zk {
 
@@ -29,22 +30,6 @@ static uint32_t ntt_threads() {
 static uint32_t ntt_tile_log() {
     static const uint32_t v = [] { const char *e = probe_env("ZKHIP_NTT_TILE"); uint32_t t = e ? (uint32_t)atoi(e) : 10u; return t < 8u ? 8u : (t > 11u ? 11u : t); }();
     return v;
-}
-
-template <class F>
-__device__ __forceinline__ F load_el(const F *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    uint4 lo = q[0], hi = q[1];
-    F r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void store_el(F *p, const F &r) {
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
 }
 
 __device__ __forceinline__ Fr29 lds_get(const int32_t *lds, uint32_t N, uint32_t e) {

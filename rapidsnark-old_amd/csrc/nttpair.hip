@@ -30,24 +30,10 @@
 #include "hipcheck.hpp"
 #include "common.hpp"
 #include "field29.hpp"
+#include "devmem.hpp"
 
 namespace zk {
 
-template <class F>
-__device__ __forceinline__ F pload_el(const F *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    uint4 lo = q[0], hi = q[1];
-    F r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void pstore_el(F *p, const F &r) {
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
 __device__ __forceinline__ Fr29 pload_tw(const TwEntry *e) {
     const uint4 *q = reinterpret_cast<const uint4 *>(e);
     const uint4 a = q[0], b = q[1];
@@ -312,13 +298,13 @@ __global__ __launch_bounds__(256, 2) void k_ntt_mid(Fr *data, const Fr *src, uin
     for (int k = 0; k < 8; k++) {
         const uint32_t v = v_of(T, k, wfirst);
         const uint64_t pos = MODE == 2 ? natural(v) : wg_base + v;
-        x[k] = active ? F::load(pload_el(xs + pos)) : F::zero();
+        x[k] = active ? F::load(load_el(xs + pos)) : F::zero();
     }
     if (MODE != 2 && t.tinv) {
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
             const uint64_t p0 = wg_base + v_of(T, k, wtop), p1 = wg_base + v_of(T, k + 1, wtop);
-            const F a = F::load(pload_el(t.tinv + (active ? p0 : 0))), b = F::load(pload_el(t.tinv + (active ? p1 : 0)));
+            const F a = F::load(load_el(t.tinv + (active ? p0 : 0))), b = F::load(load_el(t.tinv + (active ? p1 : 0)));
             F::mul2(x[k], x[k], a, x[k + 1], x[k + 1], b);
         }
     }
@@ -329,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void k_ntt_mid(Fr *data, const Fr *src, uin
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
             const uint32_t q0 = v_of(T, k, wcur) & tmask, q1 = v_of(T, k + 1, wcur) & tmask;
-            const F a = F::load(pload_el(t.dtab + q0)), b = F::load(pload_el(t.dtab + q1));
+            const F a = F::load(load_el(t.dtab + q0)), b = F::load(load_el(t.dtab + q1));
             F::mul2(x[k], x[k], a, x[k + 1], x[k + 1], b);
         }
     }
@@ -338,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void k_ntt_mid(Fr *data, const Fr *src, uin
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
             const uint64_t p0 = wg_base + v_of(T, k, wcur), p1 = wg_base + v_of(T, k + 1, wcur);
-            const F a = F::load(pload_el(t.tfwd + (active ? p0 : 0))), b = F::load(pload_el(t.tfwd + (active ? p1 : 0)));
+            const F a = F::load(load_el(t.tfwd + (active ? p0 : 0))), b = F::load(load_el(t.tfwd + (active ? p1 : 0)));
             F::mul2(x[k], x[k], a, x[k + 1], x[k + 1], b);
         }
     }
@@ -346,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void k_ntt_mid(Fr *data, const Fr *src, uin
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const uint32_t v = v_of(T, k, wcur);
-            pstore_el(xg + (MODE == 1 ? natural(v) : wg_base + v), F::store(x[k]));
+            store_el(xg + (MODE == 1 ? natural(v) : wg_base + v), F::store(x[k]));
         }
     }
 }
@@ -374,12 +360,12 @@ __global__ __launch_bounds__(NT, 2) void k_ntt_outer(Fr *data, uint64_t stride_e
     const uint32_t wfirst = DIF ? o.plan.wlo[o.plan.nph - 1] : o.plan.wlo[0];
     F x[8];
 #pragma unroll
-    for (int k = 0; k < 8; k++) x[k] = F::load(pload_el(xg + pos_of(v_of(T, k, wfirst))));
+    for (int k = 0; k < 8; k++) x[k] = F::load(load_el(xg + pos_of(v_of(T, k, wfirst))));
     if (DIF && o.tab) {
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
-            const F a = F::load(pload_el(o.tab + ((pos_of(v_of(T, k, wfirst)) >> o.tab_shift) & o.tab_mask)));
-            const F b = F::load(pload_el(o.tab + ((pos_of(v_of(T, k + 1, wfirst)) >> o.tab_shift) & o.tab_mask)));
+            const F a = F::load(load_el(o.tab + ((pos_of(v_of(T, k, wfirst)) >> o.tab_shift) & o.tab_mask)));
+            const F b = F::load(load_el(o.tab + ((pos_of(v_of(T, k + 1, wfirst)) >> o.tab_shift) & o.tab_mask)));
             F::mul2(x[k], x[k], a, x[k + 1], x[k + 1], b);
         }
     }
@@ -388,13 +374,13 @@ __global__ __launch_bounds__(NT, 2) void k_ntt_outer(Fr *data, uint64_t stride_e
     if (!DIF && o.tab) {
 #pragma unroll
         for (int k = 0; k < 8; k += 2) {
-            const F a = F::load(pload_el(o.tab + ((pos_of(v_of(T, k, wcur)) >> o.tab_shift) & o.tab_mask)));
-            const F b = F::load(pload_el(o.tab + ((pos_of(v_of(T, k + 1, wcur)) >> o.tab_shift) & o.tab_mask)));
+            const F a = F::load(load_el(o.tab + ((pos_of(v_of(T, k, wcur)) >> o.tab_shift) & o.tab_mask)));
+            const F b = F::load(load_el(o.tab + ((pos_of(v_of(T, k + 1, wcur)) >> o.tab_shift) & o.tab_mask)));
             F::mul2(x[k], x[k], a, x[k + 1], x[k + 1], b);
         }
     }
 #pragma unroll
-    for (int k = 0; k < 8; k++) pstore_el(xg + pos_of(v_of(T, k, wcur)), F::store(x[k]));
+    for (int k = 0; k < 8; k++) store_el(xg + pos_of(v_of(T, k, wcur)), F::store(x[k]));
 }
 
 // ---------------------------------------------------------------- tables
@@ -458,20 +444,20 @@ __global__ __launch_bounds__(256) void k_pair_tables(TwEntry *rfwd, TwEntry *rin
         if (i < N1) {
             Fr d = plain ? Fr::one() : pfr_pow(s_w2m, pbrev((uint32_t)i, m));
             if (t == 0) d = Fr::mul(d, s_kappa);
-            pstore_el(dtab + i, Fr29::store(Fr29::from_mont256(d)));
+            store_el(dtab + i, Fr29::store(Fr29::from_mont256(d)));
         }
         if (t && i < n) {
             const uint64_t i0 = i & (N1 - 1), k1 = pbrev((uint32_t)(i >> m), t);
             const uint64_t e = (i0 * k1) & (n - 1);
-            pstore_el(tfwd + i, Fr29::store(Fr29::from_mont256(pfr_pow(s_wn, e))));
-            pstore_el(tinv + i, Fr29::store(Fr29::from_mont256(Fr::mul(plain ? pfr_pow(s_wni, e) : Fr::mul(pfr_pow(s_wni, e), pfr_pow(s_w2n, k1)), s_kappa))));
+            store_el(tfwd + i, Fr29::store(Fr29::from_mont256(pfr_pow(s_wn, e))));
+            store_el(tinv + i, Fr29::store(Fr29::from_mont256(Fr::mul(plain ? pfr_pow(s_wni, e) : Fr::mul(pfr_pow(s_wni, e), pfr_pow(s_w2n, k1)), s_kappa))));
         }
         if (t2fwd && i < (1ull << t)) {
             const uint32_t tb = t - ta;
             const uint64_t ja = i & ((1ull << ta) - 1), kb = pbrev((uint32_t)(i >> ta), tb);
             const uint64_t e = (ja * kb) & ((1ull << t) - 1);
-            pstore_el(t2fwd + i, Fr29::store(Fr29::from_mont256(pfr_pow(s_wt, e))));
-            pstore_el(t2inv + i, Fr29::store(Fr29::from_mont256(pfr_pow(s_wti, e))));
+            store_el(t2fwd + i, Fr29::store(Fr29::from_mont256(pfr_pow(s_wt, e))));
+            store_el(t2inv + i, Fr29::store(Fr29::from_mont256(pfr_pow(s_wti, e))));
         }
     }
 }

@@ -1,7 +1,10 @@
 // Operator-level entry points of the C-ABI (host pointers, staged through the device): the counterparts of the reference's
 // E.fr.mul / FFT::fft / Curve::multiMulByScalar call sites (src/groth16.cpp:91-95, 102-152, 171-204) as stand-alone
 // operators — what the KATs, zkgen and the parity tests call — and the synthetic-table helpers of the benchmark.
-#include "prover_internal.hpp"
+#include <map>
+#include <memory>
+#include <mutex>
+#include "hiputil.hpp"
 
 static void need_device() { need_device_count(); }
 

@@ -86,10 +86,8 @@ struct PhaseClock {
 void prover_create(zk_prover **out, const zk_zkey_view *z, const zk_opts *o) {
     if (!out || !z) throw std::invalid_argument("null argument");
     PhaseClock clk;
-    need_device_count();
+    const int dev = resolve_device(o ? o->device : -1);
     std::unique_ptr<zk_prover> p(new zk_prover());
-    int dev = (o && o->device >= 0) ? o->device : -1;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
     p->device = dev;
     DeviceGuard g(dev);
     p->flags = o ? o->flags : 0;
@@ -452,14 +450,7 @@ int zk_prover_reserve(zk_prover *p, uint32_t in_flight, uint32_t host_witnesses)
             }
             for (int lane = 1; lane < p->lanes && lane < nslots; lane++)
                 if (!p->extra[lane - 1]->ready) need += lane_b;
-            if (need) {
-                size_t fr = 0, tot = 0;
-                HIP_TRY(hipMemGetInfo(&fr, &tot));
-                const size_t margin = need / 32 + ((size_t)256 << 20);
-                if (fr < need + margin)
-                    throw HipError("zk_prover_reserve: out of memory (" + std::to_string(in_flight) + " in flight need " +
-                                   std::to_string((need + margin) >> 20) + " MiB of HBM, " + std::to_string(fr >> 20) + " MiB free)");
-            }
+            if (need) need_hbm("zk_prover_reserve", need);
         }
         // Every slot of the ring is allocated NOW (device workspace, and for host witnesses the HBM witness buffer and its
         // pinned staging copy), so that out-of-memory is a start-up error and the first `depth` proofs do not pay for it.

@@ -1,9 +1,14 @@
-// Internal header of libzkhip's host side (not part of the C-ABI: include/zkhip.h is).  The prover object, the small
-// RAII helpers around HIP memory and the functions the four translation units call in each other:
+// Internal header of libzkhip's prover (not part of the C-ABI: include/zkhip.h is).  The prover object and the functions
+// its translation units call in each other:
 //   prover_create.hip    zk_prover_create / destroy / reserve / info: one-off work of Groth16::makeProver (src/groth16.cpp:9-46)
 //   prover_pipeline.hip  one proof as enqueued phases, submit / collect, the synchronous entry points (src/groth16.cpp:48-254)
 //   prover_multi.hip     one proof on several GPUs: zk_multi_prover (one process) and zk_shard_* (one process per GPU)
-//   operators.hip        operator-level entry points (zk_fr_ntt, zk_msm_g1, ...) and the synthetic-table helpers
+// What does not know the prover lives in headers of its own, which the other translation units include directly:
+//   hiputil.hpp          host side: DevBuf, StreamUploader, Stream, SortBufs, DeviceGuard, resolve_device, need_hbm, guarded
+//                        (this header includes it); operators.hip (zk_fr_ntt, zk_msm_g1, ... and the synthetic-table
+//                        helpers), r1cs.hip, setup.hip and ptau_prepare.hip need nothing more of the host side
+//   r1cs_section.hpp     a .r1cs constraints section on the device and the segment plan: r1cs.hip and setup.hip
+//   devmem.hpp           device side: element / point loads and stores and the per-lane double-and-add, every kernel file
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -28,91 +33,10 @@
 #include "common.hpp"
 #include "hipcheck.hpp"
 #include "kernels.hpp"
+#include "hiputil.hpp"
 #include "tail_pool.hpp"
 
-using namespace zk;
-
 namespace zkp {
-
-#define HIP_TRY(expr) ZK_HIP(expr)
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    DevBuf() {}
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    void alloc(size_t count) {
-        release();
-        n = count;
-        if (count) HIP_TRY(hipMalloc((void **)&p, count * sizeof(T)));
-    }
-    void upload(const void *src, size_t count, hipStream_t s) {
-        if (count) HIP_TRY(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s));
-    }
-    size_t bytes() const { return n * sizeof(T); }      // what alloc(n) asked for
-};
-
-// Host image -> HBM for the big zkey sections (src/binfile_utils.cpp:28-33 copies the whole file into a
-// malloc'ed image first; here the image is the caller's, normally a read-only mmap of the .zkey: pageable
-// and possibly not yet in the page cache).  Two pinned staging chunks: while chunk k's DMA runs, four host
-// threads pull chunk k+1 out of the mapping (page faults / disk reads happen there, off the DMA's path).
-// A source that is already page-locked is copied from directly.
-struct StreamUploader {
-    static constexpr size_t CHUNK = (size_t)64 << 20;
-    uint8_t *pin[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
-    hipStream_t s;
-    int k = 0;
-    explicit StreamUploader(hipStream_t s_) : s(s_) {}
-    ~StreamUploader() {
-        for (int i = 0; i < 2; i++) {
-            if (done[i]) {
-                (void)hipEventSynchronize(done[i]);
-                (void)hipEventDestroy(done[i]);
-            }
-            if (pin[i]) (void)hipHostFree(pin[i]);
-        }
-    }
-    void copy(void *dst, const void *src, size_t bytes) {
-        if (!bytes) return;
-        hipPointerAttribute_t attr;
-        const bool pinned = hipPointerGetAttributes(&attr, src) == hipSuccess && attr.type == hipMemoryTypeHost;
-        (void)hipGetLastError();
-        if (pinned || bytes < ((size_t)4 << 20)) {
-            HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-            return;
-        }
-        for (size_t off = 0; off < bytes; off += CHUNK, k ^= 1) {
-            const size_t len = bytes - off < CHUNK ? bytes - off : CHUNK;
-            if (!pin[k]) {
-                HIP_TRY(hipHostMalloc((void **)&pin[k], CHUNK, hipHostMallocDefault));
-                HIP_TRY(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
-            } else {
-                HIP_TRY(hipEventSynchronize(done[k]));          // the DMA that last read this chunk
-            }
-            const uint8_t *from = (const uint8_t *)src + off;
-            uint8_t *to = pin[k];
-            const size_t nt = 4, per = (len / nt + 4095) & ~(size_t)4095;
-            std::vector<std::thread> th;
-            for (size_t t = 1; t < nt; t++) {
-                const size_t lo = t * per, hi = lo + per < len ? lo + per : len;
-                if (lo < hi) th.emplace_back([=] { memcpy(to + lo, from + lo, hi - lo); });
-            }
-            memcpy(to, from, per < len ? per : len);
-            for (auto &t : th) t.join();
-            HIP_TRY(hipMemcpyAsync((uint8_t *)dst + off, to, len, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipEventRecord(done[k], s));
-        }
-    }
-};
 
 struct Slice {
     uint64_t lo, hi;
@@ -125,56 +49,6 @@ inline Slice shard_slice(uint64_t n, uint32_t idx, uint32_t cnt) {
     if (hi > n) hi = n;
     return Slice{lo, hi};
 }
-
-// Scalar-vector sort workspace (one per scalar set: witness, h)
-struct SortBufs {
-    MsmPlan plan;
-    uint64_t n = 0;
-    DevBuf<uint16_t> lo;
-    DevBuf<uint32_t> counts, starts, offsets, entries, codes, val, bin_counts, bin_starts;
-    uint32_t total_buckets() const { return plan.sets * plan.nbuckets; }
-    uint64_t max_entries() const { return (n ? n : 1) * plan.W; }
-    // batch > 1: `batch` scalar vectors of n_ scalars each, sorted together into one bucket set per vector
-    // precomp: 0 = tables as in the zkey, 1 = a table row per window, 2 = a row per second window (MsmPlan::precomp)
-    void alloc(uint64_t n_, uint32_t window_bits, uint32_t precomp = 0, uint32_t batch = 1) {
-        plan = make_msm_plan(n_ ? n_ : 1, window_bits, precomp, batch);
-        n = n_ * (batch > 1 ? batch : 1);
-        // sort entries are 32-bit (bit 31 = digit sign): positions n*W and, with window-precomputed
-        // tables, table rows j*n + i must stay below 2^32 / 2^31
-        if ((n ? n : 1) * plan.W >= (1ull << 32)) throw std::invalid_argument("MSM too large: n * windows >= 2^32 sort entries");
-        if ((n ? n : 1) * msm_table_rows(plan) >= (1ull << 31)) throw std::invalid_argument("MSM too large: table rows >= 2^31");
-        MsmSortSizes z = msm_sort_sizes(n, plan);
-        lo.alloc(z.lo_u16);
-        counts.alloc(z.counts_u32);
-        starts.alloc(z.starts_u32);
-        offsets.alloc(z.offsets_u32);
-        entries.alloc(z.entries_u32);
-        codes.alloc(z.codes_u32);
-        val.alloc(z.val_u32);
-        bin_counts.alloc(z.bin_counts_u32);
-        bin_starts.alloc(z.bin_starts_u32);
-    }
-    void release() {
-        lo.release(); counts.release(); starts.release(); offsets.release(); entries.release();
-        codes.release(); val.release(); bin_counts.release(); bin_starts.release();
-        n = 0; ran = false;
-    }
-    size_t bytes() const {
-        return lo.bytes() + counts.bytes() + starts.bytes() + offsets.bytes() + entries.bytes() + codes.bytes() + val.bytes()
-             + bin_counts.bytes() + bin_starts.bytes();
-    }
-    bool ran = false;
-    void run(const Fr *scalars, hipStream_t s) {
-        // ZKHIP_PROBE_SKIP_SORT=1 (-DZK_PROBES builds only; wrong sums): the sort runs once per buffer set and its result is reused —
-        // what a proof costs if digits + counting sort were free (profiles/NEGATIVE_RESULTS.md item 22)
-        static const bool skip = probe_env("ZKHIP_PROBE_SKIP_SORT") != nullptr;
-        if (skip && ran) return;
-        ran = true;
-        MsmSortBufs b{offsets.p, entries.p, counts.p, starts.p, codes.p, val.p, bin_counts.p, bin_starts.p, lo.p};
-        launch_msm_sort(b, scalars, n, plan, s);
-    }
-};
-
 
 }   // namespace zkp
 using namespace zkp;
@@ -400,44 +274,6 @@ struct zk_prover {
 
 namespace zkp {
 
-inline void need_device_count() {
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) throw std::runtime_error("no HIP device available (libzkhip has no CPU fallback)");
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        HIP_TRY(hipSetDevice(dev));
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-template <class Fn>
-int guarded(Fn fn) {
-    try {
-        fn();
-        return 0;
-    } catch (const HipError &e) {
-        set_error(std::string("HIP failure: ") + e.what());
-        return 2;
-    } catch (const std::exception &e) {
-        set_error(e.what());
-        return 1;
-    }
-}
-
-inline uint32_t ilog2_exact(uint64_t n) {
-    uint32_t l = 0;
-    while ((1ull << l) < n) l++;
-    if ((1ull << l) != n) throw std::invalid_argument("domainSize is not a power of two");
-    return l;
-}
-
 // ---- prover_create.hip
 void prover_create(zk_prover **out, const zk_zkey_view *z, const zk_opts *o);
 void alloc_slot(zk_prover *p, int i);                                       // device + pinned workspace of one in-flight proof
@@ -475,18 +311,5 @@ struct DirectProof {
 };
 void collect_sums(zk_prover *p, zk_msm_sums *out, SubmittedRS *rs = nullptr, const DirectProof *direct = nullptr);
 void prove_finish(zk_prover *p, const zk_msm_sums *parts, uint32_t nparts, const uint8_t *r32, const uint8_t *s32, zk_proof *out);
-
-// ---- r1cs.hip, shared with setup.hip: the one host pass over a .r1cs constraints section and the segment plan of the
-// cut-into-segments sums (rows of any length -> segments of at most SEG_TERMS inputs, one lane each, pass after pass)
-constexpr uint32_t SEG_TERMS = 16;
-constexpr uint64_t SEG_FINAL = 1ull << 63;          // segment destination: a row value, not a partial of the next pass
-struct SegPass {
-    DevBuf<uint64_t> lo, dest;                      // nseg + 1 bounds into this pass's input, nseg destinations
-    uint64_t nseg = 0;
-};
-// word offset of every linear combination (3m: A rows, then B, then C) and the row offsets of their terms (3m + 1)
-void walk_constraints(const zk_r1cs_view *v, std::vector<uint64_t> &lc_off, std::vector<uint64_t> &rowptr);
-// the passes over rows with the given offsets; max_part: partials the even / odd passes write
-void plan_segments(const std::vector<uint64_t> &rowptr, std::vector<std::unique_ptr<SegPass>> &passes, uint64_t max_part[2]);
 
 }   // namespace zkp

@@ -12,7 +12,7 @@
 // lane to lane, so there is no table to precompute.  Each stage is four launches:
 //   k_ptau_bfly   a - b to a scratch row, then a + b in place                      (a general add per lane, twice)
 //   normalise     the row of differences to affine, synth.hip's batched inversion  (~15 field products per point)
-//   k_ptau_twmul  (a - b) w' by double-and-add with MIXED adds, as k_setup_term    (~3500 field products per point)
+//   k_ptau_twmul  (a - b) w' by devmem.hpp's double-and-add with MIXED adds        (~3500 field products per point)
 // so the loop pays 8M + 2S per set bit instead of the 12M + 2S of a general add.  The last pass multiplies every point
 // by 1/n (k_ptau_scale) and writes it to its bit-reversed place; one more normalisation gives the file's bytes.  The
 // last stage's twiddles are all 1, which the loop does in one step (it runs over the bit length of the scalar).
@@ -31,48 +31,14 @@
 // section is checked against the curve equation (the twist's for G2) and for coordinates below q before it is used; the
 // all-zero encoding is infinity and is legal.  Membership of the G2 SUBGROUP is not checked: that is `powersoftau
 // verify`'s job, and a point outside it still transforms linearly.
-#include "prover_internal.hpp"
+#include "hiputil.hpp"
+#include "devmem.hpp"
 
 namespace {
 
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t MAX_POWER = 27;                   // level power + 1 needs a 2^(power+1)-th root of unity; Fr has 2^28
 constexpr uint32_t MAX_LOG_N = 28;
-
-__device__ __forceinline__ uint4 ld4(const void *p) { return *reinterpret_cast<const uint4 *>(p); }
-__device__ __forceinline__ void st4(void *p, uint4 v) { *reinterpret_cast<uint4 *>(p) = v; }
-
-__device__ __forceinline__ void ld_f(Fq &r, const uint8_t *p) {
-    const uint4 lo = ld4(p), hi = ld4(p + 16);
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-}
-__device__ __forceinline__ void ld_f(Fq2 &r, const uint8_t *p) { ld_f(r.a, p); ld_f(r.b, p + 32); }
-__device__ __forceinline__ void st_f(uint8_t *p, const Fq &r) {
-    st4(p, make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]));
-    st4(p + 16, make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]));
-}
-__device__ __forceinline__ void st_f(uint8_t *p, const Fq2 &r) { st_f(p, r.a); st_f(p + 32, r.b); }
-
-template <class F>
-__device__ __forceinline__ Affine<F> ld_aff(const Affine<F> *q) {
-    const uint8_t *p = reinterpret_cast<const uint8_t *>(q);
-    Affine<F> r;
-    ld_f(r.x, p); ld_f(r.y, p + sizeof(F));
-    return r;
-}
-template <class F>
-__device__ __forceinline__ XYZZ<F> ld_xyzz(const XYZZ<F> *q) {
-    const uint8_t *p = reinterpret_cast<const uint8_t *>(q);
-    XYZZ<F> r;
-    ld_f(r.x, p); ld_f(r.y, p + sizeof(F)); ld_f(r.zz, p + 2 * sizeof(F)); ld_f(r.zzz, p + 3 * sizeof(F));
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void st_xyzz(XYZZ<F> *q, const XYZZ<F> &r) {
-    uint8_t *p = reinterpret_cast<uint8_t *>(q);
-    st_f(p, r.x); st_f(p + sizeof(F), r.y); st_f(p + 2 * sizeof(F), r.zz); st_f(p + 3 * sizeof(F), r.zzz);
-}
 
 // ---------------------------------------------------------------- load and check
 __device__ __forceinline__ bool below_q(const Fq &a) {
@@ -88,7 +54,7 @@ template <class F>
 __global__ __launch_bounds__(256) void k_ptau_check(uint32_t *err, const Affine<F> *src, uint64_t n, F b) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const Affine<F> p = ld_aff(src + i);
+    const Affine<F> p = load_pt(src + i);
     if (p.is_inf()) return;
     const bool ok = below_q(p.x) && below_q(p.y) && F::sqr(p.y) == F::add(F::mul(F::sqr(p.x), p.x), b);
     if (!ok) atomicMin(err, (uint32_t)i);
@@ -110,8 +76,8 @@ __global__ __launch_bounds__(256) void k_ptau_load(XYZZ<F> *x, const Affine<F> *
     uint64_t r;
     row_place(i, p_lo, p, r);
     XYZZ<F> v = XYZZ<F>::inf();
-    if (r < n_src) v = XYZZ<F>::from_affine(ld_aff(src + r));
-    st_xyzz(x + i, v);
+    if (r < n_src) v = XYZZ<F>::from_affine(load_pt(src + r));
+    store_pt(x + i, v);
 }
 
 // ---------------------------------------------------------------- twiddles
@@ -126,10 +92,7 @@ __global__ __launch_bounds__(256) void k_ptau_twiddles(Fr *tab, RootPowers pw, u
 #pragma unroll 1
     for (uint32_t i = 0; i < MAX_LOG_N; i++)
         if ((k >> i) & 1) acc = Fr::mul(acc, pw.w[i]);
-    acc = Fr::from_mont(acc);
-    uint8_t *o = reinterpret_cast<uint8_t *>(tab + k);
-    st4(o, make_uint4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]));
-    st4(o + 16, make_uint4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]));
+    store_el(tab + k, Fr::from_mont(acc));
 }
 
 // ---------------------------------------------------------------- the butterflies
@@ -143,46 +106,10 @@ __global__ __launch_bounds__(64) void k_ptau_bfly(XYZZ<F> *x, XYZZ<F> *diff, uin
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nb) return;
     const uint64_t j = i / groups, g = i - j * groups, lo = base + 2 * half * g + j;
-    XYZZ<F> b = ld_xyzz(x + lo + half);
+    XYZZ<F> b = load_pt(x + lo + half);
     if (DIFF) b.y = F::neg(b.y);
-    add(b, ld_xyzz(x + lo));
-    st_xyzz(DIFF ? diff + i : x + lo, b);
-}
-
-// k P by double-and-add over the bit length of k (standard form): the scalar is shifted so that its top bit is bit 255
-// and the loop reads bit 31 of the top word, as k_setup_term: no run-time indexed register array.
-template <class F>
-__device__ __forceinline__ XYZZ<F> scalar_mul_affine(const Affine<F> &P, const Fr *kp) {
-    uint32_t k[8];
-    const uint4 klo = ld4(kp), khi = ld4(reinterpret_cast<const uint8_t *>(kp) + 16);
-    k[0] = klo.x; k[1] = klo.y; k[2] = klo.z; k[3] = klo.w;
-    k[4] = khi.x; k[5] = khi.y; k[6] = khi.z; k[7] = khi.w;
-    int bl = 0;
-#pragma unroll
-    for (int i = 7; i >= 0; i--)
-        if (bl == 0 && k[i]) bl = 32 * i + 32 - __clz(k[i]);
-    int s = 256 - bl;
-    while (s >= 32) {
-#pragma unroll
-        for (int i = 7; i > 0; i--) k[i] = k[i - 1];
-        k[0] = 0;
-        s -= 32;
-    }
-    if (s) {
-#pragma unroll
-        for (int i = 7; i > 0; i--) k[i] = (k[i] << s) | (k[i - 1] >> (32 - s));
-        k[0] <<= s;
-    }
-    XYZZ<F> acc = XYZZ<F>::inf();
-    if (P.is_inf()) return acc;
-    for (int i = 0; i < bl; i++) {
-        acc = dbl(acc);
-        if (k[7] >> 31) madd(acc, P);
-#pragma unroll
-        for (int q = 7; q > 0; q--) k[q] = (k[q] << 1) | (k[q - 1] >> 31);
-        k[0] <<= 1;
-    }
-    return acc;
+    add(b, load_pt(x + lo));
+    store_pt(DIFF ? diff + i : x + lo, b);
 }
 
 // x[hi of lane i] = aff[i] * w_(2 half)^(-j); tab holds w_N^(-k), so the entry is j << tw_shift
@@ -192,7 +119,7 @@ __global__ __launch_bounds__(64) void k_ptau_twmul(XYZZ<F> *x, const Affine<F> *
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nb) return;
     const uint64_t j = i / groups, g = i - j * groups, hi = base + 2 * half * g + j + half;
-    st_xyzz(x + hi, scalar_mul_affine(ld_aff(aff + i), tab + (j << tw_shift)));
+    store_pt(x + hi, scalar_mul_affine(load_pt(aff + i), load_el(tab + (j << tw_shift))));
 }
 
 // y[bit-reversed place of i within its level] = aff[i] / 2^p; ninv[p] = 2^(-p), standard form
@@ -204,15 +131,10 @@ __global__ __launch_bounds__(64) void k_ptau_scale(XYZZ<F> *y, const Affine<F> *
     uint64_t r;
     row_place(i, p_lo, p, r);
     const uint64_t rb = p ? __brevll(r) >> (64 - p) : 0;
-    st_xyzz(y + (i - r + rb), scalar_mul_affine(ld_aff(aff + i), ninv + p));
+    store_pt(y + (i - r + rb), scalar_mul_affine(load_pt(aff + i), load_el(ninv + p)));
 }
 
 // ---------------------------------------------------------------- host
-inline uint32_t nblocks(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
-
-void normalize(G1Affine *out, const G1XYZZ *tmp, Fq *pref, uint64_t n, hipStream_t s) { launch_normalize_g1(out, tmp, pref, n, s); }
-void normalize(G2Affine *out, const G2XYZZ *tmp, Fq2 *pref, uint64_t n, hipStream_t s) { launch_normalize_g2(out, tmp, pref, n, s); }
-
 Fq fq_std(uint32_t lo) {                             // small constant -> Montgomery
     Fq x = Fq::zero();
     x.v[0] = lo;
@@ -235,15 +157,6 @@ Fq2 curve_b<Fq2>() {
     static const uint32_t b[8] = {0x85c315d2u, 0xe4a2bd06u, 0xe52d1852u, 0xa74fa084u, 0xeed8fdf4u, 0xcd2cafadu, 0x3af0fed4u, 0x009713b0u};
     return Fq2{fq_std(a), fq_std(b)};
 }
-
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() { HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-    ~Stream() {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
-    }
-};
 
 // w_(2^28), standard form (ntt.hip)
 const uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
@@ -334,15 +247,6 @@ uint32_t load_checked(DevBuf<Affine<F>> &d_src, const void *points, uint64_t n_s
     return bad;
 }
 
-void need_hbm(const char *who, uint64_t need) {
-    size_t fr = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fr, &tot));
-    const uint64_t margin = need / 32 + ((uint64_t)256 << 20);
-    if (fr < need + margin)
-        throw HipError(std::string(who) + ": out of memory (needs " + std::to_string(need + margin) + " bytes of HBM, " + std::to_string(fr) +
-                       " bytes free)");
-}
-
 // HBM of one section whose top level is `top`: the powers, the scratch of a row of 2^top points, the scalars
 template <class F>
 uint64_t section_bytes(uint64_t n_src, uint32_t top) {
@@ -354,10 +258,7 @@ void lagrange_op(uint8_t *out, const uint8_t *points, uint64_t n_points, uint32_
     if (log_n > MAX_LOG_N) throw std::invalid_argument(std::string(who) + ": log_n " + std::to_string(log_n) + " exceeds 28");
     if (!out || (n_points && !points)) throw std::invalid_argument("null argument");
     const uint64_t n = 1ull << log_n, n_src = n_points < n ? n_points : n;
-    need_device_count();
-    int dev = device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    DeviceGuard g(dev);
+    DeviceGuard g(resolve_device(device));
     need_hbm(who, section_bytes<F>(n_src, log_n));
     Stream st;
     DevBuf<Affine<F>> d_src;
@@ -420,10 +321,7 @@ void ptau_prepare(const zk_ptau_powers_view *v, int32_t device, zk_ptau_lagrange
     check_view(v, pl);                                // the file is checked before the device is touched
     if (!out || !out->lagrange_g1 || !out->lagrange_g2 || !out->lagrange_alpha_g1 || !out->lagrange_beta_g1)
         throw std::invalid_argument("null output buffer");
-    need_device_count();
-    int dev = device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    DeviceGuard g(dev);
+    DeviceGuard g(resolve_device(device));
     need_hbm("zk_ptau_prepare", pl.device_bytes);
     Stream st;
     Scalars sc;

@@ -21,8 +21,11 @@
 // products, which touches the bound; a row of r - 1 coefficients times r - 1 witness values is the extreme case, and
 // tests/test_gpu_r1cs.py runs it at every row length around the cut points.)  A witness value >= r is a 256-bit word
 // below 2^256 < 6r: still a valid operand, so the sums stay exact and such values are reported, not mis-summed.
-#include "prover_internal.hpp"
+#include <sys/random.h>
+#include <mutex>
+#include "r1cs_section.hpp"
 #include "field29.hpp"
+#include "devmem.hpp"
 
 namespace {
 
@@ -31,26 +34,6 @@ constexpr uint32_t LAZY = 7;                 // additions between two reductions
 constexpr uint64_t FINAL = SEG_FINAL;        // segment destination: a row value, not a partial of the next pass
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
-__device__ __forceinline__ Fr r_load(const Fr *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    uint4 lo = q[0], hi = q[1];
-    Fr r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-__device__ __forceinline__ void r_store(Fr *p, const Fr &r) {
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-// w >= r (BN254 scalar field), 256-bit words little-endian
-__device__ __forceinline__ bool ge_r(const uint32_t *w) {
-    constexpr uint32_t R[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
-    for (int i = 7; i >= 0; i--)
-        if (w[i] != R[i]) return w[i] > R[i];
-    return true;
-}
 // per-lane hit counts and lowest indices -> one pair of integer atomics per wave (the kernels below stride over their
 // rows with a bounded grid, so a check in which every constraint fails still issues only a few thousand atomics)
 __device__ __forceinline__ void wave_flush(uint32_t cnt, uint32_t low, unsigned long long *count, uint32_t *lowest) {
@@ -66,28 +49,22 @@ __device__ __forceinline__ void wave_flush(uint32_t cnt, uint32_t low, unsigned 
 }
 #define R1CS_FOR(i, n) for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += gridDim.x * blockDim.x)
 
-// term t -> (row, rank): rowptr is ascending with rowptr[0] = 0 and rowptr[rows] = nnz; the row of t is the LAST r with
-// rowptr[r] <= t (empty rows share their start with the next row and are skipped by that rule)
+// one lane per term of the section (term_at: r1cs_section.hpp) -> its wire id and its coefficient as value * 2^522
 __global__ __launch_bounds__(256) void k_r1cs_decode(uint32_t *col, Fr *val, uint32_t *err, const uint32_t *sec, const uint64_t *lc_off,
                                                      const uint64_t *rowptr, uint32_t rows, uint32_t m, uint32_t nWires, uint64_t nnz, Fr k783) {
     const uint64_t st = (uint64_t)gridDim.x * blockDim.x;
     const Fr29 k = Fr29::load(k783);
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nnz; t += st) {
-        uint32_t lo = 0, hi = rows;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (rowptr[mid] <= t) lo = mid;
-            else hi = mid;
-        }
-        const uint32_t *p = sec + lc_off[lo] + 1 + 9 * (t - rowptr[lo]);
-        const uint32_t wire = p[0], cons = lo % m;
+        uint32_t row;
+        const uint32_t *p = term_at(t, sec, lc_off, rowptr, rows, row);
+        const uint32_t wire = p[0], cons = row % m;
         Fr c;
 #pragma unroll
         for (int j = 0; j < 8; j++) c.v[j] = p[1 + j];
         if (wire >= nWires) atomicMin(&err[0], cons);
         if (ge_r(c.v)) atomicMin(&err[1], cons);
         col[t] = wire < nWires ? wire : 0;
-        r_store(val + t, Fr29::store(Fr29::mul(Fr29::load(c), k)));      // value * 2^522
+        store_el(val + t, Fr29::store(Fr29::mul(Fr29::load(c), k)));      // value * 2^522
     }
 }
 
@@ -102,7 +79,7 @@ __global__ __launch_bounds__(256) void k_r1cs_pass(Fr *rows, Fr *next, const uin
     Fr29 sum = Fr29::zero();
     uint32_t pending = 0;
     for (uint64_t t = a; t < b; t++) {
-        const Fr29 x = TERMS ? Fr29::mul(Fr29::load(r_load(w + col[t])), Fr29::load(r_load(val + t))) : Fr29::load(r_load(in + t));
+        const Fr29 x = TERMS ? Fr29::mul(Fr29::load(load_el(w + col[t])), Fr29::load(load_el(val + t))) : Fr29::load(load_el(in + t));
         sum = Fr29::add(sum, x);
         if (++pending == LAZY) {
             sum = Fr29::reduce_near_zero(sum);
@@ -110,7 +87,7 @@ __global__ __launch_bounds__(256) void k_r1cs_pass(Fr *rows, Fr *next, const uin
         }
     }
     const uint64_t d = dest[j];
-    r_store((d & FINAL) ? rows + (d & ~FINAL) : next + d, Fr29::store(sum));
+    store_el((d & FINAL) ? rows + (d & ~FINAL) : next + d, Fr29::store(sum));
 }
 
 struct DevReport {                            // zk_r1cs_report's device half
@@ -130,7 +107,7 @@ __global__ void k_r1cs_report_init(DevReport *rep) {
 __global__ __launch_bounds__(256) void k_r1cs_check(DevReport *rep, const Fr *rows, uint32_t m) {
     uint32_t cnt = 0, low = NONE;
     R1CS_FOR(i, m) {
-        const Fr29 a = Fr29::load(r_load(rows + i)), b = Fr29::load(r_load(rows + (uint64_t)m + i)), c = Fr29::load(r_load(rows + 2ull * m + i));
+        const Fr29 a = Fr29::load(load_el(rows + i)), b = Fr29::load(load_el(rows + (uint64_t)m + i)), c = Fr29::load(load_el(rows + 2ull * m + i));
         if (!Fr29::sub(Fr29::mul(a, b), c).is_zero()) {
             cnt++;
             low = low < i ? low : i;
@@ -143,7 +120,7 @@ __global__ __launch_bounds__(256) void k_r1cs_check(DevReport *rep, const Fr *ro
 __global__ __launch_bounds__(256) void k_r1cs_witness(DevReport *rep, const Fr *w, uint32_t n) {
     uint32_t cnt = 0, low = NONE;
     R1CS_FOR(i, n) {
-        const Fr x = r_load(w + i);
+        const Fr x = load_el(w + i);
         if (ge_r(x.v)) {
             cnt++;
             low = low < i ? low : i;
@@ -163,8 +140,8 @@ __global__ void k_r1cs_report_rows(DevReport *rep, const Fr *rows, uint32_t m) {
     const uint32_t f = rep->first_failed, k = threadIdx.x;
     Fr v;
     for (int j = 0; j < 8; j++) v.v[j] = 0;
-    if (f != NONE && k < 3) v = Fr29::store(Fr29::from_mont(Fr29::load(r_load(rows + (uint64_t)k * m + f))));
-    if (k < 3) r_store(rep->abc + k, v);
+    if (f != NONE && k < 3) v = Fr29::store(Fr29::from_mont(Fr29::load(load_el(rows + (uint64_t)k * m + f))));
+    if (k < 3) store_el(rep->abc + k, v);
 }
 
 // zkey rows against the r1cs: row i < m: A.x and B.x equal; m <= i <= m + nPublic: A = x[i - m] (snarkjs's public-input
@@ -176,12 +153,12 @@ __global__ __launch_bounds__(256) void k_r1cs_match(unsigned long long *differ, 
         Fr wa, wb;
         for (int j = 0; j < 8; j++) wa.v[j] = wb.v[j] = 0;
         if (i < m) {
-            wa = r_load(rows + i);
-            wb = r_load(rows + (uint64_t)m + i);
+            wa = load_el(rows + i);
+            wb = load_el(rows + (uint64_t)m + i);
         } else if (i - m <= nPublic) {
-            wa = Fr29::store(Fr29::mul(Fr29::load(r_load(x + (i - m))), Fr29::load(k522)));      // x * 2^261
+            wa = Fr29::store(Fr29::mul(Fr29::load(load_el(x + (i - m))), Fr29::load(k522)));      // x * 2^261
         }
-        const Fr za = r_load(zab + i), zb = r_load(zab + (uint64_t)n + i);
+        const Fr za = load_el(zab + i), zb = load_el(zab + (uint64_t)n + i);
         uint32_t o = 0;
 #pragma unroll
         for (int j = 0; j < 8; j++) o |= (za.v[j] ^ wa.v[j]) | (zb.v[j] ^ wb.v[j]);
@@ -345,9 +322,7 @@ void r1cs_create(zk_r1cs **out, const zk_r1cs_view *v, int32_t device) {
     if (v->nConstraints && !v->constraints) throw std::invalid_argument("null constraints section");
     std::vector<uint64_t> lc_off, rowptr;
     walk_constraints(v, lc_off, rowptr);                  // the file is checked before the device is touched
-    need_device_count();
-    int dev = device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+    const int dev = resolve_device(device);
     DeviceGuard g(dev);
     std::unique_ptr<zk_r1cs> r(new zk_r1cs());
     r->device = dev;
@@ -369,27 +344,13 @@ void r1cs_create(zk_r1cs **out, const zk_r1cs_view *v, int32_t device) {
     r->col.alloc(r->nnz ? r->nnz : 1);
     r->val.alloc(r->nnz ? r->nnz : 1);
     if (r->nnz) {
-        DevBuf<uint8_t> raw;
-        DevBuf<uint64_t> d_off, d_ptr;
-        DevBuf<uint32_t> err;
-        raw.alloc(v->constraints_bytes);
-        d_off.alloc(lc_off.size());
-        d_ptr.alloc(rowptr.size());
-        err.alloc(2);
-        StreamUploader up(r->stream);
-        up.copy(raw.p, v->constraints, v->constraints_bytes);
-        HIP_TRY(hipMemcpyAsync(d_off.p, lc_off.data(), lc_off.size() * 8, hipMemcpyHostToDevice, r->stream));
-        HIP_TRY(hipMemcpyAsync(d_ptr.p, rowptr.data(), rowptr.size() * 8, hipMemcpyHostToDevice, r->stream));
-        HIP_TRY(hipMemsetAsync(err.p, 0xFF, 8, r->stream));
+        SectionOnDevice sec;
+        sec.upload(v, lc_off, rowptr, r->stream);
         const uint64_t g = r->nnz < 256ull * 4096 ? (r->nnz + 255) / 256 : 4096;
-        ZK_LAUNCH(k_r1cs_decode, dim3((uint32_t)g), dim3(256), 0, r->stream, r->col.p, r->val.p, err.p, (const uint32_t *)raw.p, d_off.p, d_ptr.p,
-                  (uint32_t)(rowptr.size() - 1), r->m, r->nWires, r->nnz, r->k783);
+        ZK_LAUNCH(k_r1cs_decode, dim3((uint32_t)g), dim3(256), 0, r->stream, r->col.p, r->val.p, sec.err.p, sec.sec(), sec.d_off.p, sec.d_ptr.p, sec.rows(),
+                  r->m, r->nWires, r->nnz, r->k783);
         ZK_LAUNCH_OK("r1cs decode");
-        uint32_t bad[2];
-        HIP_TRY(hipMemcpyAsync(bad, err.p, 8, hipMemcpyDeviceToHost, r->stream));
-        HIP_TRY(hipStreamSynchronize(r->stream));
-        if (bad[0] != NONE) throw std::invalid_argument("r1cs constraint " + std::to_string(bad[0]) + ": wire id >= nWires");
-        if (bad[1] != NONE) throw std::invalid_argument("r1cs constraint " + std::to_string(bad[1]) + ": coefficient >= r");
+        sec.check(r->stream);
     }
     plan_passes(r.get(), rowptr);
     *out = r.release();

@@ -12,75 +12,33 @@
 //   K_s  = sum_A v T15[c] + sum_B v T14[c] + sum_C v T12[c]     IC = K_0 .. K_nPublic, C = the rest
 // and H_i = T12'[2i + 1] (level k + 1 of section 12), a strided gather.
 //
-// Layout.  The constraints section is uploaded as it is in the file and decoded on the device by the walk of r1cs.hip
-// (walk_constraints: one host pass over the term counts) into one term list: the A terms, then the nPublic + 1
-// public-input rows, then the B terms, then the C terms, each (wire, constraint, coefficient in standard form).  Every
+// Layout.  The constraints section is uploaded as it is in the file and decoded on the device through
+// r1cs_section.hpp (walk_constraints: one host pass over the term counts; term_at: a lane's term), as the witness check
+// of r1cs.hip does, into one term list: the A terms, then the nPublic + 1 public-input rows, then the B terms, then the C terms, each (wire, constraint, coefficient in standard form).  Every
 // output table is a contiguous range of that list; its base table is chosen per term by two split points.
 //
 // One table.  (1) k_setup_count: terms per wire and per signed bit length.  (2) The host turns the wire counts into row
 // offsets (one pass over the wires, as many as the key has points) and plans the segmented sum.  (3) k_setup_scatter:
 // a counting sort by bit length (the order the per-term lanes run in) that also hands every term its slot in the
-// wire-grouped order (a counting sort by wire).  (4) k_setup_term: one lane per term, v T[c] by double-and-add over
+// wire-grouped order (a counting sort by wire).  (4) k_setup_term: one lane per term, v T[c] by devmem.hpp's double-and-add over
 // the bit length of the SIGNED coefficient (v > (r-1)/2 is taken as -(r - v): circom writes -1 as r - 1), so a wave of
 // +-1 and +-2^i terms does one or a few steps and never waits for a 254-bit term.  (5) k_setup_pass: the
-// cut-into-segments sum of r1cs.hip over the wire groups (at most 16 inputs per lane, pass after pass, no atomics on
+// cut-into-segments sum (r1cs_section.hpp's plan_segments, as r1cs.hip) over the wire groups (at most 16 inputs per lane, pass after pass, no atomics on
 // points), so the constant wire's column of ~m terms is m / 16 lanes, then m / 256, ...  (6) The batched affine
 // normalisation of synth.hip.  Integer atomics place terms; point sums do not depend on the order they come in.
 //
 // Fields: curve.hpp's 8 x 32-bit Montgomery forms (R = 2^256), the .ptau's and the .zkey's own byte form, so points go
 // in and come out without a conversion and the result is the fixed-base kernels' (synth.hip) form bit for bit.
-#include "prover_internal.hpp"
+#include "r1cs_section.hpp"
+#include "devmem.hpp"
 
 namespace {
 
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t MAX_LOG_DOMAIN = 27;              // the prover's limit (prover_create.hip)
 constexpr uint32_t BL_BINS = 256;                    // signed bit lengths 0 .. 254
 
-__device__ __forceinline__ uint4 ld4(const void *p) { return *reinterpret_cast<const uint4 *>(p); }
-__device__ __forceinline__ void st4(void *p, uint4 v) { *reinterpret_cast<uint4 *>(p) = v; }
-
-__device__ __forceinline__ void ld_f(Fq &r, const uint8_t *p) {
-    const uint4 lo = ld4(p), hi = ld4(p + 16);
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-}
-__device__ __forceinline__ void ld_f(Fq2 &r, const uint8_t *p) { ld_f(r.a, p); ld_f(r.b, p + 32); }
-__device__ __forceinline__ void st_f(uint8_t *p, const Fq &r) {
-    st4(p, make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]));
-    st4(p + 16, make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]));
-}
-__device__ __forceinline__ void st_f(uint8_t *p, const Fq2 &r) { st_f(p, r.a); st_f(p + 32, r.b); }
-
-template <class F>
-__device__ __forceinline__ XYZZ<F> ld_xyzz(const XYZZ<F> *q) {
-    const uint8_t *p = reinterpret_cast<const uint8_t *>(q);
-    XYZZ<F> r;
-    ld_f(r.x, p); ld_f(r.y, p + sizeof(F)); ld_f(r.zz, p + 2 * sizeof(F)); ld_f(r.zzz, p + 3 * sizeof(F));
-    return r;
-}
-template <class F>
-__device__ __forceinline__ void st_xyzz(XYZZ<F> *q, const XYZZ<F> &r) {
-    uint8_t *p = reinterpret_cast<uint8_t *>(q);
-    st_f(p, r.x); st_f(p + sizeof(F), r.y); st_f(p + 2 * sizeof(F), r.zz); st_f(p + 3 * sizeof(F), r.zzz);
-}
-
-__device__ __forceinline__ void ld_words(uint32_t w[8], const Fr *p) {
-    const uint4 lo = ld4(p), hi = ld4(reinterpret_cast<const uint8_t *>(p) + 16);
-    w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w;
-    w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w;
-}
-
-// BN254 r and (r - 1) / 2, little-endian words
-__device__ constexpr uint32_t R_WORDS[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+// (r - 1) / 2 for BN254's r, little-endian words
 __device__ constexpr uint32_t HALF_R[8] = {0xf8000000u, 0xa1f0fac9u, 0x3cdcb848u, 0x9419f424u, 0x40c0ac2eu, 0xdc2822dbu, 0x7098d014u, 0x18322739u};
-
-__device__ __forceinline__ bool ge_r(const uint32_t *w) {
-#pragma unroll
-    for (int i = 7; i >= 0; i--)
-        if (w[i] != R_WORDS[i]) return w[i] > R_WORDS[i];
-    return true;
-}
 
 // v (standard form, < r) -> |v| in w as a signed residue (v > (r-1)/2: r - v, neg) and its bit length
 __device__ __forceinline__ int signed_mag(uint32_t w[8], bool &neg) {
@@ -96,7 +54,7 @@ __device__ __forceinline__ int signed_mag(uint32_t w[8], bool &neg) {
         uint32_t bw = 0;
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            const uint64_t d = (uint64_t)R_WORDS[i] - w[i] - bw;
+            const uint64_t d = (uint64_t)FrParams::P[i] - w[i] - bw;
             w[i] = (uint32_t)d;
             bw = (uint32_t)(d >> 63);
         }
@@ -109,45 +67,38 @@ __device__ __forceinline__ int signed_mag(uint32_t w[8], bool &neg) {
 }
 
 // The term list: A terms [0, nnzA), public-input rows [nnzA, nnzA + nP1), B terms, C terms.  rows = 3m rows of the
-// file (A, B, C), rowptr / lc_off as r1cs.hip's decode; a term's row is the LAST r with rowptr[r] <= t.
+// file (A, B, C); one lane per term of the section (term_at: r1cs_section.hpp) and per public-input row.
 __global__ __launch_bounds__(256) void k_setup_decode(uint32_t *wire, uint32_t *cons, Fr *coef, uint32_t *err, const uint32_t *sec,
                                                       const uint64_t *lc_off, const uint64_t *rowptr, uint32_t rows, uint32_t m, uint32_t nWires,
                                                       uint64_t nnz, uint64_t nnzA, uint32_t nP1) {
     const uint64_t st = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nnz + nP1; t += st) {
-        uint32_t w[8];
+        Fr w;
         uint64_t g;
         uint32_t wi, ci;
         if (t < nnz) {
-            uint32_t lo = 0, hi = rows;
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + (hi - lo) / 2;
-                if (rowptr[mid] <= t) lo = mid;
-                else hi = mid;
-            }
-            const uint32_t *p = sec + lc_off[lo] + 1 + 9 * (t - rowptr[lo]);
+            uint32_t row;
+            const uint32_t *p = term_at(t, sec, lc_off, rowptr, rows, row);
             wi = p[0];
-            ci = lo % m;
+            ci = row % m;
 #pragma unroll
-            for (int j = 0; j < 8; j++) w[j] = p[1 + j];
+            for (int j = 0; j < 8; j++) w.v[j] = p[1 + j];
             if (wi >= nWires) atomicMin(&err[0], ci);
-            if (ge_r(w)) atomicMin(&err[1], ci);
+            if (ge_r(w.v)) atomicMin(&err[1], ci);
             if (wi >= nWires) wi = 0;
             g = t < nnzA ? t : t + nP1;
         } else {                                    // public-input row i: A, constraint m + i, wire i, value 1
             const uint32_t i = (uint32_t)(t - nnz);
             wi = i;
             ci = m + i;
-            w[0] = 1;
+            w.v[0] = 1;
 #pragma unroll
-            for (int j = 1; j < 8; j++) w[j] = 0;
+            for (int j = 1; j < 8; j++) w.v[j] = 0;
             g = nnzA + i;
         }
         wire[g] = wi;
         cons[g] = ci;
-        uint8_t *c = reinterpret_cast<uint8_t *>(coef + g);
-        st4(c, make_uint4(w[0], w[1], w[2], w[3]));
-        st4(c + 16, make_uint4(w[4], w[5], w[6], w[7]));
+        store_el(coef + g, w);
     }
 }
 
@@ -157,9 +108,7 @@ __global__ __launch_bounds__(256) void k_setup_coefs(uint32_t *rec, const uint32
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g == 0) rec[0] = (uint32_t)nRec;
     if (g >= nRec) return;
-    Fr v;
-    ld_words(v.v, coef + g);
-    v = Fr::mul(v, r3);                             // v R^3 / R
+    const Fr v = Fr::mul(load_el(coef + g), r3);                             // v R^3 / R
     uint32_t *o = rec + 1 + 11 * g;
     o[0] = g < nA ? 0u : 1u;
     o[1] = cons[g];
@@ -175,10 +124,9 @@ __global__ __launch_bounds__(256) void k_setup_count(uint32_t *cntW, uint32_t *c
     __syncthreads();
     const uint64_t g = t0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < t1) {
-        uint32_t w[8];
+        Fr w = load_el(coef + g);
         bool neg;
-        ld_words(w, coef + g);
-        atomicAdd(&h[signed_mag(w, neg)], 1u);
+        atomicAdd(&h[signed_mag(w.v, neg)], 1u);
         atomicAdd(&cntW[wire[g]], 1u);
     }
     __syncthreads();
@@ -195,10 +143,9 @@ __global__ __launch_bounds__(256) void k_setup_scatter(uint32_t *order, uint64_t
     const uint64_t g = t0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t bl = 0, rank = 0;
     if (g < t1) {
-        uint32_t w[8];
+        Fr w = load_el(coef + g);
         bool neg;
-        ld_words(w, coef + g);
-        bl = (uint32_t)signed_mag(w, neg);
+        bl = (uint32_t)signed_mag(w.v, neg);
         rank = atomicAdd(&h[bl], 1u);
     }
     __syncthreads();
@@ -218,45 +165,21 @@ struct Bases {
     uint64_t split[2];
 };
 
-// One lane per term: v T[c] by double-and-add over the bit length of the signed coefficient.  The magnitude is shifted
-// so that its top bit is bit 255 and the loop reads bit 31 of the top word: no run-time indexed register array.
+// One lane per term: v T[c] by devmem.hpp's double-and-add over the bit length of the signed coefficient (-|v| P is
+// |v| (-P): the base's y is negated, so -1 costs what 1 costs).
 template <class F>
 __global__ __launch_bounds__(64) void k_setup_term(XYZZ<F> *tmp, const uint32_t *order, const uint64_t *slot, uint64_t cnt, const uint32_t *cons,
                                                    const Fr *coef, Bases<F> b) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= cnt) return;
     const uint32_t g = order[j];
-    uint32_t k[8];
+    Fr k = load_el(coef + g);
     bool neg;
-    ld_words(k, coef + g);
-    const int bl = signed_mag(k, neg);
-    int s = 256 - bl;
-    while (s >= 32) {
-#pragma unroll
-        for (int i = 7; i > 0; i--) k[i] = k[i - 1];
-        k[0] = 0;
-        s -= 32;
-    }
-    if (s) {
-#pragma unroll
-        for (int i = 7; i > 0; i--) k[i] = (k[i] << s) | (k[i - 1] >> (32 - s));
-        k[0] <<= s;
-    }
+    signed_mag(k.v, neg);
     const Affine<F> *tab = g < b.split[0] ? b.t[0] : (g < b.split[1] ? b.t[1] : b.t[2]);
-    const uint8_t *bp = reinterpret_cast<const uint8_t *>(tab + cons[g]);
-    Affine<F> P;
-    ld_f(P.x, bp);
-    ld_f(P.y, bp + sizeof(F));
+    Affine<F> P = load_pt(tab + cons[g]);
     if (neg) P.y = F::neg(P.y);
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (int i = 0; i < bl; i++) {
-        acc = dbl(acc);
-        if (k[7] >> 31) madd(acc, P);
-#pragma unroll
-        for (int q = 7; q > 0; q--) k[q] = (k[q] << 1) | (k[q - 1] >> 31);
-        k[0] <<= 1;
-    }
-    st_xyzz(tmp + slot[j], acc);
+    store_pt(tmp + slot[j], scalar_mul_affine(P, k));
 }
 
 // One lane per segment [lo[j], lo[j+1]) of this pass's input (pass 0: the terms grouped by wire; later passes: the
@@ -268,9 +191,9 @@ __global__ __launch_bounds__(64) void k_setup_pass(XYZZ<F> *sums, XYZZ<F> *next,
     if (j >= nseg) return;
     const uint64_t a = lo[j], e = lo[j + 1];
     XYZZ<F> acc = XYZZ<F>::inf();
-    for (uint64_t t = a; t < e; t++) add(acc, ld_xyzz(in + t));
+    for (uint64_t t = a; t < e; t++) add(acc, load_pt(in + t));
     const uint64_t d = dest[j];
-    st_xyzz((d & SEG_FINAL) ? sums + (d & ~SEG_FINAL) : next + d, acc);
+    store_pt((d & SEG_FINAL) ? sums + (d & ~SEG_FINAL) : next + d, acc);
 }
 
 // H_i = T12'[2i + 1]
@@ -280,11 +203,6 @@ __global__ __launch_bounds__(256) void k_setup_h(uint4 *out, const uint4 *lvl, u
 #pragma unroll
     for (int q = 0; q < 4; q++) out[4 * i + q] = lvl[4 * (2 * i + 1) + q];
 }
-
-inline uint32_t nblocks(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
-
-void normalize(G1Affine *out, const G1XYZZ *tmp, Fq *pref, uint64_t n, hipStream_t s) { launch_normalize_g1(out, tmp, pref, n, s); }
-void normalize(G2Affine *out, const G2XYZZ *tmp, Fq2 *pref, uint64_t n, hipStream_t s) { launch_normalize_g2(out, tmp, pref, n, s); }
 
 struct Sizes {                                      // what zk_groth16_setup_sizes decides, and the walk of the file
     uint32_t k = 0, m = 0, nWires = 0, nPublic = 0;
@@ -336,15 +254,6 @@ void check_views(const zk_r1cs_view *r, const zk_ptau_view *p, Sizes &z) {
     z.nnzB = z.rowptr[2ull * z.m] - z.nnzA;
     if (z.nnz + z.nP1() >= (1ull << 32)) throw std::invalid_argument("r1cs has 2^32 terms or more: not supported");
 }
-
-struct Stream {
-    hipStream_t s = nullptr;
-    Stream() { HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-    ~Stream() {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
-    }
-};
 
 void upload_level(DevBuf<uint8_t> &d, const void *section, uint32_t p, uint64_t pt_bytes, hipStream_t s) {
     const uint64_t count = 1ull << p;
@@ -427,18 +336,8 @@ void groth16_setup(const zk_r1cs_view *r, const zk_ptau_view *p, int32_t device,
     const uint64_t n = z.n(), nw = z.nWires, nP1 = z.nP1(), nC = nw - nP1, nRec = z.nCoefs();
     if (!out->coefs || !out->pointsIC || !out->pointsA || !out->pointsB1 || !out->pointsB2 || !out->pointsH || (nC && !out->pointsC))
         throw std::invalid_argument("null output buffer");
-    need_device_count();
-    int dev = device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    DeviceGuard g(dev);
-    {
-        size_t fr = 0, tot = 0;
-        HIP_TRY(hipMemGetInfo(&fr, &tot));
-        const uint64_t need = hbm_need(z, r), margin = need / 32 + ((uint64_t)256 << 20);
-        if (fr < need + margin)
-            throw HipError("zk_groth16_setup: out of memory (2^" + std::to_string(z.k) + " setup needs " + std::to_string((need + margin) >> 20) +
-                           " MiB of HBM, " + std::to_string(fr >> 20) + " MiB free)");
-    }
+    DeviceGuard g(resolve_device(device));
+    need_hbm("zk_groth16_setup", hbm_need(z, r));
     Stream st;
     const hipStream_t s = st.s;
 
@@ -450,29 +349,13 @@ void groth16_setup(const zk_r1cs_view *r, const zk_ptau_view *p, int32_t device,
     cons.alloc(N);
     coef.alloc(N);
     {
-        DevBuf<uint8_t> raw;
-        DevBuf<uint64_t> d_off, d_ptr;
-        DevBuf<uint32_t> err;
-        raw.alloc(r->constraints_bytes ? r->constraints_bytes : 4);
-        d_off.alloc(z.lc_off.size() ? z.lc_off.size() : 1);
-        d_ptr.alloc(z.rowptr.size());
-        err.alloc(2);
-        {
-            StreamUploader up(s);
-            up.copy(raw.p, r->constraints, r->constraints_bytes);
-        }
-        if (!z.lc_off.empty()) HIP_TRY(hipMemcpyAsync(d_off.p, z.lc_off.data(), z.lc_off.size() * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_ptr.p, z.rowptr.data(), z.rowptr.size() * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(err.p, 0xFF, 8, s));
+        SectionOnDevice sec;
+        sec.upload(r, z.lc_off, z.rowptr, s);
         const uint64_t gsz = N < 256ull * 4096 ? (N + 255) / 256 : 4096;
-        ZK_LAUNCH(k_setup_decode, dim3((uint32_t)gsz), dim3(256), 0, s, wire.p, cons.p, coef.p, err.p, (const uint32_t *)raw.p, d_off.p, d_ptr.p,
-                  (uint32_t)(z.rowptr.size() - 1), z.m, z.nWires, z.nnz, z.nnzA, (uint32_t)nP1);
+        ZK_LAUNCH(k_setup_decode, dim3((uint32_t)gsz), dim3(256), 0, s, wire.p, cons.p, coef.p, sec.err.p, sec.sec(), sec.d_off.p, sec.d_ptr.p, sec.rows(),
+                  z.m, z.nWires, z.nnz, z.nnzA, (uint32_t)nP1);
         ZK_LAUNCH_OK("setup decode");
-        uint32_t bad[2];
-        HIP_TRY(hipMemcpyAsync(bad, err.p, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (bad[0] != NONE) throw std::invalid_argument("r1cs constraint " + std::to_string(bad[0]) + ": wire id >= nWires");
-        if (bad[1] != NONE) throw std::invalid_argument("r1cs constraint " + std::to_string(bad[1]) + ": coefficient >= r");
+        sec.check(s);
     }
 
     // ---- section 4

@@ -7,30 +7,11 @@
 // (Montgomery's batch-inversion trick over the segment's ZZ*ZZZ products).
 #include "kernels.hpp"
 #include "hipcheck.hpp"
+#include "devmem.hpp"
 
 namespace zk {
 
 #define CHAIN_SEG 64u
-
-template <class F>
-__device__ __forceinline__ F ld(const F *p);
-template <>
-__device__ __forceinline__ Fq ld<Fq>(const Fq *p) {
-    const uint4 *q = reinterpret_cast<const uint4 *>(p);
-    uint4 lo = q[0], hi = q[1];
-    Fq r;
-    r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = lo.z; r.v[3] = lo.w;
-    r.v[4] = hi.x; r.v[5] = hi.y; r.v[6] = hi.z; r.v[7] = hi.w;
-    return r;
-}
-template <>
-__device__ __forceinline__ Fq2 ld<Fq2>(const Fq2 *p) { return Fq2{ld(&p->a), ld(&p->b)}; }
-__device__ __forceinline__ void st(Fq *p, const Fq &r) {
-    uint4 *q = reinterpret_cast<uint4 *>(p);
-    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
-__device__ __forceinline__ void st(Fq2 *p, const Fq2 &r) { st(&p->a, r.a); st(&p->b, r.b); }
 
 template <class F>
 __global__ __launch_bounds__(64) void k_chain_walk(XYZZ<F> *tmp, Affine<F> P0, Affine<F> Q, uint64_t n) {
@@ -44,7 +25,7 @@ __global__ __launch_bounds__(64) void k_chain_walk(XYZZ<F> *tmp, Affine<F> P0, A
     madd(acc, P0);
     uint64_t hi = lo + CHAIN_SEG < n ? lo + CHAIN_SEG : n;
     for (uint64_t i = lo; i < hi; i++) {
-        st(&tmp[i].x, acc.x); st(&tmp[i].y, acc.y); st(&tmp[i].zz, acc.zz); st(&tmp[i].zzz, acc.zzz);
+        store_el(&tmp[i].x, acc.x); store_el(&tmp[i].y, acc.y); store_el(&tmp[i].zz, acc.zz); store_el(&tmp[i].zzz, acc.zzz);
         madd(acc, Q);
     }
 }
@@ -56,22 +37,22 @@ __global__ __launch_bounds__(64) void k_chain_normalize(Affine<F> *out, const XY
     uint64_t hi = lo + CHAIN_SEG < n ? lo + CHAIN_SEG : n;
     F acc = F::one();
     for (uint64_t i = lo; i < hi; i++) {
-        st(&pref[i], acc);
-        F t = F::mul(ld(&tmp[i].zz), ld(&tmp[i].zzz));
+        store_el(&pref[i], acc);
+        F t = F::mul(load_el(&tmp[i].zz), load_el(&tmp[i].zzz));
         if (!t.is_zero()) acc = F::mul(acc, t);          // infinity in the chain: skipped
     }
     F inv = F::inv(acc);
     for (uint64_t i = hi; i-- > lo;) {
-        F zz = ld(&tmp[i].zz), zzz = ld(&tmp[i].zzz);
+        F zz = load_el(&tmp[i].zz), zzz = load_el(&tmp[i].zzz);
         F t = F::mul(zz, zzz);
         if (t.is_zero()) {
-            st(&out[i].x, F::zero()); st(&out[i].y, F::zero());
+            store_el(&out[i].x, F::zero()); store_el(&out[i].y, F::zero());
             continue;
         }
-        F ii = F::mul(inv, ld(&pref[i]));                // 1/(zz*zzz)
+        F ii = F::mul(inv, load_el(&pref[i]));                // 1/(zz*zzz)
         inv = F::mul(inv, t);
-        st(&out[i].x, F::mul(ld(&tmp[i].x), F::mul(ii, zzz)));   // X/ZZ
-        st(&out[i].y, F::mul(ld(&tmp[i].y), F::mul(ii, zz)));    // Y/ZZZ
+        store_el(&out[i].x, F::mul(load_el(&tmp[i].x), F::mul(ii, zzz)));   // X/ZZ
+        store_el(&out[i].y, F::mul(load_el(&tmp[i].y), F::mul(ii, zz)));    // Y/ZZZ
     }
 }
 
@@ -100,7 +81,7 @@ __global__ __launch_bounds__(64) void k_fixed_base(XYZZ<F> *tmp, Affine<F> B, co
         acc = dbl(acc);
         if ((k[bit >> 5] >> (bit & 31)) & 1u) madd(acc, B);
     }
-    st(&tmp[i].x, acc.x); st(&tmp[i].y, acc.y); st(&tmp[i].zz, acc.zz); st(&tmp[i].zzz, acc.zzz);
+    store_el(&tmp[i].x, acc.x); store_el(&tmp[i].y, acc.y); store_el(&tmp[i].zz, acc.zz); store_el(&tmp[i].zzz, acc.zzz);
 }
 template <class F>
 static void fixed_base(Affine<F> *d_out, XYZZ<F> *d_tmp, F *d_pref, const Affine<F> &B, const uint32_t *d_scalars, uint64_t n, hipStream_t s) {

@@ -254,6 +254,40 @@ def test_shapes_against_setup_scalars(zk, tmp_path, kind):
     assert got["nCoefs"] == pn
 
 
+def test_base_tables_of_infinity_points(zk, tmp_path):
+    """tau = 1: L_j(1) = 0 for every j > 0 of every level, so all the base points but index 0 are the all-zero infinity
+    encoding and every term outside constraint 0 (the public-input rows included) multiplies infinity, at every bit
+    length.  What is left is row 0: table entry s is (its coefficient of wire s) times G, alpha G or beta G.
+    (oracle.groth16_ref.setup_scalars cannot serve: its _lagrange_at inverts tau - w^j, which is zero here.)"""
+    rng = random.Random("infinity bases")
+    _, alpha, beta = TOXIC3
+    m, nw, npub = 6, 10, 2
+    full = lambda: rng.randrange(RM // 2, RM)
+    A = [[(0, 1), (3, RM - 1), (5, full())]] + [[(rng.randrange(nw), c)] for c in (1, RM - 1, full(), 2, 1 << 100)]
+    B = [[(1, RM - 1), (4, full()), (7, 1)]] + [[(rng.randrange(nw), c)] for c in (full(), 1, RM - 1, 3, RM - 2)]
+    C = [[(2, full()), (5, 1), (9, RM - 1)]] + [[(rng.randrange(nw), c)] for c in (RM - 1, full(), 1, 5, 1 << 200)]
+    assert (len(A), len(B), len(C)) == (m, m, m)
+    rp, pp = str(tmp_path / "c.r1cs"), str(tmp_path / "p.ptau")
+    with open(rp, "wb") as f:
+        f.write(R.write_r1cs_rows(A, B, C, nw, npub))
+    zk.write_trapdoor_ptau(5, 1, alpha, beta, pp)                     # domain 16: power k + 1
+    pf = zk.PtauFile(pp)
+    lvl = np.asarray(pf.level(12, 4)).reshape(-1, 64).copy()
+    pf.close()
+    assert lvl[0].any() and not lvl[1:].any()
+    got = zk.groth16_setup(rp, pp, device=0)
+    assert (got["nVars"], got["nPublic"], got["domainSize"]) == (nw, npub, 16)
+    row0 = lambda M: [dict(M[0]).get(s, 0) for s in range(nw)]
+    a0, b0, c0 = row0(A), row0(B), row0(C)
+    K = [(beta * a + alpha * b + c) % RM for a, b, c in zip(a0, b0, c0)]
+    want = {"pointsA": zk.fixed_base_g1(G1, a0), "pointsB1": zk.fixed_base_g1(G1, b0), "pointsB2": zk.fixed_base_g2(G2, b0),
+            "pointsIC": zk.fixed_base_g1(G1, K[:npub + 1]), "pointsC": zk.fixed_base_g1(G1, K[npub + 1:]),
+            "pointsH": np.zeros(16 * 64, dtype=np.uint8)}
+    for name, v in want.items():
+        assert np.array_equal(np.asarray(got[name]).reshape(-1), v), name
+    assert np.asarray(got["pointsA"]).reshape(-1, 64)[[0, 3, 5]].any(axis=1).all()      # row 0 is there: not everything vanished
+
+
 # ---------------------------------------------------------------- errors
 def test_errors_through_the_abi_and_the_cli(zk, small_ptau, tmp_path):
     c, _ = GOLD["r1cs_n8"]
