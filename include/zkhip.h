@@ -408,6 +408,54 @@ int zk_ptau_prepare_sizes(const zk_ptau_powers_view *ptau, zk_ptau_lagrange_size
  * is an error naming the bytes needed and free.  A point off the curve is an error naming its section and index. */
 int zk_ptau_prepare(const zk_ptau_powers_view *ptau, int32_t device, zk_ptau_lagrange_out *out);
 
+/* ---- Phase-2 contribution: delta <- delta d, sections 8 and 9 <- d^-1 (their points) ------ */
+/* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
+ * counterpart is the arithmetic of snarkjs `zkey contribute`.
+ * The operator: out[i] = k points[i] for n G1 points (the .zkey encoding: affine Montgomery, all-zero = infinity, which
+ * stays all-zero) and ONE scalar k (32 bytes LE, standard form, as zk_g1_mul takes it).  k >= r is an error, k = 0 gives n
+ * points at infinity, n = 0 is legal.  Every point is checked (coordinates below q, y^2 = x^3 + 3) before it is used: one
+ * that fails is an error naming the lowest such index.  The points go through the device in chunks (ZKHIP_SCALE_CHUNK
+ * =<points> in the environment sets their length, 2^20 otherwise) on two buffer sets, so n is not bound by the HBM.
+ * ZKHIP_SCALE_PLAIN=1 computes the same bytes by the plain 254-bit double-and-add (the yardstick of the timing tool).
+ * device -1: the current one. */
+int zk_g1_scale(uint8_t *out, const uint8_t *points, uint64_t n, const uint8_t k[32], int32_t device);
+/* What the host makes of k before the kernel runs, for a check without a device: k = k1 + k2 lambda by BN254's
+ * endomorphism (lambda = 4407920970296243842393367215006156084916469457145843978461, |k1|, |k2| < 2^127), recoded as one
+ * joint signed-digit schedule: *len <= ZK_SCALE_PLAN_MAX columns, digits in {-1, 0, 1}, least significant first, with
+ *     sum_i 2^i (digits_p[i] + lambda digits_phi[i]) = k  (mod r).
+ * cap: the room in both arrays; *len is written even when it exceeds cap (an error).  k >= r is an error. */
+#define ZK_SCALE_PLAN_MAX 130
+int zk_g1_scale_plan(const uint8_t k[32], int8_t *digits_p, int8_t *digits_phi, uint32_t cap, uint32_t *len);
+/* The contribution.  zk_zkey_contrib_view: the key's two delta points (section 2) and its sections 8 (C) and 9 (H) as
+ * pointers and byte sizes into the mapped file.  An empty section 8 (every signal public) is legal. */
+typedef struct zk_zkey_contrib_view {
+    const void *vk_delta1;   /* G1 */
+    const void *vk_delta2;   /* G2 */
+    const void *pointsC;     /* section 8 */
+    const void *pointsH;     /* section 9 */
+    uint64_t pointsC_bytes, pointsH_bytes;
+} zk_zkey_contrib_view;
+typedef struct zk_zkey_contrib_sizes {
+    uint64_t pointsC_bytes, pointsH_bytes;   /* of the output sections: those of the input */
+    uint64_t chunk_points;                   /* points per chunk in effect */
+    uint64_t device_bytes;                   /* HBM the call holds: two buffer sets of one chunk each */
+} zk_zkey_contrib_sizes;
+typedef struct zk_zkey_contrib_out {
+    uint8_t *vk_delta1;      /* 64 bytes */
+    uint8_t *vk_delta2;      /* 128 bytes */
+    uint8_t *pointsC, *pointsH;
+} zk_zkey_contrib_out;
+/* Checks the view without touching a device: a section that is not a whole number of points, a delta point that is not on
+ * its curve. */
+int zk_zkey_contribute_sizes(const zk_zkey_contrib_view *zkey, zk_zkey_contrib_sizes *sizes);
+/* vk_delta1 <- d vk_delta1, vk_delta2 <- d vk_delta2 (on the host, the code of zk_g1_mul / zk_g2_mul), every point of
+ * sections 8 and 9 <- d^-1 point (zk_g1_scale's kernel, chunk by chunk; the caller buffers may be a mapping of the output
+ * file).  d: 32 bytes LE standard form; 0 and d >= r are errors.  Free HBM is checked before anything is allocated: too
+ * little is an error naming the bytes needed and free.  A point off the curve is an error naming its section and index.
+ * d, d^-1 and everything derived from them are zeroed in host and device memory before the call returns; no message of
+ * zk_last_error contains them. */
+int zk_zkey_contribute(const zk_zkey_contrib_view *zkey, const uint8_t d[32], int32_t device, zk_zkey_contrib_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,33 +33,15 @@
 // verify`'s job, and a point outside it still transforms linearly.
 #include "hiputil.hpp"
 #include "devmem.hpp"
+#include "ptcheck.hpp"
 
 namespace {
 
-constexpr uint32_t NONE = 0xFFFFFFFFu;
+constexpr uint32_t NONE = NO_BAD_POINT;
 constexpr uint32_t MAX_POWER = 27;                   // level power + 1 needs a 2^(power+1)-th root of unity; Fr has 2^28
 constexpr uint32_t MAX_LOG_N = 28;
 
-// ---------------------------------------------------------------- load and check
-__device__ __forceinline__ bool below_q(const Fq &a) {
-    uint32_t bw = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) (void)subb(a.v[i], FqParams::P[i], bw);
-    return bw != 0;
-}
-__device__ __forceinline__ bool below_q(const Fq2 &a) { return below_q(a.a) && below_q(a.b); }
-
-// y^2 = x^3 + b (b = 3 in G1, 3 / (9 + u) on the twist), coordinates below q; the lowest failing index goes to *err
-template <class F>
-__global__ __launch_bounds__(256) void k_ptau_check(uint32_t *err, const Affine<F> *src, uint64_t n, F b) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Affine<F> p = load_pt(src + i);
-    if (p.is_inf()) return;
-    const bool ok = below_q(p.x) && below_q(p.y) && F::sqr(p.y) == F::add(F::mul(F::sqr(p.x), p.x), b);
-    if (!ok) atomicMin(err, (uint32_t)i);
-}
-
+// ---------------------------------------------------------------- load
 // A row holds the levels p_lo .. p_hi back to back: place i is point r = i + 2^p_lo - 2^p of level p = floor(log2(i + 2^p_lo))
 __device__ __forceinline__ void row_place(uint64_t i, uint32_t p_lo, uint32_t &p, uint64_t &r) {
     const uint64_t u = i + (1ull << p_lo);
@@ -135,29 +117,6 @@ __global__ __launch_bounds__(64) void k_ptau_scale(XYZZ<F> *y, const Affine<F> *
 }
 
 // ---------------------------------------------------------------- host
-Fq fq_std(uint32_t lo) {                             // small constant -> Montgomery
-    Fq x = Fq::zero();
-    x.v[0] = lo;
-    return Fq::to_mont(x);
-}
-Fq fq_std(const uint32_t w[8]) {
-    Fq x;
-    for (int i = 0; i < 8; i++) x.v[i] = w[i];
-    return Fq::to_mont(x);
-}
-template <class F>
-F curve_b();
-template <>
-Fq curve_b<Fq>() { return fq_std(3); }
-template <>
-Fq2 curve_b<Fq2>() {
-    // 3 / (9 + u) = 19485874751759354771024239261021720505790618469301721065564631296452457478373
-    //             + 266929791119991161246907387137283842545076965332900288569378510910307636690 u
-    static const uint32_t a[8] = {0x24a138e5u, 0x3267e6dcu, 0x59dbefa3u, 0xb5b4c5e5u, 0x1be06ac3u, 0x81be1899u, 0xceb8aaaeu, 0x2b149d40u};
-    static const uint32_t b[8] = {0x85c315d2u, 0xe4a2bd06u, 0xe52d1852u, 0xa74fa084u, 0xeed8fdf4u, 0xcd2cafadu, 0x3af0fed4u, 0x009713b0u};
-    return Fq2{fq_std(a), fq_std(b)};
-}
-
 // w_(2^28), standard form (ntt.hip)
 const uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
 
@@ -238,9 +197,7 @@ uint32_t load_checked(DevBuf<Affine<F>> &d_src, const void *points, uint64_t n_s
     }
     DevBuf<uint32_t> err;
     err.alloc(1);
-    HIP_TRY(hipMemsetAsync(err.p, 0xFF, 4, s));
-    ZK_LAUNCH(k_ptau_check<F>, dim3(nblocks(n_src, 256)), dim3(256), 0, s, err.p, d_src.p, n_src, curve_b<F>());
-    ZK_LAUNCH_OK("ptau check");
+    launch_point_check<F>(err.p, d_src.p, n_src, s);
     uint32_t bad = NONE;
     HIP_TRY(hipMemcpyAsync(&bad, err.p, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -18,6 +18,7 @@
 #include "../csrc/common.hpp"
 #include "../csrc/field64.hpp"
 #include "outfile.hpp"
+#include "vkjson.hpp"
 #include "zkfile.hpp"
 
 namespace {
@@ -40,14 +41,6 @@ void generators(uint8_t g1[64], uint8_t g2[128]) {
     fq_mont(g2 + 32, 0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull);
     fq_mont(g2 + 64, 0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
     fq_mont(g2 + 96, 0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
-}
-
-std::string g1_json(const uint8_t *p) {
-    return "[\"" + zk::HostTail::fq_mont_to_dec(p) + "\", \"" + zk::HostTail::fq_mont_to_dec(p + 32) + "\", \"1\"]";
-}
-std::string g2_json(const uint8_t *p) {
-    auto d = [&](int i) { return "\"" + zk::HostTail::fq_mont_to_dec(p + 32 * i) + "\""; };
-    return "[[" + d(0) + ", " + d(1) + "], [" + d(2) + ", " + d(3) + "], [\"1\", \"0\"]]";
 }
 
 int run(const std::string &r1csPath, const std::string &ptauPath, const std::string &zkeyPath, const std::string &vkPath) {
@@ -116,12 +109,7 @@ int run(const std::string &r1csPath, const std::string &ptauPath, const std::str
     std::unique_ptr<OutFile> vk;
     if (!vkPath.empty()) {
         vk.reset(new OutFile(vkPath));
-        std::string j = "{\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\",\n \"nPublic\": " + std::to_string(sz.nPublic) + ",\n";
-        j += " \"vk_alpha_1\": " + g1_json(static_cast<const uint8_t *>(ph->alpha1)) + ",\n";
-        j += " \"vk_beta_2\": " + g2_json(static_cast<const uint8_t *>(ph->beta2)) + ",\n";
-        j += " \"vk_gamma_2\": " + g2_json(g2) + ",\n \"vk_delta_2\": " + g2_json(g2) + ",\n \"IC\": [";
-        for (uint64_t i = 0; i < np1; i++) j += std::string(i ? ",\n  " : "\n  ") + g1_json(ic.data() + 64 * i);
-        j += "\n ]\n}";
+        const std::string j = verification_key_json(sz.nPublic, static_cast<const uint8_t *>(ph->alpha1), static_cast<const uint8_t *>(ph->beta2), g2, g2, ic.data());
         vk->write(j.data(), j.size());
     }
     z.commit();

@@ -87,6 +87,19 @@ class zk_ptau_lagrange_out(C.Structure):
     _fields_ = [("lagrange_g1", C.c_void_p), ("lagrange_g2", C.c_void_p), ("lagrange_alpha_g1", C.c_void_p), ("lagrange_beta_g1", C.c_void_p)]
 
 
+class zk_zkey_contrib_view(C.Structure):
+    _fields_ = [("vk_delta1", C.c_void_p), ("vk_delta2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p),
+                ("pointsC_bytes", C.c_uint64), ("pointsH_bytes", C.c_uint64)]
+
+
+class zk_zkey_contrib_sizes(C.Structure):
+    _fields_ = [("pointsC_bytes", C.c_uint64), ("pointsH_bytes", C.c_uint64), ("chunk_points", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class zk_zkey_contrib_out(C.Structure):
+    _fields_ = [("vk_delta1", C.c_void_p), ("vk_delta2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -126,7 +139,9 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_multi_prover_info", "zk_shard_info", "zk_shard_set_exchange", "zk_shard_begin", "zk_shard_step",
            "zk_r1cs_create", "zk_r1cs_destroy", "zk_r1cs_check", "zk_r1cs_check_dev", "zk_r1cs_match_zkey",
            "zk_groth16_setup_sizes", "zk_groth16_setup",
-           "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare"]
+           "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare",
+           "zk_g1_scale", "zk_g1_scale_plan", "zk_zkey_contribute_sizes", "zk_zkey_contribute"]
+ZK_SCALE_PLAN_MAX = 130
 
 
 def load_library():
@@ -216,6 +231,11 @@ def load_library():
         lib.zk_g2_lagrange.argtypes = [u8p, u8p, C.c_uint64, C.c_uint32, C.c_int32]
         lib.zk_ptau_prepare_sizes.argtypes = [C.POINTER(zk_ptau_powers_view), C.POINTER(zk_ptau_lagrange_sizes)]
         lib.zk_ptau_prepare.argtypes = [C.POINTER(zk_ptau_powers_view), C.c_int32, C.POINTER(zk_ptau_lagrange_out)]
+    if hasattr(lib, "zk_g1_scale"):
+        lib.zk_g1_scale.argtypes = [u8p, u8p, C.c_uint64, u8p, C.c_int32]
+        lib.zk_g1_scale_plan.argtypes = [u8p, C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.zk_zkey_contribute_sizes.argtypes = [C.POINTER(zk_zkey_contrib_view), C.POINTER(zk_zkey_contrib_sizes)]
+        lib.zk_zkey_contribute.argtypes = [C.POINTER(zk_zkey_contrib_view), u8p, C.c_int32, C.POINTER(zk_zkey_contrib_out)]
     _LIB = lib
     return lib
 
@@ -399,6 +419,39 @@ def g1_lagrange(points, log_n, device=-1):
 
 def g2_lagrange(points, log_n, device=-1):
     return _lagrange("zk_g2_lagrange", 128, points, log_n, device)
+
+
+def _scalar32(k):
+    k = int(k)
+    if not 0 <= k < 1 << 256:
+        raise ValueError("scalar: 0 <= k < 2^256 expected")
+    return np.frombuffer(k.to_bytes(32, "little"), dtype=np.uint8).copy()
+
+
+def g1_scale(points, k, device=-1):
+    """[k * P for P in points] on the GPU (zk_g1_scale): n x 64 B affine Montgomery in, numpy uint8 [n * 64] out, all-zero =
+    infinity.  One scalar for all points (int, 0 <= k < r): the host splits it by BN254's endomorphism and recodes it once.
+    Raises ZkHipError for k >= r and for a point that is not on the curve (the message names its index)."""
+    pts = _buf(points)
+    if pts.size % 64:
+        raise ValueError("points: a multiple of 64 bytes expected")
+    fn = getattr(load_library(), "zk_g1_scale", None)
+    if fn is None:
+        raise ZkHipError("zk_g1_scale is not in this build of libzkhip.so")
+    out = np.zeros(pts.size, dtype=np.uint8)
+    kk = _scalar32(k)
+    check(fn(_ptr(out) if pts.size else None, _ptr(pts) if pts.size else None, pts.size // 64, _ptr(kk), device))
+    return out
+
+
+def g1_scale_plan(k):
+    """zk_g1_scale_plan -> (digits_p, digits_phi): the joint signed-digit schedule the host makes of k, least significant
+    first, sum 2^i (digits_p[i] + lambda digits_phi[i]) = k mod r.  No device is touched."""
+    a, b = (C.c_int8 * ZK_SCALE_PLAN_MAX)(), (C.c_int8 * ZK_SCALE_PLAN_MAX)()
+    n = C.c_uint32(0)
+    kk = _scalar32(k)
+    check(load_library().zk_g1_scale_plan(_ptr(kk), a, b, ZK_SCALE_PLAN_MAX, C.byref(n)))
+    return list(a[:n.value]), list(b[:n.value])
 
 
 def g1_mul(p, k):
