@@ -456,6 +456,41 @@ int zk_zkey_contribute_sizes(const zk_zkey_contrib_view *zkey, zk_zkey_contrib_s
  * zk_last_error contains them. */
 int zk_zkey_contribute(const zk_zkey_contrib_view *zkey, const uint8_t d[32], int32_t device, zk_zkey_contrib_out *out);
 
+/* ---- Pairing and verification: the optimal ate pairing on BN254, Groth16 verify ---------- */
+/* Nothing in the reference corresponds to these entry points (it only proves); the counterpart is snarkjs `groth16
+ * verify`.  Points are in the .zkey encoding (affine Montgomery, all-zero = infinity).
+ * The pairs (g1[i], g2[i]), i < n_pairs, are taken in consecutive groups of `group` (the last may be shorter); out receives
+ * 384 bytes per group: the final-exponentiated product of e(P_i, Q_i) over the group, as 12 Fq values of 32 bytes
+ * little-endian in standard form (NOT Montgomery), in the order c0.c0.re, c0.c0.im, c0.c1.re, ... c1.c2.im of
+ * Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - (9 + u)), Fq2 = Fq[u]/(u^2 + 1), G2 on the D-type twist untwisted by
+ * (x, y) -> (x w^2, y w^3).  A pair with a point at infinity contributes 1.  Every point is checked first (coordinates
+ * below q, the curve's / the twist's equation, and [r] Q = infinity in G2): one that fails is an error naming its index,
+ * "pairing: G2 point 37 is not in the subgroup".  n_pairs = 0 is legal, group = 0 an error.  The groups go through the
+ * device in chunks of ZKHIP_VERIFY_CHUNK (2^16 otherwise).  device -1: the current one. */
+int zk_pairing(uint8_t *out, const uint8_t *g1, const uint8_t *g2, uint64_t n_pairs, uint32_t group, int32_t device);
+/* A verification key on a device.  create checks the key's points (alpha, beta, gamma, delta not infinity and on their
+ * curves, the three G2 points in the subgroup, every IC point on the curve), uploads IC, writes the line coefficients of
+ * gamma and delta and the Miller value of (alpha, beta) once. */
+typedef struct zk_vkey zk_vkey;
+typedef struct zk_vkey_view {
+    const void *vk_alpha1;                  /* G1, 64 bytes */
+    const void *vk_beta2, *vk_gamma2, *vk_delta2;   /* G2, 128 bytes each */
+    const void *IC;                         /* (nPublic + 1) x 64 bytes */
+    uint32_t nPublic;
+} zk_vkey_view;
+int zk_vkey_create(zk_vkey **out, const zk_vkey_view *view, int32_t device);
+void zk_vkey_destroy(zk_vkey *vk);
+/* verdict[i] of proof i: OK; INVALID: well-formed, but e(A, B) != e(alpha, beta) e(vk_x, gamma) e(C, delta); MALFORMED: a
+ * coordinate not below q, A or C off the curve, B off the twist or outside the order-r subgroup, A, B or C at infinity, a
+ * public signal not below r.  proofs: n x 256 bytes, A 64 | B 128 | C 64 (the layout of zk_proof); publics: n x nPublic x
+ * 32 bytes little-endian standard form (may be NULL when nPublic = 0).  The return value tells only whether the call ran.
+ * Proofs go through the device in chunks of ZKHIP_VERIFY_CHUNK (2^16 otherwise): the device memory held does not grow
+ * with n.  Calls on one key are serialised.  Each proof gets its own verdict; nothing is batched by random combination. */
+#define ZK_VERIFY_OK 0
+#define ZK_VERIFY_INVALID 1
+#define ZK_VERIFY_MALFORMED 2
+int zk_vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict);
+
 #ifdef __cplusplus
 }
 #endif

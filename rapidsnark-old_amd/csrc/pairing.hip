@@ -1,0 +1,454 @@
+// Pairings and Groth16 verification on the device (include/zkhip.h, section "Pairing and verification").  Nothing in the
+// reference corresponds to it (it only proves); the counterpart is snarkjs `groth16 verify`.  The arithmetic is
+// pairing.hpp's; this file is the lane mapping, the checks made before any pairing, and the entry points.
+//
+// One lane per job.  A job is a group of (P, Q) pairs that share one f: one squaring chain per group, each pair's line
+// multiplied in at every step.  No lane talks to another.
+//   zk_pairing: every Q is the caller's, so every pair carries a running T; it lives in device memory (192 B a pair) and
+//   is loaded, stepped and stored per line.  k_miller_groups, then k_final_exp.
+//   zk_vkey_verify: e(-A, B) e(alpha, beta) e(vk_x, gamma) e(C, delta) = 1.  gamma and delta are the key's: k_line_table
+//   writes the MILLER_LINES line coefficients of each once, when the key is made, and k_verify_miller reads them with a
+//   wave-uniform index and evaluates them at the lane's own vk_x and C; only B carries a T, in the lane's own memory.  The
+//   Miller value of (alpha, beta) is made once and multiplied in.  Per proof: one variable-Q loop, two table-driven ones,
+//   one Fq12 product, one final exponentiation.
+//
+// Checks before any pairing (k_pair_check, k_verify_check): coordinates below q, y^2 = x^3 + 3 in G1, y^2 = x^3 + 3/xi on
+// the twist, and membership of the order-r subgroup of the twist by [r] Q = infinity (devmem.hpp's scalar_mul_affine over
+// the 254 bits of r: the plain test, about as many Fq products as the Miller loop itself; an endomorphism test would be
+// several times cheaper and is not built).  Public signals below r.  vk_x = IC_0 + sum pub_j IC_j per lane, by the same
+// scalar_mul_affine and curve.hpp's add, which take every special case; vk_x = infinity is legal and contributes 1.
+//
+// Field form: field.hpp's 8 x 32-bit Montgomery words, the form of the .zkey's and the proof's own bytes and of every
+// helper used here (ptcheck.hpp, curve.hpp, devmem.hpp).  field29.hpp's multiplier is about twice as fast; DESIGN.md
+// section 17 says what that choice costs and why it was made.
+#include <memory>
+#include <mutex>
+
+#include "hiputil.hpp"
+#include "devmem.hpp"
+#include "ptcheck.hpp"
+#include "pairing.hpp"
+
+namespace {
+
+constexpr uint64_t DEFAULT_CHUNK = 1ull << 16;        // jobs per chunk
+constexpr uint32_t ST_OK = 0, ST_MALFORMED = 1;       // k_verify_check's word per proof
+
+static_assert(sizeof(G1Affine) == 64 && sizeof(G2Affine) == 128 && sizeof(Fq12) == 384 && sizeof(G2Proj) == 192 && sizeof(Line) == 192, "layout");
+
+// ---------------------------------------------------------------- device: checks
+__device__ __forceinline__ bool below_r(const Fr &a) {
+    uint32_t bw = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) (void)subb(a.v[i], FrParams::P[i], bw);
+    return bw != 0;
+}
+template <class F>
+__device__ __forceinline__ bool on_curve(const Affine<F> &p, const F &b) {
+    return below_q(p.x) && below_q(p.y) && F::sqr(p.y) == F::add(F::mul(F::sqr(p.x), p.x), b);
+}
+__device__ __noinline__ bool in_subgroup(const G2Affine &Q) {   // [r] Q = infinity
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = FrParams::P[i];
+    return scalar_mul_affine(Q, r).is_inf();
+}
+
+// err[0]: the lowest G1 index off the curve, err[1]: the lowest G2 index off the twist, err[2]: the lowest G2 index
+// outside the subgroup (NO_BAD_POINT: none).  The all-zero encoding (infinity) passes.
+__global__ __launch_bounds__(64) void k_pair_check(uint32_t *err, const G1Affine *__restrict__ g1, uint64_t n1, const G2Affine *__restrict__ g2,
+                                                   uint64_t n2, Fq b1, Fq2 b2) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n1) {
+        const G1Affine P = load_pt(g1 + i);
+        if (!P.is_inf() && !on_curve(P, b1)) atomicMin(err + 0, (uint32_t)i);
+    }
+    if (i < n2) {
+        const G2Affine Q = load_pt(g2 + i);
+        if (!Q.is_inf()) {
+            if (!on_curve(Q, b2)) atomicMin(err + 1, (uint32_t)i);
+            else if (!in_subgroup(Q)) atomicMin(err + 2, (uint32_t)i);
+        }
+    }
+}
+
+// ---------------------------------------------------------------- device: constants, tables
+__global__ void k_pair_consts(PairConsts *k) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) pair_consts_init(*k);
+}
+
+// tab[j * MILLER_LINES + i]: line i of the loop over Q[j], to be evaluated at any P (f12_mul_line_at)
+__global__ __launch_bounds__(64) void k_line_table(Line *tab, const G2Affine *Q, uint32_t n, const PairConsts *k) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const G2Affine q = load_pt(Q + j);
+    G2Proj T{q.x, q.y, Fq2::one()};
+    Line *out = tab + (uint64_t)j * MILLER_LINES;
+    Line l;
+    int at = 0;
+    for (int i = 0; i < 64; i++) {
+        step_dbl(T, l, *k);
+        out[at++] = l;
+        if (ate_bit(i)) {
+            step_add(T, l, q);
+            out[at++] = l;
+        }
+    }
+    G2Affine q1, q2;
+    frob_twist(q1, q2, q, *k);
+    step_add(T, l, q1);
+    out[at++] = l;
+    step_add(T, l, q2);
+    out[at++] = l;
+}
+
+// ---------------------------------------------------------------- device: Miller loops
+// f_out[j] = prod over the pairs p of group j of the Miller value of (g1[p], g2[p]); a pair with a point at infinity
+// contributes 1.  T: n_pairs running points, this kernel's own.
+__global__ __launch_bounds__(64) void k_miller_groups(Fq12 *f_out, const G1Affine *__restrict__ g1, const G2Affine *__restrict__ g2, G2Proj *T,
+                                                      uint64_t n_pairs, uint32_t group, const PairConsts *k) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t lo = j * group;
+    if (lo >= n_pairs) return;
+    const uint64_t hi = n_pairs - lo < group ? n_pairs : lo + group;
+    Fq12 f;
+    f12_one(f);
+    Line l;
+    for (uint64_t p = lo; p < hi; p++) {
+        const G2Affine Q = load_pt(g2 + p);
+        T[p] = G2Proj{Q.x, Q.y, Fq2::one()};
+    }
+    for (int i = 0; i <= 64; i++) {                   // i = 64: the two Frobenius chords
+        if (i < 64) f12_sqr(f, f);
+        for (uint64_t p = lo; p < hi; p++) {
+            const G1Affine P = load_pt(g1 + p);
+            const G2Affine Q = load_pt(g2 + p);
+            if (P.is_inf() || Q.is_inf()) continue;
+            G2Proj t = T[p];
+            if (i < 64) {
+                step_dbl(t, l, *k);
+                f12_mul_line_at(f, l, P);
+                if (ate_bit(i)) {
+                    step_add(t, l, Q);
+                    f12_mul_line_at(f, l, P);
+                }
+            } else {
+                G2Affine q1, q2;
+                frob_twist(q1, q2, Q, *k);
+                step_add(t, l, q1);
+                f12_mul_line_at(f, l, P);
+                step_add(t, l, q2);
+                f12_mul_line_at(f, l, P);
+            }
+            T[p] = t;
+        }
+    }
+    f_out[j] = f;
+}
+
+// out[j]: the final exponentiation of f[j] as 12 x 32 bytes little-endian, standard form
+__global__ __launch_bounds__(64) void k_final_exp(uint8_t *out, const Fq12 *f, uint64_t n, const PairConsts *k) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    Fq12 r;
+    final_exp(r, f[j], *k);
+    const Fq *c = reinterpret_cast<const Fq *>(&r);
+    Fq *o = reinterpret_cast<Fq *>(out + j * sizeof(Fq12));
+    for (int i = 0; i < 12; i++) store_el(o + i, Fq::from_mont(c[i]));
+}
+
+// ---------------------------------------------------------------- device: verification
+__device__ __forceinline__ G1Affine g1_to_affine(const G1XYZZ &p) {
+    if (p.is_inf()) return G1Affine::inf();
+    const Fq t = Fq::inv(Fq::mul(p.zz, p.zzz));       // x = X/ZZ, y = Y/ZZZ by one inversion
+    return G1Affine{Fq::mul(p.x, Fq::mul(t, p.zzz)), Fq::mul(p.y, Fq::mul(t, p.zz))};
+}
+
+// status[i], and vk_x of proof i when it is well-formed.  proofs: A 64 | B 128 | C 64; publics: n x nPublic x 32 B
+__global__ __launch_bounds__(64) void k_verify_check(uint32_t *status, G1Affine *vkx, const uint8_t *__restrict__ proofs, const Fr *__restrict__ publics,
+                                                     uint64_t n, uint32_t nPublic, const G1Affine *__restrict__ ic, Fq b1, Fq2 b2) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *pr = proofs + i * 256;
+    const G1Affine A = load_pt(reinterpret_cast<const G1Affine *>(pr));
+    const G2Affine B = load_pt(reinterpret_cast<const G2Affine *>(pr + 64));
+    const G1Affine C = load_pt(reinterpret_cast<const G1Affine *>(pr + 192));
+    bool ok = !A.is_inf() && !B.is_inf() && !C.is_inf() && on_curve(A, b1) && on_curve(C, b1) && on_curve(B, b2);
+    const Fr *pub = publics + i * nPublic;
+    for (uint32_t j = 0; ok && j < nPublic; j++) ok = below_r(load_el(pub + j));
+    if (ok) ok = in_subgroup(B);
+    status[i] = ok ? ST_OK : ST_MALFORMED;
+    if (!ok) return;
+    G1XYZZ acc = G1XYZZ::from_affine(load_pt(ic));
+    for (uint32_t j = 0; j < nPublic; j++) {
+        const G1XYZZ t = scalar_mul_affine(load_pt(ic + 1 + j), load_el(pub + j));
+        add(acc, t);
+    }
+    const G1Affine X = g1_to_affine(acc);
+    store_el(&vkx[i].x, X.x);
+    store_el(&vkx[i].y, X.y);
+}
+
+// f_out[i] = miller(-A, B) miller(vk_x, gamma) miller(C, delta) miller(alpha, beta); tab: gamma's lines, then delta's
+__global__ __launch_bounds__(64) void k_verify_miller(Fq12 *f_out, const uint32_t *__restrict__ status, const uint8_t *__restrict__ proofs,
+                                                      const G1Affine *__restrict__ vkx, const Line *__restrict__ tab, const Fq12 *ml_ab, uint64_t n,
+                                                      const PairConsts *k) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || status[i] != ST_OK) return;
+    const uint8_t *pr = proofs + i * 256;
+    G1Affine A = load_pt(reinterpret_cast<const G1Affine *>(pr));
+    A.y = Fq::neg(A.y);
+    const G2Affine B = load_pt(reinterpret_cast<const G2Affine *>(pr + 64));
+    const G1Affine C = load_pt(reinterpret_cast<const G1Affine *>(pr + 192));
+    const G1Affine X = load_pt(vkx + i);
+    const bool have_x = !X.is_inf();
+    const Line *tg = tab, *td = tab + MILLER_LINES;
+    G2Proj T{B.x, B.y, Fq2::one()};
+    G2Affine q1, q2;
+    frob_twist(q1, q2, B, *k);
+    Fq12 f;
+    f12_one(f);
+    Line l;
+    int at = 0;                                       // wave-uniform: the index into both tables
+    auto lines = [&]() {                              // the line just made at -A, and the tables' lines at vk_x and C
+        f12_mul_line_at(f, l, A);
+        if (have_x) f12_mul_line_at(f, tg[at], X);
+        f12_mul_line_at(f, td[at], C);
+        at++;
+    };
+    for (int s = 0; s < 64; s++) {
+        f12_sqr(f, f);
+        step_dbl(T, l, *k);
+        lines();
+        if (ate_bit(s)) {
+            step_add(T, l, B);
+            lines();
+        }
+    }
+    step_add(T, l, q1);
+    lines();
+    step_add(T, l, q2);
+    lines();
+    f12_mul(f, f, *ml_ab);
+    f_out[i] = f;
+}
+
+__global__ __launch_bounds__(64) void k_verify_final(uint8_t *verdict, const Fq12 *f, const uint32_t *__restrict__ status, uint64_t n, const PairConsts *k) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (status[i] != ST_OK) {
+        verdict[i] = ZK_VERIFY_MALFORMED;
+        return;
+    }
+    Fq12 r;
+    final_exp(r, f[i], *k);
+    verdict[i] = f12_is_one(r) ? ZK_VERIFY_OK : ZK_VERIFY_INVALID;
+}
+
+// ---------------------------------------------------------------- host
+uint64_t chunk_jobs() {
+    const char *e = getenv("ZKHIP_VERIFY_CHUNK");
+    if (e && *e) {
+        char *end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (*end || v < 1 || v > (1ull << 24)) throw std::invalid_argument("ZKHIP_VERIFY_CHUNK: a number of proofs from 1 to 2^24 expected");
+        return v;
+    }
+    return DEFAULT_CHUNK;
+}
+
+struct Consts {
+    DevBuf<PairConsts> k;
+    void make(hipStream_t s) {
+        k.alloc(1);
+        ZK_LAUNCH(k_pair_consts, dim3(1), dim3(1), 0, s, k.p);
+        ZK_LAUNCH_OK("pairing constants");
+    }
+};
+
+// the three words of k_pair_check after the stream has drained
+struct CheckWords {
+    DevBuf<uint32_t> d;
+    uint32_t h[3];
+    void run(const G1Affine *g1, uint64_t n1, const G2Affine *g2, uint64_t n2, hipStream_t s) {
+        if (!d.p) d.alloc(3);
+        HIP_TRY(hipMemsetAsync(d.p, 0xFF, 12, s));
+        const uint64_t n = n1 > n2 ? n1 : n2;
+        if (n) ZK_LAUNCH(k_pair_check, dim3(nblocks(n, 64)), dim3(64), 0, s, d.p, g1, n1, g2, n2, curve_b<Fq>(), curve_b<Fq2>());
+        ZK_LAUNCH_OK("pairing point check");
+        HIP_TRY(hipMemcpyAsync(h, d.p, 12, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+};
+
+void pairing(uint8_t *out, const uint8_t *g1, const uint8_t *g2, uint64_t n_pairs, uint32_t group, int32_t device) {
+    if (!group) throw std::invalid_argument("zk_pairing: group is 0");
+    if (!n_pairs) return;
+    if (!out || !g1 || !g2) throw std::invalid_argument("null argument");
+    const uint64_t jobs = (n_pairs + group - 1) / group, chunk = chunk_jobs();
+    const uint64_t cap_jobs = jobs < chunk ? jobs : chunk;
+    if (cap_jobs > (1ull << 31) / group) throw std::invalid_argument("zk_pairing: a chunk of " + std::to_string(cap_jobs) + " groups of " + std::to_string(group) + " pairs is too large");
+    const uint64_t cap_pairs = cap_jobs * group < n_pairs ? cap_jobs * group : n_pairs;
+    DeviceGuard g(resolve_device(device));
+    need_hbm("zk_pairing", cap_pairs * (sizeof(G1Affine) + sizeof(G2Affine) + sizeof(G2Proj)) + cap_jobs * 2 * sizeof(Fq12) + 65536);
+    Stream st;
+    hipStream_t s = st.s;
+    Consts kc;
+    kc.make(s);
+    DevBuf<G1Affine> d1;
+    DevBuf<G2Affine> d2;
+    DevBuf<G2Proj> dT;
+    DevBuf<Fq12> df;
+    DevBuf<uint8_t> dout;
+    CheckWords cw;
+    d1.alloc(cap_pairs);
+    d2.alloc(cap_pairs);
+    dT.alloc(cap_pairs);
+    df.alloc(cap_jobs);
+    dout.alloc(cap_jobs * sizeof(Fq12));
+    for (uint64_t j0 = 0; j0 < jobs; j0 += cap_jobs) {
+        const uint64_t nj = jobs - j0 < cap_jobs ? jobs - j0 : cap_jobs;
+        const uint64_t p0 = j0 * group, np = n_pairs - p0 < nj * group ? n_pairs - p0 : nj * group;
+        HIP_TRY(hipMemcpyAsync(d1.p, g1 + p0 * sizeof(G1Affine), np * sizeof(G1Affine), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d2.p, g2 + p0 * sizeof(G2Affine), np * sizeof(G2Affine), hipMemcpyHostToDevice, s));
+        cw.run(d1.p, np, d2.p, np, s);
+        if (cw.h[0] != NO_BAD_POINT) throw std::invalid_argument("pairing: G1 point " + std::to_string(p0 + cw.h[0]) + " is not on the curve");
+        if (cw.h[1] != NO_BAD_POINT) throw std::invalid_argument("pairing: G2 point " + std::to_string(p0 + cw.h[1]) + " is not on the curve");
+        if (cw.h[2] != NO_BAD_POINT) throw std::invalid_argument("pairing: G2 point " + std::to_string(p0 + cw.h[2]) + " is not in the subgroup");
+        ZK_LAUNCH(k_miller_groups, dim3(nblocks(nj, 64)), dim3(64), 0, s, df.p, d1.p, d2.p, dT.p, np, group, kc.k.p);
+        ZK_LAUNCH(k_final_exp, dim3(nblocks(nj, 64)), dim3(64), 0, s, dout.p, df.p, nj, kc.k.p);
+        ZK_LAUNCH_OK("pairing");
+        HIP_TRY(hipMemcpyAsync(out + j0 * sizeof(Fq12), dout.p, nj * sizeof(Fq12), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+}
+
+}   // namespace
+
+// The key on its device: IC, the line tables of gamma and delta, the Miller value of (alpha, beta), the constants.
+struct zk_vkey {
+    int device = 0;
+    uint32_t nPublic = 0;
+    std::mutex mu;                                    // calls on one key are serialised
+    Consts kc;
+    DevBuf<G1Affine> ic;
+    DevBuf<Line> tab;
+    DevBuf<Fq12> ml_ab;
+};
+
+namespace {
+
+bool all_zero(const void *p, size_t n) {
+    const uint8_t *b = static_cast<const uint8_t *>(p);
+    for (size_t i = 0; i < n; i++)
+        if (b[i]) return false;
+    return true;
+}
+
+zk_vkey *vkey_create(const zk_vkey_view *v, int32_t device) {
+    if (!v || !v->vk_alpha1 || !v->vk_beta2 || !v->vk_gamma2 || !v->vk_delta2 || !v->IC) throw std::invalid_argument("null argument");
+    const void *g2s[3] = {v->vk_beta2, v->vk_gamma2, v->vk_delta2};
+    static const char *const g2name[3] = {"vk_beta_2", "vk_gamma_2", "vk_delta_2"};
+    if (all_zero(v->vk_alpha1, sizeof(G1Affine))) throw std::invalid_argument("verification key: vk_alpha_1 is the point at infinity");
+    for (int i = 0; i < 3; i++)
+        if (all_zero(g2s[i], sizeof(G2Affine))) throw std::invalid_argument(std::string("verification key: ") + g2name[i] + " is the point at infinity");
+    const uint64_t n1 = (uint64_t)v->nPublic + 2;     // alpha, then IC
+    std::unique_ptr<zk_vkey> vk(new zk_vkey);
+    vk->device = resolve_device(device);
+    vk->nPublic = v->nPublic;
+    DeviceGuard g(vk->device);
+    need_hbm("zk_vkey_create", n1 * sizeof(G1Affine) + 2 * MILLER_LINES * sizeof(Line) + 65536);
+    Stream st;
+    hipStream_t s = st.s;
+    DevBuf<G1Affine> d1;
+    DevBuf<G2Affine> d2;
+    DevBuf<G2Proj> dT;
+    d1.alloc(n1);
+    d2.alloc(3);
+    dT.alloc(1);
+    HIP_TRY(hipMemcpyAsync(d1.p, v->vk_alpha1, sizeof(G1Affine), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d1.p + 1, v->IC, (n1 - 1) * sizeof(G1Affine), hipMemcpyHostToDevice, s));
+    for (int i = 0; i < 3; i++) HIP_TRY(hipMemcpyAsync(d2.p + i, g2s[i], sizeof(G2Affine), hipMemcpyHostToDevice, s));
+    CheckWords cw;
+    cw.run(d1.p, n1, d2.p, 3, s);
+    if (cw.h[0] == 0) throw std::invalid_argument("verification key: vk_alpha_1 is not on the curve");
+    if (cw.h[0] != NO_BAD_POINT) throw std::invalid_argument("verification key: IC point " + std::to_string(cw.h[0] - 1) + " is not on the curve");
+    if (cw.h[1] != NO_BAD_POINT) throw std::invalid_argument(std::string("verification key: ") + g2name[cw.h[1]] + " is not on the curve");
+    if (cw.h[2] != NO_BAD_POINT) throw std::invalid_argument(std::string("verification key: ") + g2name[cw.h[2]] + " is not in the subgroup");
+    vk->kc.make(s);
+    vk->ic.alloc(n1 - 1);
+    vk->tab.alloc(2 * MILLER_LINES);
+    vk->ml_ab.alloc(1);
+    HIP_TRY(hipMemcpyAsync(vk->ic.p, d1.p + 1, (n1 - 1) * sizeof(G1Affine), hipMemcpyDeviceToDevice, s));
+    ZK_LAUNCH(k_line_table, dim3(1), dim3(64), 0, s, vk->tab.p, d2.p + 1, 2u, vk->kc.k.p);
+    ZK_LAUNCH(k_miller_groups, dim3(1), dim3(64), 0, s, vk->ml_ab.p, d1.p, d2.p, dT.p, (uint64_t)1, 1u, vk->kc.k.p);
+    ZK_LAUNCH_OK("verification key set-up");
+    HIP_TRY(hipStreamSynchronize(s));
+    return vk.release();
+}
+
+void vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict) {
+    if (!vk) throw std::invalid_argument("null argument");
+    if (!n) return;
+    if (!proofs || !verdict || (vk->nPublic && !publics)) throw std::invalid_argument("null argument");
+    std::lock_guard<std::mutex> lock(vk->mu);
+    const uint64_t chunk = chunk_jobs(), cap = n < chunk ? n : chunk, pub_bytes = (uint64_t)vk->nPublic * 32;
+    DeviceGuard g(vk->device);
+    need_hbm("zk_vkey_verify", cap * (256 + pub_bytes + 4 + sizeof(G1Affine) + sizeof(Fq12) + 1) + 65536);
+    Stream st;
+    hipStream_t s = st.s;
+    DevBuf<uint8_t> dp, dv;
+    DevBuf<Fr> dpub;
+    DevBuf<uint32_t> dst;
+    DevBuf<G1Affine> dx;
+    DevBuf<Fq12> df;
+    dp.alloc(cap * 256);
+    dv.alloc(cap);
+    dpub.alloc(cap * vk->nPublic);
+    dst.alloc(cap);
+    dx.alloc(cap);
+    df.alloc(cap);
+    for (uint64_t off = 0; off < n; off += cap) {
+        const uint64_t cnt = n - off < cap ? n - off : cap;
+        const dim3 grid(nblocks(cnt, 64)), block(64);
+        HIP_TRY(hipMemcpyAsync(dp.p, proofs + off * 256, cnt * 256, hipMemcpyHostToDevice, s));
+        if (pub_bytes) HIP_TRY(hipMemcpyAsync(dpub.p, publics + off * pub_bytes, cnt * pub_bytes, hipMemcpyHostToDevice, s));
+        ZK_LAUNCH(k_verify_check, grid, block, 0, s, dst.p, dx.p, dp.p, dpub.p, cnt, vk->nPublic, vk->ic.p, curve_b<Fq>(), curve_b<Fq2>());
+        ZK_LAUNCH(k_verify_miller, grid, block, 0, s, df.p, dst.p, dp.p, dx.p, vk->tab.p, vk->ml_ab.p, cnt, vk->kc.k.p);
+        ZK_LAUNCH(k_verify_final, grid, block, 0, s, dv.p, df.p, dst.p, cnt, vk->kc.k.p);
+        ZK_LAUNCH_OK("verification");
+        HIP_TRY(hipMemcpyAsync(verdict + off, dv.p, cnt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+}
+
+}   // namespace
+
+extern "C" {
+
+int zk_pairing(uint8_t *out, const uint8_t *g1, const uint8_t *g2, uint64_t n_pairs, uint32_t group, int32_t device) {
+    return guarded([&] { pairing(out, g1, g2, n_pairs, group, device); });
+}
+
+int zk_vkey_create(zk_vkey **out, const zk_vkey_view *view, int32_t device) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        *out = vkey_create(view, device);
+    });
+}
+
+void zk_vkey_destroy(zk_vkey *vk) {
+    if (!vk) return;
+    int prev = -1;
+    const bool had = hipGetDevice(&prev) == hipSuccess;
+    (void)hipSetDevice(vk->device);
+    delete vk;
+    if (had) (void)hipSetDevice(prev);
+}
+
+int zk_vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict) {
+    return guarded([&] { vkey_verify(vk, proofs, publics, n, verdict); });
+}
+
+}   // extern "C"

@@ -4,7 +4,10 @@
 #pragma once
 #include <cctype>
 #include <cstdio>
+#include <stdexcept>
 #include <string>
+#include <utility>
+#include <vector>
 
 namespace JsonMin {
 
@@ -135,5 +138,126 @@ inline std::string quote(const std::string &v) {
     }
     return o + "\"";
 }
+
+// A parsed document, for the few JSON files the tools READ (verifier: proof.json, public.json, verification_key.json).
+// Numbers keep their text (the values of interest are 254-bit integers, written as strings or as bare numbers); strings
+// are unescaped except \u sequences, which none of these files use in a value that is looked at.
+struct Value {
+    enum Type { Null, Bool, Number, String, Array, Object } type = Null;
+    std::string text;                                  // Number: as written; String: the content; Bool: "true" / "false"
+    std::vector<Value> items;                          // Array
+    std::vector<std::pair<std::string, Value>> members;   // Object, in file order
+    const Value *find(const std::string &key) const {
+        for (const auto &m : members)
+            if (m.first == key) return &m.second;
+        return nullptr;
+    }
+};
+
+class Parser {
+    const std::string &s;
+    size_t p = 0;
+    int depth = 0;
+    [[noreturn]] void fail(const char *what) const { throw std::invalid_argument(std::string("JSON: ") + what + " at byte " + std::to_string(p)); }
+    void ws() { while (p < s.size() && (s[p] == ' ' || s[p] == '\t' || s[p] == '\n' || s[p] == '\r')) p++; }
+    std::string str() {
+        std::string o;
+        p++;                                           // the opening quote
+        for (;;) {
+            if (p >= s.size()) fail("unterminated string");
+            const unsigned char c = (unsigned char)s[p++];
+            if (c == '"') return o;
+            if (c < 0x20) fail("control character in a string");
+            if (c != '\\') {
+                o += (char)c;
+                continue;
+            }
+            if (p >= s.size()) fail("unterminated string");
+            const char e = s[p++];
+            switch (e) {
+                case '"': case '\\': case '/': o += e; break;
+                case 'b': o += '\b'; break;
+                case 'f': o += '\f'; break;
+                case 'n': o += '\n'; break;
+                case 'r': o += '\r'; break;
+                case 't': o += '\t'; break;
+                case 'u':
+                    for (int i = 0; i < 4; i++)
+                        if (p >= s.size() || !isxdigit((unsigned char)s[p++])) fail("bad \\u escape");
+                    o += '?';
+                    break;
+                default: fail("bad escape");
+            }
+        }
+    }
+    Value value() {
+        if (++depth > 512) fail("nesting too deep");
+        ws();
+        Value v;
+        if (p >= s.size()) fail("value expected");
+        const char c = s[p];
+        if (c == '{') {
+            v.type = Value::Object;
+            p++;
+            ws();
+            if (p < s.size() && s[p] == '}') p++;
+            else
+                for (;;) {
+                    ws();
+                    if (p >= s.size() || s[p] != '"') fail("member name expected");
+                    std::string key = str();
+                    ws();
+                    if (p >= s.size() || s[p++] != ':') fail("':' expected");
+                    v.members.emplace_back(std::move(key), value());
+                    ws();
+                    if (p < s.size() && s[p] == ',') { p++; continue; }
+                    if (p < s.size() && s[p] == '}') { p++; break; }
+                    fail("',' or '}' expected");
+                }
+        } else if (c == '[') {
+            v.type = Value::Array;
+            p++;
+            ws();
+            if (p < s.size() && s[p] == ']') p++;
+            else
+                for (;;) {
+                    v.items.push_back(value());
+                    ws();
+                    if (p < s.size() && s[p] == ',') { p++; continue; }
+                    if (p < s.size() && s[p] == ']') { p++; break; }
+                    fail("',' or ']' expected");
+                }
+        } else if (c == '"') {
+            v.type = Value::String;
+            v.text = str();
+        } else if (s.compare(p, 4, "true") == 0) {
+            v.type = Value::Bool; v.text = "true"; p += 4;
+        } else if (s.compare(p, 5, "false") == 0) {
+            v.type = Value::Bool; v.text = "false"; p += 5;
+        } else if (s.compare(p, 4, "null") == 0) {
+            p += 4;
+        } else {
+            const size_t st = p;
+            while (p < s.size() && (isdigit((unsigned char)s[p]) || s[p] == '-' || s[p] == '+' || s[p] == '.' || s[p] == 'e' || s[p] == 'E')) p++;
+            if (p == st || !isValid(s.substr(st, p - st))) { p = st; fail("value expected"); }
+            v.type = Value::Number;
+            v.text = s.substr(st, p - st);
+        }
+        depth--;
+        return v;
+    }
+
+public:
+    explicit Parser(const std::string &text) : s(text) {}
+    Value parse() {
+        Value v = value();
+        ws();
+        if (p != s.size()) fail("text after the document");
+        return v;
+    }
+};
+
+// throws std::invalid_argument("JSON: ... at byte N") for text that is not one JSON document
+inline Value parse(const std::string &text) { return Parser(text).parse(); }
 
 }   // namespace JsonMin

@@ -1,0 +1,258 @@
+// verifier <verification_key.json | circuit.zkey> <public.json> <proof.json>
+//
+// Verifies a Groth16 proof on the GPU (libzkhip zk_vkey_*), the counterpart of snarkjs `groth16 verify` and of the
+// `verifier` the newer rapidsnark ships next to `prover` (the same argument order); the reference of this project has no
+// such program.  The key is snarkjs's verification_key.json (vk_alpha_1, vk_beta_2, vk_gamma_2, vk_delta_2, IC; protocol
+// groth16, curve bn128 / bn254; vk_alphabeta_12 is ignored) or a .zkey, of which only sections 1 to 3 are read.  Points are
+// decimal strings (or bare numbers); a third projective coordinate is honoured: 0 is the point at infinity, anything else
+// divides x and y.  public.json may be `null` (what `prover` writes for a circuit without public signals).
+// Exit codes: 0 "OK: the proof verifies"; 1 "INVALID: ..." on stdout, saying whether the proof is malformed (a point off
+// its curve, outside the subgroup or at infinity, a coordinate not below q, a public signal not below r) or well-formed
+// with a failing pairing equation; 255 with a message on stderr for anything else: usage, an unreadable or ill-formed file,
+// another protocol or curve, a number of public signals that is not the key's, no device (as `wtnscheck`).  All three
+// files are read and checked before the device is touched.  ZKHIP_DEVICE=<n> picks the device.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <sstream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/zkhip.h"
+#include "../csrc/curve.hpp"
+#include "json_min.hpp"
+#include "zkfile.hpp"
+
+namespace {
+
+using JsonMin::Value;
+using zk::Fq;
+using zk::Fq2;
+
+constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
+                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
+constexpr uint8_t kBn254Q[32] = {0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
+                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
+
+std::string slurp(const std::string &path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::invalid_argument(path + ": cannot be opened");
+    std::ostringstream o;
+    o << f.rdbuf();
+    return o.str();
+}
+
+// a decimal integer below 2^256, as a JSON string or a bare number -> 8 little-endian words
+void decimal(const Value &v, const std::string &what, uint32_t w[8]) {
+    const std::invalid_argument bad(what + " is not a decimal integer below 2^256");
+    if ((v.type != Value::String && v.type != Value::Number) || v.text.empty()) throw bad;
+    memset(w, 0, 32);
+    for (const char c : v.text) {
+        if (c < '0' || c > '9') throw bad;
+        uint64_t carry = (uint64_t)(c - '0');
+        for (int i = 0; i < 8; i++) {
+            const uint64_t t = (uint64_t)w[i] * 10u + carry;
+            w[i] = (uint32_t)t;
+            carry = t >> 32;
+        }
+        if (carry) throw bad;
+    }
+}
+bool below_q(const uint32_t w[8]) {
+    for (int i = 7; i >= 0; i--)
+        if (w[i] != zk::FqParams::P[i]) return w[i] < zk::FqParams::P[i];
+    return false;
+}
+// The coordinate as the library takes it: Montgomery form.  One that is not below q is passed as written, so that the
+// device's own check refuses the proof (`reduced` tells the caller that nothing may be computed with it here).
+Fq coord(const Value &v, const std::string &what, bool &reduced) {
+    Fq x;
+    decimal(v, what, x.v);
+    if (!below_q(x.v)) {
+        reduced = false;
+        return x;
+    }
+    return Fq::to_mont(x);
+}
+const Value &item(const Value &v, size_t i, const std::string &what) {
+    if (v.type != Value::Array || v.items.size() <= i) throw std::invalid_argument(what + " is not an array of at least " + std::to_string(i + 1) + " elements");
+    return v.items[i];
+}
+
+void g1_point(const Value &v, const std::string &what, uint8_t out[64]) {
+    bool red = true;
+    Fq x = coord(item(v, 0, what), what + "[0]", red), y = coord(item(v, 1, what), what + "[1]", red);
+    if (v.items.size() > 2) {
+        const Fq z = coord(v.items[2], what + "[2]", red);
+        if (red && z.is_zero()) {
+            memset(out, 0, 64);
+            return;
+        }
+        if (red && z != Fq::one()) {
+            const Fq zi = Fq::inv(z);
+            x = Fq::mul(x, zi);
+            y = Fq::mul(y, zi);
+        }
+    }
+    memcpy(out, x.v, 32);
+    memcpy(out + 32, y.v, 32);
+}
+void g2_point(const Value &v, const std::string &what, uint8_t out[128]) {
+    bool red = true;
+    auto f2 = [&](size_t i) {
+        const std::string w = what + "[" + std::to_string(i) + "]";
+        const Value &c = item(v, i, what);
+        Fq2 r;
+        r.a = coord(item(c, 0, w), w + "[0]", red);
+        r.b = coord(item(c, 1, w), w + "[1]", red);
+        return r;
+    };
+    Fq2 x = f2(0), y = f2(1);
+    if (v.items.size() > 2) {
+        const Fq2 z = f2(2);
+        if (red && z.is_zero()) {
+            memset(out, 0, 128);
+            return;
+        }
+        if (red && z != Fq2::one()) {
+            const Fq2 zi = Fq2::inv(z);
+            x = Fq2::mul(x, zi);
+            y = Fq2::mul(y, zi);
+        }
+    }
+    memcpy(out, x.a.v, 32);
+    memcpy(out + 32, x.b.v, 32);
+    memcpy(out + 64, y.a.v, 32);
+    memcpy(out + 96, y.b.v, 32);
+}
+const Value &member(const Value &o, const char *key, const std::string &file) {
+    const Value *m = o.type == Value::Object ? o.find(key) : nullptr;
+    if (!m) throw std::invalid_argument(file + ": no \"" + key + "\"");
+    return *m;
+}
+
+struct Key {
+    uint8_t alpha1[64], beta2[128], gamma2[128], delta2[128];
+    std::vector<uint8_t> ic;
+};
+
+void key_from_json(const std::string &path, const std::string &text, Key &k) {
+    Value j;
+    try {
+        j = JsonMin::parse(text);
+    } catch (const std::exception &e) {
+        throw std::invalid_argument(path + " is neither a verification_key.json nor a .zkey (" + e.what() + ")");
+    }
+    if (j.type != Value::Object) throw std::invalid_argument(path + " is neither a verification_key.json nor a .zkey");
+    if (const Value *p = j.find("protocol"))
+        if (p->text != "groth16") throw std::invalid_argument(path + ": protocol \"" + p->text + "\" is not groth16");
+    if (const Value *c = j.find("curve"))
+        if (c->text != "bn128" && c->text != "bn254") throw std::invalid_argument(path + ": curve \"" + c->text + "\" is not bn128");
+    g1_point(member(j, "vk_alpha_1", path), "vk_alpha_1", k.alpha1);
+    g2_point(member(j, "vk_beta_2", path), "vk_beta_2", k.beta2);
+    g2_point(member(j, "vk_gamma_2", path), "vk_gamma_2", k.gamma2);
+    g2_point(member(j, "vk_delta_2", path), "vk_delta_2", k.delta2);
+    const Value &ic = member(j, "IC", path);
+    if (ic.type != Value::Array || ic.items.empty()) throw std::invalid_argument(path + ": IC is not a list of points");
+    k.ic.resize(ic.items.size() * 64);
+    for (size_t i = 0; i < ic.items.size(); i++) g1_point(ic.items[i], "IC[" + std::to_string(i) + "]", k.ic.data() + 64 * i);
+}
+
+void key_from_zkey(const std::string &path, Key &k) {
+    auto f = BinFileUtils::openExisting(path, "zkey", 1);
+    auto h = ZKeyUtils::loadHeader(f.get());
+    if (memcmp(h->qPrime.data(), kBn254Q, 32) != 0 || memcmp(h->rPrime.data(), kBn254R, 32) != 0) throw std::invalid_argument("zkey curve not supported");
+    if (f->getSectionSize(3) != (uint64_t(h->nPublic) + 1) * 64)
+        throw std::invalid_argument("zkey section 3 holds " + std::to_string(f->getSectionSize(3)) + " bytes, nPublic = " + std::to_string(h->nPublic) + " implies " +
+                                    std::to_string((uint64_t(h->nPublic) + 1) * 64));
+    memcpy(k.alpha1, h->vk_alpha1, 64);
+    memcpy(k.beta2, h->vk_beta2, 128);
+    memcpy(k.gamma2, h->vk_gamma2, 128);
+    memcpy(k.delta2, h->vk_delta2, 128);
+    const uint8_t *ic = static_cast<const uint8_t *>(f->getSectionData(3));
+    k.ic.assign(ic, ic + f->getSectionSize(3));
+}
+
+Value parse_file(const std::string &path) {
+    try {
+        return JsonMin::parse(slurp(path));
+    } catch (const std::invalid_argument &e) {
+        const std::string m = e.what();
+        throw std::invalid_argument(m.compare(0, 5, "JSON:") == 0 ? path + ": " + m : m);
+    }
+}
+
+int run(const std::string &keyPath, const std::string &publicPath, const std::string &proofPath) {
+    // the three files are read and checked before the device is touched
+    Key key;
+    const std::string keyText = slurp(keyPath);
+    if (keyText.compare(0, 4, "zkey") == 0) key_from_zkey(keyPath, key);
+    else key_from_json(keyPath, keyText, key);
+
+    const Value pub = parse_file(publicPath);
+    if (pub.type != Value::Null && pub.type != Value::Array) throw std::invalid_argument(publicPath + ": a list of public signals (or null) expected");
+    std::vector<uint8_t> publics(pub.items.size() * 32);
+    for (size_t i = 0; i < pub.items.size(); i++) {
+        uint32_t w[8];
+        decimal(pub.items[i], publicPath + ": public signal " + std::to_string(i), w);
+        memcpy(publics.data() + 32 * i, w, 32);
+    }
+    if (key.ic.size() / 64 != pub.items.size() + 1)
+        throw std::invalid_argument("the verification key has " + std::to_string(key.ic.size() / 64) + " IC points for " + std::to_string(pub.items.size()) +
+                                    " public signals (nPublic + 1 expected)");
+
+    const Value pj = parse_file(proofPath);
+    if (pj.type != Value::Object) throw std::invalid_argument(proofPath + ": a proof object expected");
+    if (const Value *p = pj.find("protocol"))
+        if (p->text != "groth16") throw std::invalid_argument(proofPath + ": protocol \"" + p->text + "\" is not groth16");
+    if (const Value *c = pj.find("curve"))
+        if (c->text != "bn128" && c->text != "bn254") throw std::invalid_argument(proofPath + ": curve \"" + c->text + "\" is not bn128");
+    uint8_t proof[256];
+    g1_point(member(pj, "pi_a", proofPath), "pi_a", proof);
+    g2_point(member(pj, "pi_b", proofPath), "pi_b", proof + 64);
+    g1_point(member(pj, "pi_c", proofPath), "pi_c", proof + 192);
+
+    const char *dev = getenv("ZKHIP_DEVICE");
+    zk_vkey_view view;
+    view.vk_alpha1 = key.alpha1;
+    view.vk_beta2 = key.beta2;
+    view.vk_gamma2 = key.gamma2;
+    view.vk_delta2 = key.delta2;
+    view.IC = key.ic.data();
+    view.nPublic = (uint32_t)pub.items.size();
+    zk_vkey *vk = nullptr;
+    if (zk_vkey_create(&vk, &view, dev ? atoi(dev) : -1) != 0) throw std::runtime_error(zk_last_error());
+    uint8_t verdict = ZK_VERIFY_MALFORMED;
+    const int rc = zk_vkey_verify(vk, proof, publics.empty() ? nullptr : publics.data(), 1, &verdict);
+    const std::string err = rc ? zk_last_error() : "";
+    zk_vkey_destroy(vk);
+    if (rc != 0) throw std::runtime_error(err);
+    if (verdict == ZK_VERIFY_OK) {
+        std::cout << "OK: the proof verifies\n";
+        return 0;
+    }
+    if (verdict == ZK_VERIFY_MALFORMED)
+        std::cout << "INVALID: the proof is malformed (a point off its curve, outside the subgroup or at infinity, or a value that is not reduced)\n";
+    else
+        std::cout << "INVALID: the proof is well-formed but the pairing equation does not hold\n";
+    return 1;
+}
+
+}   // namespace
+
+int main(int argc, char **argv) {
+    if (argc != 4) {
+        std::cerr << "Invalid number of parameters:\n";
+        std::cerr << "Usage: verifier <verification_key.json | circuit.zkey> <public.json> <proof.json>\n";
+        return -1;
+    }
+    try {
+        return run(argv[1], argv[2], argv[3]);
+    } catch (std::exception &e) {
+        std::cerr << e.what() << '\n';
+        return -1;
+    }
+}

@@ -100,6 +100,11 @@ class zk_zkey_contrib_out(C.Structure):
     _fields_ = [("vk_delta1", C.c_void_p), ("vk_delta2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
 
 
+class zk_vkey_view(C.Structure):
+    _fields_ = [("vk_alpha1", C.c_void_p), ("vk_beta2", C.c_void_p), ("vk_gamma2", C.c_void_p), ("vk_delta2", C.c_void_p),
+                ("IC", C.c_void_p), ("nPublic", C.c_uint32)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -140,8 +145,10 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_r1cs_create", "zk_r1cs_destroy", "zk_r1cs_check", "zk_r1cs_check_dev", "zk_r1cs_match_zkey",
            "zk_groth16_setup_sizes", "zk_groth16_setup",
            "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare",
-           "zk_g1_scale", "zk_g1_scale_plan", "zk_zkey_contribute_sizes", "zk_zkey_contribute"]
+           "zk_g1_scale", "zk_g1_scale_plan", "zk_zkey_contribute_sizes", "zk_zkey_contribute",
+           "zk_pairing", "zk_vkey_create", "zk_vkey_destroy", "zk_vkey_verify"]
 ZK_SCALE_PLAN_MAX = 130
+ZK_VERIFY_OK, ZK_VERIFY_INVALID, ZK_VERIFY_MALFORMED = 0, 1, 2
 
 
 def load_library():
@@ -236,6 +243,12 @@ def load_library():
         lib.zk_g1_scale_plan.argtypes = [u8p, C.POINTER(C.c_int8), C.POINTER(C.c_int8), C.c_uint32, C.POINTER(C.c_uint32)]
         lib.zk_zkey_contribute_sizes.argtypes = [C.POINTER(zk_zkey_contrib_view), C.POINTER(zk_zkey_contrib_sizes)]
         lib.zk_zkey_contribute.argtypes = [C.POINTER(zk_zkey_contrib_view), u8p, C.c_int32, C.POINTER(zk_zkey_contrib_out)]
+    if hasattr(lib, "zk_pairing"):
+        lib.zk_pairing.argtypes = [u8p, u8p, u8p, C.c_uint64, C.c_uint32, C.c_int32]
+        lib.zk_vkey_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(zk_vkey_view), C.c_int32]
+        lib.zk_vkey_destroy.argtypes = [C.c_void_p]
+        lib.zk_vkey_destroy.restype = None
+        lib.zk_vkey_verify.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p]
     _LIB = lib
     return lib
 
