@@ -19,10 +19,6 @@ extern char **environ;
 
 namespace {
 
-// BN254 scalar field order, little-endian (the reference compares decimal strings, src/fullprover.cpp:31-35)
-const uint8_t kBn254Order[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
-                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
-
 // ZKHIP_FIXED_R / ZKHIP_FIXED_S (64 hex digits, LE): deterministic proofs for parity tests
 bool scalarFromEnv(const char *name, uint8_t out[32]) {
     const char *v = getenv(name);
@@ -96,7 +92,7 @@ FullProver::FullProver(std::string zkeyFileNames[], int size) {
         const std::string circuit = std::filesystem::path(zkeyFileNames[i]).stem().string();   // circuit name = file stem (fullprover.cpp:14-19,25)
         auto zkey = BinFileUtils::openExisting(zkeyFileNames[i], "zkey", 1);
         auto hdr = ZKeyUtils::loadHeader(zkey.get());
-        if (memcmp(hdr->rPrime.data(), kBn254Order, 32) != 0) throw std::invalid_argument("zkey curve not supported");
+        if (!U256::is_bn254_r(hdr->rPrime)) throw std::invalid_argument("zkey curve not supported");
         const uint64_t sizes[6] = {zkey->getSectionSize(4), zkey->getSectionSize(5), zkey->getSectionSize(6),
                                    zkey->getSectionSize(7), zkey->getSectionSize(8), zkey->getSectionSize(9)};
         Circuit &c = circuits[circuit];
@@ -185,7 +181,7 @@ void FullProver::generateWitness(Job &job, const std::string &tag) {
 
 void FullProver::adoptWitness(Job &job, const ZKeyUtils::Header *zh) {
     auto wh = WtnsUtils::loadHeader(job.wtns.get());
-    if (memcmp(wh->prime.data(), kBn254Order, 32) != 0) throw std::invalid_argument("different wtns curve");
+    if (!U256::is_bn254_r(wh->prime)) throw std::invalid_argument("different wtns curve");
     if (wh->nVars != zh->nVars || job.wtns->getSectionSize(2) < (uint64_t)zh->nVars * 32)
         throw std::invalid_argument("witness does not match the zkey (nVars)");
     job.wtnsData = static_cast<const uint8_t *>(job.wtns->getSectionData(2));

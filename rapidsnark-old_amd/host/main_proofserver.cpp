@@ -24,6 +24,7 @@
 #include <string>
 #include <sys/socket.h>
 #include <unistd.h>
+#include <vector>
 
 #include "fullprover.hpp"
 #include "http_front.hpp"
@@ -81,10 +82,8 @@ int main(int argc, char **argv) {
     try {
         std::cerr << "Initializing server...\n";
         int port = std::stoi(argv[1]);
-        std::string *zkeyFileNames = new std::string[argc - 2];
-        for (int i = 0; i < argc - 2; i++) zkeyFileNames[i] = argv[i + 2];
-        FullProver fullProver(zkeyFileNames, argc - 2);
-        delete[] zkeyFileNames;
+        std::vector<std::string> zkeyFileNames(argv + 2, argv + argc);
+        FullProver fullProver(zkeyFileNames.data(), argc - 2);
 
         signal(SIGPIPE, SIG_IGN);
         int ls = ::socket(AF_INET, SOCK_STREAM, 0);

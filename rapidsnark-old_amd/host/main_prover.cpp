@@ -18,18 +18,12 @@
 #include <string>
 #include <unistd.h>
 
+#include "cli.hpp"
 #include "groth16.hpp"
 #include "r1cs_check.hpp"
 #include "zkfile.hpp"
 
 namespace {
-
-// BN254 scalar field order r, little-endian (the reference compares against the decimal
-// string 21888242871839275222246405745257275088548364400416034343698204186575808495617)
-constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
-                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
-
-bool is_bn254_r(const std::array<uint8_t, 32> &p) { return memcmp(p.data(), kBn254R, sizeof kBn254R) == 0; }
 
 struct Scalar32 {
     uint8_t b[32];
@@ -113,11 +107,11 @@ int run(const std::string &zkeyPath, const std::string &wtnsPath, const std::str
     Lap lap;
     auto zkey = BinFileUtils::openExisting(zkeyPath, "zkey", 1);
     auto zh = ZKeyUtils::loadHeader(zkey.get());
-    if (!is_bn254_r(zh->rPrime)) throw std::invalid_argument("zkey curve not supported");
+    if (!U256::is_bn254_r(zh->rPrime)) throw std::invalid_argument("zkey curve not supported");
 
     auto wtns = BinFileUtils::openExisting(wtnsPath, "wtns", 2);
     auto wh = WtnsUtils::loadHeader(wtns.get());
-    if (!is_bn254_r(wh->prime)) throw std::invalid_argument("different wtns curve");
+    if (!U256::is_bn254_r(wh->prime)) throw std::invalid_argument("different wtns curve");
     // the reference indexes the witness blindly (out-of-bounds read on a mismatch, quirk Q8)
     if (wh->nVars != zh->nVars || wtns->getSectionSize(2) < uint64_t(zh->nVars) * 32)
         throw std::invalid_argument("witness does not match the zkey (nVars)");
@@ -166,16 +160,8 @@ int run(const std::string &zkeyPath, const std::string &wtnsPath, const std::str
 }   // namespace
 
 int main(int argc, char **argv) {
-    if (argc != 5) {
-        std::cerr << "Invalid number of parameters:\n";
-        std::cerr << "Usage: prover <circuit.zkey> <witness.wtns> <proof.json> <public.json>\n";
-        return -1;
-    }
-    try {
-        run(argv[1], argv[2], argv[3], argv[4]);
-    } catch (std::exception &e) {
-        std::cerr << e.what() << '\n';
-        return -1;
-    }
+    const int rc = cli_main(argc == 5, "prover <circuit.zkey> <witness.wtns> <proof.json> <public.json>",
+                            [&] { return run(argv[1], argv[2], argv[3], argv[4]); });
+    if (rc != 0) return rc;
     exit(EXIT_SUCCESS);
 }

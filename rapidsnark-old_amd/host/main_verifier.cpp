@@ -23,6 +23,7 @@
 
 #include "../../include/zkhip.h"
 #include "../csrc/curve.hpp"
+#include "cli.hpp"
 #include "json_min.hpp"
 #include "zkfile.hpp"
 
@@ -32,11 +33,6 @@ using JsonMin::Value;
 using zk::Fq;
 using zk::Fq2;
 
-constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
-                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
-constexpr uint8_t kBn254Q[32] = {0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
-                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
-
 std::string slurp(const std::string &path) {
     std::ifstream f(path, std::ios::binary);
     if (!f) throw std::invalid_argument(path + ": cannot be opened");
@@ -45,27 +41,12 @@ std::string slurp(const std::string &path) {
     return o.str();
 }
 
-// a decimal integer below 2^256, as a JSON string or a bare number -> 8 little-endian words
-void decimal(const Value &v, const std::string &what, uint32_t w[8]) {
-    const std::invalid_argument bad(what + " is not a decimal integer below 2^256");
-    if ((v.type != Value::String && v.type != Value::Number) || v.text.empty()) throw bad;
-    memset(w, 0, 32);
-    for (const char c : v.text) {
-        if (c < '0' || c > '9') throw bad;
-        uint64_t carry = (uint64_t)(c - '0');
-        for (int i = 0; i < 8; i++) {
-            const uint64_t t = (uint64_t)w[i] * 10u + carry;
-            w[i] = (uint32_t)t;
-            carry = t >> 32;
-        }
-        if (carry) throw bad;
-    }
+// a decimal integer below 2^256, as a JSON string or a bare number -> 32 little-endian bytes
+void decimal(const Value &v, const std::string &what, void *out) {
+    if ((v.type != Value::String && v.type != Value::Number) || !U256::from_dec(v.text, static_cast<uint8_t *>(out)))
+        throw std::invalid_argument(what + " is not a decimal integer below 2^256");
 }
-bool below_q(const uint32_t w[8]) {
-    for (int i = 7; i >= 0; i--)
-        if (w[i] != zk::FqParams::P[i]) return w[i] < zk::FqParams::P[i];
-    return false;
-}
+bool below_q(const void *le) { return U256::less(static_cast<const uint8_t *>(le), U256::kBn254Q.data()); }
 // The coordinate as the library takes it: Montgomery form.  One that is not below q is passed as written, so that the
 // device's own check refuses the proof (`reduced` tells the caller that nothing may be computed with it here).
 Fq coord(const Value &v, const std::string &what, bool &reduced) {
@@ -164,10 +145,11 @@ void key_from_json(const std::string &path, const std::string &text, Key &k) {
 void key_from_zkey(const std::string &path, Key &k) {
     auto f = BinFileUtils::openExisting(path, "zkey", 1);
     auto h = ZKeyUtils::loadHeader(f.get());
-    if (memcmp(h->qPrime.data(), kBn254Q, 32) != 0 || memcmp(h->rPrime.data(), kBn254R, 32) != 0) throw std::invalid_argument("zkey curve not supported");
-    if (f->getSectionSize(3) != (uint64_t(h->nPublic) + 1) * 64)
+    if (!U256::is_bn254_q(h->qPrime) || !U256::is_bn254_r(h->rPrime)) throw std::invalid_argument("zkey curve not supported");
+    const uint64_t want = ZKeyUtils::Shape{h->nVars, h->nPublic, h->domainSize, h->nCoefs}.sectionBytes(3);
+    if (f->getSectionSize(3) != want)
         throw std::invalid_argument("zkey section 3 holds " + std::to_string(f->getSectionSize(3)) + " bytes, nPublic = " + std::to_string(h->nPublic) + " implies " +
-                                    std::to_string((uint64_t(h->nPublic) + 1) * 64));
+                                    std::to_string(want));
     memcpy(k.alpha1, h->vk_alpha1, 64);
     memcpy(k.beta2, h->vk_beta2, 128);
     memcpy(k.gamma2, h->vk_gamma2, 128);
@@ -195,11 +177,7 @@ int run(const std::string &keyPath, const std::string &publicPath, const std::st
     const Value pub = parse_file(publicPath);
     if (pub.type != Value::Null && pub.type != Value::Array) throw std::invalid_argument(publicPath + ": a list of public signals (or null) expected");
     std::vector<uint8_t> publics(pub.items.size() * 32);
-    for (size_t i = 0; i < pub.items.size(); i++) {
-        uint32_t w[8];
-        decimal(pub.items[i], publicPath + ": public signal " + std::to_string(i), w);
-        memcpy(publics.data() + 32 * i, w, 32);
-    }
+    for (size_t i = 0; i < pub.items.size(); i++) decimal(pub.items[i], publicPath + ": public signal " + std::to_string(i), publics.data() + 32 * i);
     if (key.ic.size() / 64 != pub.items.size() + 1)
         throw std::invalid_argument("the verification key has " + std::to_string(key.ic.size() / 64) + " IC points for " + std::to_string(pub.items.size()) +
                                     " public signals (nPublic + 1 expected)");
@@ -215,7 +193,6 @@ int run(const std::string &keyPath, const std::string &publicPath, const std::st
     g2_point(member(pj, "pi_b", proofPath), "pi_b", proof + 64);
     g1_point(member(pj, "pi_c", proofPath), "pi_c", proof + 192);
 
-    const char *dev = getenv("ZKHIP_DEVICE");
     zk_vkey_view view;
     view.vk_alpha1 = key.alpha1;
     view.vk_beta2 = key.beta2;
@@ -224,7 +201,7 @@ int run(const std::string &keyPath, const std::string &publicPath, const std::st
     view.IC = key.ic.data();
     view.nPublic = (uint32_t)pub.items.size();
     zk_vkey *vk = nullptr;
-    if (zk_vkey_create(&vk, &view, dev ? atoi(dev) : -1) != 0) throw std::runtime_error(zk_last_error());
+    if (zk_vkey_create(&vk, &view, device_from_env()) != 0) throw std::runtime_error(zk_last_error());
     uint8_t verdict = ZK_VERIFY_MALFORMED;
     const int rc = zk_vkey_verify(vk, proof, publics.empty() ? nullptr : publics.data(), 1, &verdict);
     const std::string err = rc ? zk_last_error() : "";
@@ -244,15 +221,6 @@ int run(const std::string &keyPath, const std::string &publicPath, const std::st
 }   // namespace
 
 int main(int argc, char **argv) {
-    if (argc != 4) {
-        std::cerr << "Invalid number of parameters:\n";
-        std::cerr << "Usage: verifier <verification_key.json | circuit.zkey> <public.json> <proof.json>\n";
-        return -1;
-    }
-    try {
-        return run(argv[1], argv[2], argv[3]);
-    } catch (std::exception &e) {
-        std::cerr << e.what() << '\n';
-        return -1;
-    }
+    return cli_main(argc == 4, "verifier <verification_key.json | circuit.zkey> <public.json> <proof.json>",
+                    [&] { return run(argv[1], argv[2], argv[3]); });
 }

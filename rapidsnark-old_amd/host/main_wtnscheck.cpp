@@ -10,13 +10,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "cli.hpp"
 #include "r1cs_check.hpp"
 #include "zkfile.hpp"
 
 namespace {
-
-constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
-                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
 
 int run(const std::string &r1csPath, const std::string &wtnsPath) {
     // both files are read and matched before the device is touched
@@ -24,11 +22,10 @@ int run(const std::string &r1csPath, const std::string &wtnsPath) {
     auto rh = R1csUtils::loadHeader(r1cs.get());
     auto wtns = BinFileUtils::openExisting(wtnsPath, "wtns", 2);
     auto wh = WtnsUtils::loadHeader(wtns.get());
-    if (memcmp(wh->prime.data(), kBn254R, 32) != 0) throw std::invalid_argument("different wtns curve");
+    if (!U256::is_bn254_r(wh->prime)) throw std::invalid_argument("different wtns curve");
     if (wh->nVars != rh->nWires || wtns->getSectionSize(2) < uint64_t(wh->nVars) * 32)
         throw std::invalid_argument("witness does not match the r1cs (nVars " + std::to_string(wh->nVars) + ", nWires " + std::to_string(rh->nWires) + ")");
-    const char *dev = getenv("ZKHIP_DEVICE");
-    R1csCheck::Checker checker(r1csPath, dev ? atoi(dev) : -1);
+    R1csCheck::Checker checker(r1csPath, device_from_env());
     const zk_r1cs_report rep = checker.check(static_cast<const uint8_t *>(wtns->getSectionData(2)), wh->nVars);
     if (R1csCheck::passed(rep)) {
         std::cout << "witness OK: " << rh->nConstraints << " constraints hold\n";
@@ -37,8 +34,8 @@ int run(const std::string &r1csPath, const std::string &wtnsPath) {
     if (!rep.one_ok) std::cout << "w[0] is not 1\n";
     if (rep.first_unreduced != UINT32_MAX) std::cout << "w[" << rep.first_unreduced << "] is not below r\n";
     if (rep.failed) {
-        std::cout << "constraint " << rep.first_failed << " fails: A.w = " << R1csCheck::to_dec(rep.a) << ", B.w = " << R1csCheck::to_dec(rep.b)
-                  << ", C.w = " << R1csCheck::to_dec(rep.c) << "\n";
+        std::cout << "constraint " << rep.first_failed << " fails: A.w = " << U256::to_dec(rep.a) << ", B.w = " << U256::to_dec(rep.b)
+                  << ", C.w = " << U256::to_dec(rep.c) << "\n";
         std::cout << rep.failed << " of " << rh->nConstraints << " constraints fail\n";
     }
     return 1;
@@ -47,15 +44,5 @@ int run(const std::string &r1csPath, const std::string &wtnsPath) {
 }   // namespace
 
 int main(int argc, char **argv) {
-    if (argc != 3) {
-        std::cerr << "Invalid number of parameters:\n";
-        std::cerr << "Usage: wtnscheck <circuit.r1cs> <witness.wtns>\n";
-        return -1;
-    }
-    try {
-        return run(argv[1], argv[2]);
-    } catch (std::exception &e) {
-        std::cerr << e.what() << '\n';
-        return -1;
-    }
+    return cli_main(argc == 3, "wtnscheck <circuit.r1cs> <witness.wtns>", [&] { return run(argv[1], argv[2]); });
 }

@@ -13,7 +13,6 @@
 // or 255 with a message on stderr (as `zkeynew`).  ZKHIP_DEVICE=<n> picks the device.
 // FOR TESTS ONLY: ZKHIP_CONTRIB_SCALAR=<decimal> fixes d (0 < d < r).  A key contributed to with a d that anybody knows is
 // as unsafe as before.
-#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -23,48 +22,27 @@
 #include <vector>
 
 #include <sys/random.h>
-#include <sys/stat.h>
 
 #include "../../include/zkhip.h"
+#include "cli.hpp"
 #include "outfile.hpp"
 #include "vkjson.hpp"
 #include "zkfile.hpp"
 
 namespace {
 
-constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
-                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
-constexpr uint8_t kBn254Q[32] = {0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
-                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
-
 bool is_zero(const uint8_t d[32]) {
     uint8_t any = 0;
     for (int i = 0; i < 32; i++) any |= d[i];
     return !any;
 }
-bool below_r(const uint8_t d[32]) {                       // little-endian bytes
-    for (int i = 31; i >= 0; i--)
-        if (d[i] != kBn254R[i]) return d[i] < kBn254R[i];
-    return false;
-}
+bool below_r(const uint8_t d[32]) { return U256::less(d, U256::kBn254R.data()); }
 
 // the secret: ZKHIP_CONTRIB_SCALAR (tests only) or 32 bytes of getrandom, redrawn until 0 < d < r
 void draw_scalar(uint8_t d[32]) {
     if (const char *e = getenv("ZKHIP_CONTRIB_SCALAR")) {
-        const std::invalid_argument bad("ZKHIP_CONTRIB_SCALAR is not a decimal number d with 0 < d < r");
-        if (!*e) throw bad;
-        memset(d, 0, 32);
-        for (const char *c = e; *c; c++) {
-            if (*c < '0' || *c > '9') throw bad;
-            unsigned carry = (unsigned)(*c - '0');                 // d = 10 d + digit, a byte at a time
-            for (int i = 0; i < 32; i++) {
-                const unsigned t = d[i] * 10u + carry;
-                d[i] = (uint8_t)t;
-                carry = t >> 8;
-            }
-            if (carry) throw bad;
-        }
-        if (is_zero(d) || !below_r(d)) throw bad;
+        if (!U256::from_dec(e, d) || is_zero(d) || !below_r(d))
+            throw std::invalid_argument("ZKHIP_CONTRIB_SCALAR is not a decimal number d with 0 < d < r");
         return;
     }
     do {
@@ -79,31 +57,24 @@ void draw_scalar(uint8_t d[32]) {
 }
 
 int run(const std::string &inPath, const std::string &outPath, const std::string &vkPath) {
-    struct stat a, b;
-    if (stat(inPath.c_str(), &a) == 0 && stat(outPath.c_str(), &b) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino)
-        throw std::invalid_argument("the input and the output are the same file");
+    ContainerOut o(inPath, outPath);
     auto zkey = BinFileUtils::openExisting(inPath, "zkey", 1);
-    char magicVersion[8];                                  // copied as they are
-    if (!std::ifstream(inPath, std::ios::binary).read(magicVersion, 8)) throw std::runtime_error("cannot read " + inPath);
     for (uint32_t id = 1; id <= 10; id++)
         if (!zkey->hasSection(id)) throw std::invalid_argument("zkey has no section " + std::to_string(id));
     auto zh = ZKeyUtils::loadHeader(zkey.get());
-    if (memcmp(zh->qPrime.data(), kBn254Q, 32) != 0 || memcmp(zh->rPrime.data(), kBn254R, 32) != 0)
+    if (!U256::is_bn254_q(zh->qPrime) || !U256::is_bn254_r(zh->rPrime))
         throw std::invalid_argument("zkey curve not supported (q and r are not BN254's)");
     if (zh->nVars < (uint64_t)zh->nPublic + 1) throw std::invalid_argument("zkey header: nPublic + 1 exceeds nVars");
     const uint64_t nv = zh->nVars, np1 = (uint64_t)zh->nPublic + 1, n = zh->domainSize;
     if (zkey->getSectionSize(4) < 4) throw std::invalid_argument("zkey section 4 is short: it has no record count");
     uint32_t nCoefs;
     memcpy(&nCoefs, zkey->getSectionData(4), 4);
-    const struct {
-        uint32_t id;
-        uint64_t want;
-    } implied[] = {{3, np1 * 64}, {4, 4 + (uint64_t)nCoefs * 44}, {5, nv * 64}, {6, nv * 64}, {7, nv * 128}, {8, (nv - np1) * 64}, {9, n * 64}};
-    for (const auto &s : implied) {
-        const uint64_t have = zkey->getSectionSize(s.id);
-        if (have != s.want)
-            throw std::invalid_argument("zkey section " + std::to_string(s.id) + (have < s.want ? " is short: " : " is long: ") + std::to_string(have) +
-                                        " bytes, the header implies " + std::to_string(s.want));
+    const ZKeyUtils::Shape shape{nv, zh->nPublic, n, nCoefs};
+    for (uint32_t id = 3; id <= 9; id++) {
+        const uint64_t have = zkey->getSectionSize(id), want = shape.sectionBytes(id);
+        if (have != want)
+            throw std::invalid_argument("zkey section " + std::to_string(id) + (have < want ? " is short: " : " is long: ") + std::to_string(have) +
+                                        " bytes, the header implies " + std::to_string(want));
     }
 
     struct Secret {
@@ -122,41 +93,21 @@ int run(const std::string &inPath, const std::string &outPath, const std::string
     zk_zkey_contrib_sizes sz{};
     if (zk_zkey_contribute_sizes(&zv, &sz) != 0) throw std::invalid_argument(zk_last_error());
 
-    struct Sec {
-        uint32_t id;
-        const uint8_t *data;
-        uint64_t size;
-    };
-    std::vector<Sec> secs;                                 // sections 1 to 10, in the input's order
-    for (uint32_t id = 1; id <= 10; id++) secs.push_back({id, static_cast<const uint8_t *>(zkey->getSectionData(id)), zkey->getSectionSize(id)});
-    std::sort(secs.begin(), secs.end(), [](const Sec &x, const Sec &y) { return x.data < y.data; });
-    uint64_t total = 12;
-    for (const auto &s : secs) total += 12 + s.size;
-
-    MappedOutFile o(outPath, total);
+    std::vector<ContainerOut::Section> secs;               // sections 1 to 10, in the input's order; 8 and 9 are the library's
+    for (const auto &s : zkey->sectionsInFileOrder(1, 10)) secs.push_back({s.id, s.size, s.id == 8 || s.id == 9 ? nullptr : s.data});
+    const std::vector<uint8_t *> at = o.write(zkey->magicVersion(), secs);
     std::unique_ptr<OutFile> vk;
     if (!vkPath.empty()) vk.reset(new OutFile(vkPath));
-    uint8_t *at = o.data;
-    const uint32_t count = (uint32_t)secs.size();
-    memcpy(at, magicVersion, 8);
-    memcpy(at + 8, &count, 4);
-    at += 12;
     zk_zkey_contrib_out out{};
-    for (const auto &s : secs) {
-        memcpy(at, &s.id, 4);
-        memcpy(at + 4, &s.size, 8);
-        at += 12;
-        if (s.id == 8) out.pointsC = at;
-        else if (s.id == 9) out.pointsH = at;
-        else memcpy(at, s.data, s.size);
-        if (s.id == 2) {                                   // the delta points are the last G1 and the last G2 of the section
-            out.vk_delta1 = at + (static_cast<const uint8_t *>(zh->vk_delta1) - s.data);
-            out.vk_delta2 = at + (static_cast<const uint8_t *>(zh->vk_delta2) - s.data);
+    for (size_t i = 0; i < secs.size(); i++) {
+        if (secs[i].id == 8) out.pointsC = at[i];
+        if (secs[i].id == 9) out.pointsH = at[i];
+        if (secs[i].id == 2) {                             // the delta points are the last G1 and the last G2 of the section
+            out.vk_delta1 = at[i] + (static_cast<const uint8_t *>(zh->vk_delta1) - secs[i].src);
+            out.vk_delta2 = at[i] + (static_cast<const uint8_t *>(zh->vk_delta2) - secs[i].src);
         }
-        at += s.size;
     }
-    const char *dev = getenv("ZKHIP_DEVICE");
-    if (zk_zkey_contribute(&zv, secret.d, dev ? atoi(dev) : -1, &out) != 0) throw std::runtime_error(zk_last_error());
+    if (zk_zkey_contribute(&zv, secret.d, device_from_env(), &out) != 0) throw std::runtime_error(zk_last_error());
     if (vk) {
         const std::string j = verification_key_json(zh->nPublic, static_cast<const uint8_t *>(zh->vk_alpha1), static_cast<const uint8_t *>(zh->vk_beta2),
                                                     static_cast<const uint8_t *>(zh->vk_gamma2), out.vk_delta2,
@@ -172,15 +123,6 @@ int run(const std::string &inPath, const std::string &outPath, const std::string
 }   // namespace
 
 int main(int argc, char **argv) {
-    if (argc != 3 && argc != 4) {
-        std::cerr << "Invalid number of parameters:\n";
-        std::cerr << "Usage: zkeycontribute <in.zkey> <out.zkey> [verification_key.json]\n";
-        return -1;
-    }
-    try {
-        return run(argv[1], argv[2], argc == 4 ? argv[3] : "");
-    } catch (std::exception &e) {
-        std::cerr << e.what() << '\n';
-        return -1;
-    }
+    return cli_main(argc == 3 || argc == 4, "zkeycontribute <in.zkey> <out.zkey> [verification_key.json]",
+                    [&] { return run(argv[1], argv[2], argc == 4 ? argv[3] : ""); });
 }

@@ -16,31 +16,22 @@
 
 #include "../../include/zkhip.h"
 #include "../csrc/common.hpp"
-#include "../csrc/field64.hpp"
+#include "cli.hpp"
 #include "outfile.hpp"
 #include "vkjson.hpp"
 #include "zkfile.hpp"
 
 namespace {
 
-constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
-                                 0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
-
-// Montgomery bytes of a standard-form Fq constant given as little-endian 64-bit limbs
-void fq_mont(uint8_t *out, uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
-    zk::Fq64 x;
-    x.v[0] = a; x.v[1] = b; x.v[2] = c; x.v[3] = d;
-    x = zk::Fq64::to_mont(x);
-    memcpy(out, x.v, 32);
-}
 // the generators of G1, (1, 2), and of G2 (EIP-197), affine Montgomery: gamma2 = delta2 = G2, delta1 = G1
 void generators(uint8_t g1[64], uint8_t g2[128]) {
-    fq_mont(g1, 1, 0, 0, 0);
-    fq_mont(g1 + 32, 2, 0, 0, 0);
-    fq_mont(g2, 0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull);
-    fq_mont(g2 + 32, 0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull);
-    fq_mont(g2 + 64, 0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
-    fq_mont(g2 + 96, 0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
+    auto put = [](uint8_t *out, uint64_t a, uint64_t b, uint64_t c, uint64_t d) { memcpy(out, fq_mont(a, b, c, d).v, 32); };
+    put(g1, 1, 0, 0, 0);
+    put(g1 + 32, 2, 0, 0, 0);
+    put(g2, 0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull);
+    put(g2 + 32, 0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull);
+    put(g2 + 64, 0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull);
+    put(g2 + 96, 0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull);
 }
 
 int run(const std::string &r1csPath, const std::string &ptauPath, const std::string &zkeyPath, const std::string &vkPath) {
@@ -49,7 +40,7 @@ int run(const std::string &r1csPath, const std::string &ptauPath, const std::str
     auto rh = R1csUtils::loadHeader(r1cs.get());
     auto ptau = BinFileUtils::openExisting(ptauPath, "ptau", 1);
     auto ph = PtauUtils::loadHeader(ptau.get());
-    zk_r1cs_view rv{rh->nWires, rh->nPubOut, rh->nPubIn, rh->nPrvIn, rh->nConstraints, rh->constraints, rh->constraintsBytes};
+    zk_r1cs_view rv = rh->view();
     zk_ptau_view pv{};
     pv.power = ph->power;
     pv.alpha1 = ph->alpha1;
@@ -66,11 +57,11 @@ int run(const std::string &r1csPath, const std::string &ptauPath, const std::str
     zk_setup_sizes sz{};
     if (zk_groth16_setup_sizes(&rv, &pv, &sz) != 0) throw std::invalid_argument(zk_last_error());
 
-    const uint64_t nv = sz.nVars, np1 = (uint64_t)sz.nPublic + 1, n = sz.domainSize;
-    std::vector<uint8_t> coefs(4 + 44 * sz.nCoefs), ic(np1 * 64), a(nv * 64), b1(nv * 64), b2(nv * 128), c((nv - np1) * 64), h(n * 64);
+    const ZKeyUtils::Shape shape{sz.nVars, sz.nPublic, sz.domainSize, sz.nCoefs};
+    std::vector<uint8_t> ic(shape.sectionBytes(3)), coefs(shape.sectionBytes(4)), a(shape.sectionBytes(5)), b1(shape.sectionBytes(6)),
+        b2(shape.sectionBytes(7)), c(shape.sectionBytes(8)), h(shape.sectionBytes(9));
     zk_setup_out out{coefs.data(), ic.data(), a.data(), b1.data(), b2.data(), c.empty() ? nullptr : c.data(), h.data()};
-    const char *dev = getenv("ZKHIP_DEVICE");
-    if (zk_groth16_setup(&rv, &pv, dev ? atoi(dev) : -1, &out) != 0) throw std::runtime_error(zk_last_error());
+    if (zk_groth16_setup(&rv, &pv, device_from_env(), &out) != 0) throw std::runtime_error(zk_last_error());
 
     uint8_t g1[64], g2[128];
     generators(g1, g2);
@@ -84,7 +75,7 @@ int run(const std::string &r1csPath, const std::string &ptauPath, const std::str
     z.u32(32);
     z.write(ph->q.data(), 32);
     z.u32(32);
-    z.write(kBn254R, 32);
+    z.write(U256::kBn254R.data(), 32);
     z.u32(sz.nVars);
     z.u32(sz.nPublic);
     z.u32(sz.domainSize);
@@ -121,15 +112,6 @@ int run(const std::string &r1csPath, const std::string &ptauPath, const std::str
 }   // namespace
 
 int main(int argc, char **argv) {
-    if (argc != 4 && argc != 5) {
-        std::cerr << "Invalid number of parameters:\n";
-        std::cerr << "Usage: zkeynew <circuit.r1cs> <pot.ptau> <circuit.zkey> [verification_key.json]\n";
-        return -1;
-    }
-    try {
-        return run(argv[1], argv[2], argv[3], argc == 5 ? argv[4] : "");
-    } catch (std::exception &e) {
-        std::cerr << e.what() << '\n';
-        return -1;
-    }
+    return cli_main(argc == 4 || argc == 5, "zkeynew <circuit.r1cs> <pot.ptau> <circuit.zkey> [verification_key.json]",
+                    [&] { return run(argv[1], argv[2], argv[3], argc == 5 ? argv[4] : ""); });
 }

@@ -12,25 +12,6 @@
 
 namespace R1csCheck {
 
-// canonical base 10 of a 32-byte little-endian integer
-inline std::string to_dec(const uint8_t le[32]) {
-    uint32_t w[8];
-    memcpy(w, le, 32);
-    std::string s;
-    for (;;) {
-        bool zero = true;
-        uint64_t rem = 0;
-        for (int i = 7; i >= 0; i--) {
-            const uint64_t cur = (rem << 32) | w[i];
-            w[i] = (uint32_t)(cur / 10);
-            rem = cur % 10;
-            zero = zero && w[i] == 0;
-        }
-        s.insert(s.begin(), char('0' + rem));
-        if (zero) return s;
-    }
-}
-
 struct Checker {
     zk_r1cs *h = nullptr;
     std::unique_ptr<BinFileUtils::BinFile> file;
@@ -38,8 +19,7 @@ struct Checker {
     Checker(const std::string &path, int32_t device) {
         file = BinFileUtils::openExisting(path, "r1cs", 1);
         header = R1csUtils::loadHeader(file.get());
-        zk_r1cs_view v{header->nWires, header->nPubOut, header->nPubIn, header->nPrvIn, header->nConstraints, header->constraints,
-                       header->constraintsBytes};
+        const zk_r1cs_view v = header->view();
         if (zk_r1cs_create(&h, &v, device) != 0) throw std::runtime_error(zk_last_error());
     }
     ~Checker() { zk_r1cs_destroy(h); }

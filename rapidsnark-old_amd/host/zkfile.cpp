@@ -1,8 +1,8 @@
 #include "zkfile.hpp"
 
-#include "../csrc/field64.hpp"         // libzkhip's host field: the .ptau header's curve-membership check
-#include "../csrc/curve.hpp"
+#include "../csrc/curve.hpp"           // libzkhip's host field: the .ptau header's curve-membership check
 
+#include <algorithm>
 #include <cerrno>
 #include <cstring>
 #include <fcntl.h>
@@ -111,6 +111,14 @@ void *BinFile::read(uint64_t len) { return const_cast<uint8_t *>(take(len)); }
 void *BinFile::getSectionData(uint32_t sectionId, uint32_t sectionPos) { return map_ + extent(sectionId, sectionPos).begin; }
 uint64_t BinFile::getSectionSize(uint32_t sectionId, uint32_t sectionPos) { return extent(sectionId, sectionPos).length; }
 
+std::vector<BinFile::Section> BinFile::sectionsInFileOrder(uint32_t firstId, uint32_t lastId) const {
+    std::vector<Section> secs;
+    for (uint32_t id = firstId; id <= lastId; id++)
+        if (hasSection(id)) secs.push_back({id, map_ + extent(id, 0).begin, extent(id, 0).length});
+    std::sort(secs.begin(), secs.end(), [](const Section &x, const Section &y) { return x.data < y.data; });
+    return secs;
+}
+
 std::unique_ptr<BinFile> openExisting(const std::string &filename, const std::string &type, uint32_t maxVersion) {
     return std::make_unique<BinFile>(filename, type, maxVersion);
 }
@@ -175,13 +183,11 @@ std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f) {
 namespace R1csUtils {
 
 std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f) {
-    static constexpr uint8_t kBn254R[32] = {0x01, 0x00, 0x00, 0xf0, 0x93, 0xf5, 0xe1, 0x43, 0x91, 0x70, 0xb9, 0x79, 0x48, 0xe8, 0x33, 0x28,
-                                            0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
     if (f->hasSection(4) || f->hasSection(5)) throw std::invalid_argument("r1cs custom gates are not supported: Groth16 cannot use them");
     auto h = std::make_unique<Header>();
     f->startReadSection(1);
     h->n8 = read_field_modulus(*f, h->prime, "r1cs");
-    if (memcmp(h->prime.data(), kBn254R, sizeof kBn254R) != 0) throw std::invalid_argument("r1cs curve not supported");
+    if (!U256::is_bn254_r(h->prime)) throw std::invalid_argument("r1cs curve not supported");
     for (uint32_t *dst : {&h->nWires, &h->nPubOut, &h->nPubIn, &h->nPrvIn}) *dst = f->readU32LE();
     h->nLabels = f->readU64LE();
     h->nConstraints = f->readU32LE();
@@ -204,17 +210,7 @@ zk::Fq64 fq_load(const uint8_t *p) {
     memcpy(x.v, p, 32);
     return x;
 }
-// a standard-form constant as little-endian 64-bit limbs -> Montgomery
-zk::Fq64 fq_mont(uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
-    zk::Fq64 x;
-    x.v[0] = a; x.v[1] = b; x.v[2] = c; x.v[3] = d;
-    return zk::Fq64::to_mont(x);
-}
-bool below_q(const uint8_t *p) {
-    uint64_t v[4];
-    memcpy(v, p, 32);
-    return !zk::Fq64::geq_p(v);
-}
+bool below_q(const uint8_t *p) { return U256::less(p, U256::kBn254Q.data()); }
 
 // y^2 = x^3 + b with b = 3 (G1) or 3 / (9 + u) (the G2 twist); the all-zero encoding (infinity) is refused
 template <class F>
@@ -242,12 +238,10 @@ bool g2_ok(const uint8_t *p) {
 }   // namespace
 
 std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f) {
-    static constexpr uint8_t kBn254Q[32] = {0x47, 0xfd, 0x7c, 0xd8, 0x16, 0x8c, 0x20, 0x3c, 0x8d, 0xca, 0x71, 0x68, 0x91, 0x6a, 0x81, 0x97,
-                                            0x5d, 0x58, 0x81, 0x81, 0xb6, 0x45, 0x50, 0xb8, 0x29, 0xa0, 0x31, 0xe1, 0x72, 0x4e, 0x64, 0x30};
     auto h = std::make_unique<Header>();
     f->startReadSection(1);
     h->n8 = read_field_modulus(*f, h->q, "ptau");
-    if (memcmp(h->q.data(), kBn254Q, sizeof kBn254Q) != 0) throw std::invalid_argument("ptau curve not supported (q is not BN254's)");
+    if (!U256::is_bn254_q(h->q)) throw std::invalid_argument("ptau curve not supported (q is not BN254's)");
     h->power = f->readU32LE();
     h->ceremonyPower = f->readU32LE();
     f->endReadSection(false);

@@ -14,10 +14,79 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
+
+#include "../../include/zkhip.h"
+#include "../csrc/field64.hpp"         // libzkhip's host field: BN254's primes are its FrParams::P / FqParams::P
+
+// 256-bit integers as the files hold them, 32 little-endian bytes: BN254's two primes, decimal text, comparison
+namespace U256 {
+
+typedef std::array<uint8_t, 32> Bytes;
+
+constexpr Bytes from_words(const uint32_t (&w)[8]) {
+    Bytes b{};
+    for (int i = 0; i < 32; i++) b[i] = (uint8_t)(w[i / 4] >> (8 * (i % 4)));
+    return b;
+}
+inline constexpr Bytes kBn254R = from_words(zk::FrParams::P), kBn254Q = from_words(zk::FqParams::P);
+inline bool is_bn254_r(const Bytes &p) { return p == kBn254R; }
+inline bool is_bn254_q(const Bytes &p) { return p == kBn254Q; }
+
+inline bool less(const uint8_t a[32], const uint8_t b[32]) {
+    for (int i = 31; i >= 0; i--)
+        if (a[i] != b[i]) return a[i] < b[i];
+    return false;
+}
+// decimal text -> out; false for an empty string, a character that is no digit or a value of 2^256 or more
+inline bool from_dec(const std::string &text, uint8_t out[32]) {
+    if (text.empty()) return false;
+    uint32_t w[8] = {};
+    for (const char c : text) {
+        if (c < '0' || c > '9') return false;
+        uint64_t carry = (uint64_t)(c - '0');               // w = 10 w + digit
+        for (int i = 0; i < 8; i++) {
+            const uint64_t t = (uint64_t)w[i] * 10u + carry;
+            w[i] = (uint32_t)t;
+            carry = t >> 32;
+        }
+        if (carry) return false;
+    }
+    memcpy(out, w, 32);
+    return true;
+}
+// canonical base 10
+inline std::string to_dec(const uint8_t le[32]) {
+    uint32_t w[8];
+    memcpy(w, le, 32);
+    std::string s;
+    for (;;) {
+        bool zero = true;
+        uint64_t rem = 0;
+        for (int i = 7; i >= 0; i--) {
+            const uint64_t cur = (rem << 32) | w[i];
+            w[i] = (uint32_t)(cur / 10);
+            rem = cur % 10;
+            zero = zero && w[i] == 0;
+        }
+        s.insert(s.begin(), char('0' + rem));
+        if (zero) return s;
+    }
+}
+
+}   // namespace U256
+
+// a standard-form Fq constant given as little-endian 64-bit limbs -> Montgomery
+inline zk::Fq64 fq_mont(uint64_t a, uint64_t b, uint64_t c, uint64_t d) {
+    zk::Fq64 x;
+    x.v[0] = a; x.v[1] = b; x.v[2] = c; x.v[3] = d;
+    return zk::Fq64::to_mont(x);
+}
 
 namespace BinFileUtils {
 
@@ -41,6 +110,16 @@ public:
     void *getSectionData(uint32_t sectionId, uint32_t sectionPos = 0);
     uint64_t getSectionSize(uint32_t sectionId, uint32_t sectionPos = 0);
     bool hasSection(uint32_t sectionId) const { return index_.count(sectionId) != 0; }
+
+    // what a program that rewrites the container copies: the magic and version (the file's first 8 bytes), and those of
+    // sections firstId to lastId that the file has, in the file's order
+    const uint8_t *magicVersion() const { return map_; }
+    struct Section {
+        uint32_t id;
+        const uint8_t *data;
+        uint64_t size;
+    };
+    std::vector<Section> sectionsInFileOrder(uint32_t firstId, uint32_t lastId) const;
 
 private:
     struct Extent {
@@ -79,6 +158,22 @@ public:
 };
 std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f);
 
+// the byte size a key's header implies for sections 3 to 9; section 4 is sized from its own leading record count
+struct Shape {
+    uint64_t nVars, nPublic, domainSize, nCoefs;
+    uint64_t sectionBytes(uint32_t id) const {
+        switch (id) {
+        case 3: return (nPublic + 1) * 64;              // IC
+        case 4: return 4 + 44 * nCoefs;
+        case 5: case 6: return nVars * 64;              // A, B1
+        case 7: return nVars * 128;                     // B2
+        case 8: return (nVars - nPublic - 1) * 64;      // C
+        case 9: return domainSize * 64;                 // H
+        }
+        throw std::logic_error("zkey section " + std::to_string(id) + " has no implied size");
+    }
+};
+
 }   // namespace ZKeyUtils
 
 namespace WtnsUtils {
@@ -107,6 +202,7 @@ public:
     uint32_t nConstraints = 0;
     const void *constraints = nullptr;
     uint64_t constraintsBytes = 0;
+    zk_r1cs_view view() const { return zk_r1cs_view{nWires, nPubOut, nPubIn, nPrvIn, nConstraints, constraints, constraintsBytes}; }
 };
 std::unique_ptr<Header> loadHeader(BinFileUtils::BinFile *f);
 

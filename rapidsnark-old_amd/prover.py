@@ -9,7 +9,7 @@ from .binfile import open_existing
 from .zkey import load_zkey_header
 from .wtns import load_wtns_header
 
-BN254_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617   # main_prover.cpp:34
+from .synth import R_MOD as BN254_R   # main_prover.cpp:34
 
 
 def _zkey_view(zkey, keep):

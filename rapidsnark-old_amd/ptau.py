@@ -17,14 +17,13 @@ groth16_setup(r1cs, ptau) makes the phase-2 starting key of snarkjs `groth16 set
 GPU (gamma = delta = 1) as the key dict zkgen.write_zkey / zkgen.verification_key take."""
 import ctypes as C
 import mmap
-import os
 import struct
 
 import numpy as np
 
 from . import lib as L
 from . import synth
-from .binfile import BinFile
+from .binfile import BinFile, rewrite_mapped, write_container
 
 Q_MOD = synth.Q_MOD
 R_MOD = synth.R_MOD
@@ -185,12 +184,7 @@ def write_trapdoor_ptau(power, tau, alpha, beta, path, prepared=True):
             (14, L.fixed_base_g1(g1, a_k(lag13, alpha))),
             (15, L.fixed_base_g1(g1, a_k(lag13, beta))),
         ]
-    with open(path, "wb") as f:
-        f.write(b"ptau" + struct.pack("<II", 1, len(sections)))
-        for sid, payload in sections:
-            payload = payload if isinstance(payload, bytes) else np.ascontiguousarray(payload).tobytes()
-            f.write(struct.pack("<IQ", sid, len(payload)))
-            f.write(payload)
+    write_container(path, b"ptau", 1, sections)
 
 
 # ---------------------------------------------------------------- prepare phase 2
@@ -215,7 +209,6 @@ def prepare_phase2(src, dst, device=-1):
     ValueError for a file that is already prepared) leaves neither file."""
     lib = L.load_library()
     pf, own = _open_ptau(src)
-    tmp = dst + ".partial"
     try:
         if pf.prepared:
             raise ValueError("the ptau file is already prepared for phase 2 (it has sections 12 to 15)")
@@ -223,39 +216,13 @@ def prepare_phase2(src, dst, device=-1):
         z = L.zk_ptau_lagrange_sizes()
         L.check(lib.zk_ptau_prepare_sizes(C.byref(pv), C.byref(z)))
         keep = sorted((pos, size, sid) for sid, (pos, size) in pf.sections.items() if 1 <= sid <= 7)
-        new = [(sid, int(getattr(z, name + "_bytes"))) for sid, name in
-               zip(LAGRANGE, ("lagrange_g1", "lagrange_g2", "lagrange_alpha_g1", "lagrange_beta_g1"))]
-        total = 12 + sum(12 + size for _, size, _ in keep) + sum(12 + size for _, size in new)
-        try:
-            with open(tmp, "wb+") as f:
-                f.truncate(total)
-                m = mmap.mmap(f.fileno(), total)
-            try:
-                o = np.frombuffer(m, dtype=np.uint8)
-                o[:4] = pf.raw[:4]
-                o[4:8] = pf.raw[4:8]
-                o[8:12] = np.frombuffer(struct.pack("<I", len(keep) + len(new)), dtype=np.uint8)
-                at = 12
-                for pos, size, sid in keep:
-                    o[at:at + 12] = np.frombuffer(struct.pack("<IQ", sid, size), dtype=np.uint8)
-                    o[at + 12:at + 12 + size] = pf.raw[pos:pos + size]
-                    at += 12 + size
-                ptrs = []
-                for sid, size in new:
-                    o[at:at + 12] = np.frombuffer(struct.pack("<IQ", sid, size), dtype=np.uint8)
-                    ptrs.append(o[at + 12:at + 12 + size].ctypes.data)
-                    at += 12 + size
-                out = L.zk_ptau_lagrange_out(*ptrs)
-                L.check(lib.zk_ptau_prepare(C.byref(pv), device, C.byref(out)))
-                m.flush()
-            finally:
-                del o
-                m.close()
-            os.replace(tmp, dst)
-        except BaseException:
-            if os.path.exists(tmp):
-                os.remove(tmp)
-            raise
+        secs = [(sid, size, pf.raw[pos:pos + size]) for pos, size, sid in keep]
+        secs += [(sid, int(getattr(z, name + "_bytes")), None) for sid, name in
+                 zip(LAGRANGE, ("lagrange_g1", "lagrange_g2", "lagrange_alpha_g1", "lagrange_beta_g1"))]
+        with rewrite_mapped(dst, pf.raw[:8], secs) as (o, starts):
+            out = L.zk_ptau_lagrange_out(*(o[at:].ctypes.data for at in starts[-4:]))
+            L.check(lib.zk_ptau_prepare(C.byref(pv), device, C.byref(out)))
+            del o
     finally:
         if own:
             pf.close()

@@ -16,9 +16,9 @@ import struct
 import numpy as np
 
 from . import lib as L
-from .binfile import open_existing
+from .binfile import container_parts, open_existing
+from .synth import R_MOD as BN254_R
 
-BN254_R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 TERM_BYTES = 4 + 32
 NONE = 0xFFFFFFFF
 
@@ -154,10 +154,7 @@ def write_r1cs(A, B, C, n_wires, n_pub_out=0, n_pub_in=0, n_prv_in=None, n_label
     sec1 = (struct.pack("<I", 32) + int(prime).to_bytes(32, "little")
             + struct.pack("<IIIIQI", n_wires, n_pub_out, n_pub_in, n_prv_in, n_labels, m))
     sec3 = np.arange(n_wires, dtype="<u8").tobytes()
-    parts = [b"r1cs", struct.pack("<II", 1, 3)]
-    for sid, payload in ((1, sec1), (2, sec2.tobytes()), (3, sec3)):
-        parts += [struct.pack("<IQ", sid, len(payload)), payload]
-    return b"".join(parts)
+    return b"".join(container_parts(b"r1cs", 1, [(1, sec1), (2, sec2), (3, sec3)]))
 
 
 def write_r1cs_rows(A, B, C, n_wires, n_public, **kw):

@@ -4,12 +4,14 @@ snarkjs `groth16 verify`, which the reference leaves to snarkjs.  The arithmetic
 points affine Montgomery, x | y (G2: x.re | x.im | y.re | y.im), all-zero = infinity; public signals 32 bytes little-endian."""
 import ctypes as C
 import json
+import mmap
 import struct
 
 import numpy as np
 
 from . import lib as L
-from .zkey import Q_MOD, R_MOD
+from .binfile import BinFile
+from .zkey import Q_MOD, R_MOD, load_zkey_header
 
 VERIFY_OK, VERIFY_INVALID, VERIFY_MALFORMED = 0, 1, 2
 _MONT = 1 << 256
@@ -127,50 +129,38 @@ class VerificationKey:
     @staticmethod
     def read_zkey(path):
         """(alpha1, beta2, gamma2, delta2, IC) of a .zkey: only the section table and sections 1 to 3 are read"""
-        want = {}
-        with open(path, "rb") as f:
-            if f.read(4) != b"zkey":
+        with open(path, "rb") as fh:
+            if fh.read(4) != b"zkey":
                 raise ValueError("not a zkey file")
-            _version, nsec = struct.unpack("<II", f.read(8))
-            for _ in range(nsec):
-                head = f.read(12)
-                if len(head) != 12:
-                    raise ValueError("zkey file is truncated")
-                sid, size = struct.unpack("<IQ", head)
-                if sid in (1, 2, 3) and sid not in want:
-                    want[sid] = f.read(size)
-                    if len(want[sid]) != size:
-                        raise ValueError("zkey file is truncated")
-                else:
-                    f.seek(size, 1)
-        for sid in (1, 2, 3):
-            if sid not in want:
-                raise ValueError("zkey has no section %d" % sid)
-        if len(want[1]) < 4 or struct.unpack_from("<I", want[1], 0)[0] != 1:
-            raise ValueError("zkey file is not groth16")
-        s2 = want[2]
+            m = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
         try:
-            n8q = struct.unpack_from("<I", s2, 0)[0]
-            q = int.from_bytes(s2[4:4 + n8q], "little")
-            n8r = struct.unpack_from("<I", s2, 4 + n8q)[0]
-            r = int.from_bytes(s2[8 + n8q:8 + n8q + n8r], "little")
-            pos = 8 + n8q + n8r
-            _n_vars, n_public, _domain = struct.unpack_from("<III", s2, pos)
-        except struct.error:
-            raise ValueError("zkey header is short") from None
-        if q != Q_MOD or r != R_MOD:
-            raise ValueError("zkey curve not supported (q and r are not BN254's)")
-        pos += 12
-        if len(s2) < pos + 64 * 3 + 128 * 3:
-            raise ValueError("zkey header is short")
-        alpha1 = s2[pos:pos + 64]
-        pos += 128                                        # beta1 skipped
-        beta2, gamma2 = s2[pos:pos + 128], s2[pos + 128:pos + 256]
-        pos += 256 + 64                                   # delta1 skipped
-        delta2 = s2[pos:pos + 128]
-        if len(want[3]) != (n_public + 1) * 64:
-            raise ValueError("zkey section 3 holds %d bytes, nPublic = %d implies %d" % (len(want[3]), n_public, (n_public + 1) * 64))
-        return alpha1, beta2, gamma2, delta2, want[3]
+            try:
+                f = BinFile(m, "zkey", 1)
+            except struct.error:
+                raise ValueError("zkey file is truncated") from None
+            for sid in (1, 2, 3):
+                if sid not in f.sections:
+                    raise ValueError("zkey has no section %d" % sid)
+                if sum(f.sections[sid][0]) > len(m):
+                    raise ValueError("zkey file is truncated")
+            try:
+                h = load_zkey_header(f)
+            except struct.error:
+                raise ValueError("zkey header is short") from None
+            except IndexError as e:                  # section 2 ends before its six points do, or another section is not as it must be
+                raise ValueError("zkey header is short" if f.pos > sum(f.sections[2][0]) else "zkey header: %s" % e) from None
+            if h.qPrime != Q_MOD or h.rPrime != R_MOD:
+                raise ValueError("zkey curve not supported (q and r are not BN254's)")
+            ic = bytes(f.getSectionData(3))
+            if len(ic) != (h.nPublic + 1) * 64:
+                raise ValueError("zkey section 3 holds %d bytes, nPublic = %d implies %d" % (len(ic), h.nPublic, (h.nPublic + 1) * 64))
+            return h.vk_alpha1, h.vk_beta2, h.vk_gamma2, h.vk_delta2, ic
+        finally:
+            f = None
+            try:
+                m.close()
+            except BufferError:          # an exception's traceback still holds a view: the mapping goes with it
+                pass
 
     @staticmethod
     def read_json(path):

@@ -9,8 +9,7 @@ import struct
 
 import numpy as np
 
-Q_MOD = 21888242871839275222246405745257275088696311157297823662689037894645226208583
-R_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+from .synth import Q_MOD, R_MOD
 
 
 class ZkeyHeader:
@@ -74,7 +73,7 @@ def zkey_contribute(src, dst, d=None, vk_path=None, device=-1):
     Raises ValueError for a file that is not such a key or a d out of range, ZkHipError with the library's message (a point
     off the curve names its section and index)."""
     from . import lib as L
-    from .binfile import BinFile
+    from .binfile import BinFile, rewrite_mapped
     if d is None:
         d = 0
         while not 0 < d < R_MOD:
@@ -87,7 +86,6 @@ def zkey_contribute(src, dst, d=None, vk_path=None, device=-1):
     lib = L.load_library()
     with open(src, "rb") as fh:
         m_in = mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
-    tmp = dst + ".partial"
     raw = np.frombuffer(m_in, dtype=np.uint8)
     try:
         if bytes(raw[:4]) != b"zkey":
@@ -124,23 +122,11 @@ def zkey_contribute(src, dst, d=None, vk_path=None, device=-1):
             setattr(zv, name + "_bytes", sections[sid][1])
         z = L.zk_zkey_contrib_sizes()
         L.check(lib.zk_zkey_contribute_sizes(C.byref(zv), C.byref(z)))
-        order = sorted((sections[sid][0], sections[sid][1], sid) for sid in range(1, 11))
-        total = 12 + sum(12 + size for _, size, _ in order)
+        order = sorted((sections[sid][0], sid) for sid in range(1, 11))
+        secs = [(sid, sections[sid][1], None if sid in (8, 9) else sec(sid)) for _, sid in order]
         try:
-            with open(tmp, "wb+") as fo:
-                fo.truncate(total)
-                m = mmap.mmap(fo.fileno(), total)
-            try:
-                o = np.frombuffer(m, dtype=np.uint8)
-                o[:8] = raw[:8]
-                o[8:12] = np.frombuffer(struct.pack("<I", len(order)), dtype=np.uint8)
-                at, where = 12, {}
-                for pos, size, sid in order:
-                    o[at:at + 12] = np.frombuffer(struct.pack("<IQ", sid, size), dtype=np.uint8)
-                    where[sid] = at + 12
-                    if sid not in (8, 9):
-                        o[at + 12:at + 12 + size] = raw[pos:pos + size]
-                    at += 12 + size
+            with rewrite_mapped(dst, raw[:8], secs) as (o, starts):
+                where = {sid: at for (sid, _, _), at in zip(secs, starts)}
                 out = L.zk_zkey_contrib_out()
                 out.vk_delta1 = o[where[2] + d1_at:].ctypes.data
                 out.vk_delta2 = o[where[2] + d2_at:].ctypes.data
@@ -153,19 +139,13 @@ def zkey_contribute(src, dst, d=None, vk_path=None, device=-1):
                     dd[:] = 0
                 if vk_path is not None:
                     vk = _vk_json(h, bytes(o[where[2] + d2_at:where[2] + d2_at + 128]), bytes(sec(3)))
-                m.flush()
-            finally:
+                    with open(vk_path + ".partial", "w") as fv:
+                        json.dump(vk, fv, indent=1)
+                    os.replace(vk_path + ".partial", vk_path)
                 del o
-                m.close()
-            if vk_path is not None:
-                with open(vk_path + ".partial", "w") as fv:
-                    json.dump(vk, fv, indent=1)
-                os.replace(vk_path + ".partial", vk_path)
-            os.replace(tmp, dst)
         except BaseException:
-            for p in (tmp,) + ((vk_path + ".partial",) if vk_path is not None else ()):
-                if os.path.exists(p):
-                    os.remove(p)
+            if vk_path is not None and os.path.exists(vk_path + ".partial"):
+                os.remove(vk_path + ".partial")
             raise
     finally:
         del raw

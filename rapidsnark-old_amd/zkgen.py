@@ -28,6 +28,8 @@ import numpy as np
 
 from . import lib as L
 from . import synth
+from .binfile import write_container
+from .zkey import ZkeyHeader, _vk_json
 
 R_MOD = synth.R_MOD
 Q_MOD = synth.Q_MOD
@@ -291,33 +293,19 @@ def expected_proof_dlogs(key, r, s):
 
 
 # ---------------------------------------------------------------- files
-def _binfile(magic, version, sections):
-    out = [magic, struct.pack("<II", version, len(sections))]
-    for sid, payload in sections:
-        payload = payload if isinstance(payload, (bytes, bytearray)) else np.ascontiguousarray(payload).tobytes()
-        out.append(struct.pack("<IQ", sid, len(payload)))
-        out.append(payload)
-    return out
-
-
 def write_zkey(key, path):
     b = lambda name: np.ascontiguousarray(key[name]).tobytes()
     sec2 = (struct.pack("<I", 32) + int(Q_MOD).to_bytes(32, "little") + struct.pack("<I", 32) + int(R_MOD).to_bytes(32, "little")
             + struct.pack("<III", key["nVars"], key["nPublic"], key["domainSize"])
             + b("vk_alpha1") + b("vk_beta1") + b("vk_beta2") + b("vk_gamma2") + b("vk_delta1") + b("vk_delta2"))
-    parts = _binfile(b"zkey", 1, [(1, struct.pack("<I", 1)), (2, sec2), (3, key["pointsIC"]), (4, key["coefs"]),
-                                  (5, key["pointsA"]), (6, key["pointsB1"]), (7, key["pointsB2"]), (8, key["pointsC"]),
-                                  (9, key["pointsH"]), (10, bytes(68))])
-    with open(path, "wb") as f:
-        for p in parts:
-            f.write(p)
+    write_container(path, b"zkey", 1, [(1, struct.pack("<I", 1)), (2, sec2), (3, key["pointsIC"]), (4, key["coefs"]),
+                                       (5, key["pointsA"]), (6, key["pointsB1"]), (7, key["pointsB2"]), (8, key["pointsC"]),
+                                       (9, key["pointsH"]), (10, bytes(68))])
 
 
 def write_wtns(key, path):
     sec1 = struct.pack("<I", 32) + int(R_MOD).to_bytes(32, "little") + struct.pack("<I", key["nVars"])
-    with open(path, "wb") as f:
-        for p in _binfile(b"wtns", 2, [(1, sec1), (2, key["witness"])]):
-            f.write(p)
+    write_container(path, b"wtns", 2, [(1, sec1), (2, key["witness"])])
 
 
 def write_r1cs(key, path):
@@ -344,29 +332,14 @@ def write_r1cs(key, path):
         f.write(data)
 
 
-def _fq_std(mont_bytes):
-    """Montgomery Fq coordinates -> list of standard-form ints."""
-    a = np.ascontiguousarray(mont_bytes).reshape(-1)
-    n = a.size // 32
-    one = np.tile(np.frombuffer((1).to_bytes(32, "little"), dtype=np.uint8), n)
-    std = L.fq_mul_vec(a, one)
-    return [int.from_bytes(std[32 * i:32 * i + 32], "little") for i in range(n)]
-
-
 def verification_key(key):
     """snarkjs verification_key.json content (groth16_verify.js reads vk_alpha_1, vk_beta_2, vk_gamma_2,
     vk_delta_2 and IC; vk_alphabeta_12 — a pairing value it does not use for verification — is omitted:
     there is no pairing in this repository)."""
-    g1 = lambda b: [str(v) for v in _fq_std(b)] + ["1"]
-
-    def g2(b):
-        xa, xb, ya, yb = _fq_std(b)
-        return [[str(xa), str(xb)], [str(ya), str(yb)], ["1", "0"]]
-
-    ic = np.ascontiguousarray(key["pointsIC"]).reshape(-1, 64)
-    return {"protocol": "groth16", "curve": "bn128", "nPublic": key["nPublic"],
-            "vk_alpha_1": g1(key["vk_alpha1"]), "vk_beta_2": g2(key["vk_beta2"]), "vk_gamma_2": g2(key["vk_gamma2"]),
-            "vk_delta_2": g2(key["vk_delta2"]), "IC": [g1(row) for row in ic]}
+    b = lambda name: np.ascontiguousarray(key[name]).tobytes()
+    h = ZkeyHeader()
+    h.nPublic, h.vk_alpha1, h.vk_beta2, h.vk_gamma2 = key["nPublic"], b("vk_alpha1"), b("vk_beta2"), b("vk_gamma2")
+    return _vk_json(h, b("vk_delta2"), b("pointsIC"))
 
 
 def write_all(key, outdir):

@@ -170,3 +170,47 @@ def test_zkeynew_arguments_and_file_errors(p2, tmp_path):
         f.write(b"r1cs" + struct.pack("<II", 1, 0))
     res = run_zkeynew(rp, pp, zp)
     assert res.returncode == 255 and not os.path.exists(zp)
+
+
+# ---------------------------------------------------------------- zkeynew: the exact exit code, stdout and stderr
+def exact_case(name, d, ptau):
+    """-> argv of one refusal; the files are written into d, which is the program's directory"""
+    r1cs = circuit(1)
+    head = 12 + 12                                    # section 1 leads the file: n8, the prime, the counts
+    if name == "r1cs_other_prime":
+        r1cs = r1cs[:head + 4] + QM.to_bytes(32, "little") + r1cs[head + 36:]
+    elif name == "r1cs_n8_48":
+        r1cs = r1cs[:head] + struct.pack("<I", 48) + r1cs[head + 4:]
+    elif name == "r1cs_custom_gates":
+        r1cs = r1cs[:8] + struct.pack("<I", 4) + r1cs[12:] + struct.pack("<IQ", 5, 4) + bytes(4)
+    elif name == "r1cs_is_a_ptau":
+        r1cs = ptau
+    elif name == "ptau_version_2":
+        ptau = ptau[:4] + struct.pack("<I", 2) + ptau[8:]
+    elif name == "ptau_cut_in_the_table":
+        ptau = ptau[:30]
+    for fname, data in (("c.r1cs", r1cs), ("p.ptau", ptau)):
+        if name != "ptau_missing" or fname != "p.ptau":
+            with open(os.path.join(d, fname), "wb") as f:
+                f.write(data)
+    return () if name == "usage" else ("c.r1cs", "p.ptau", "c.zkey", "vk.json")
+
+
+EXACT = {      # what the programs of the commit before the host helpers were shared printed: (exit code, stdout, stderr)
+    "usage": (255, "", "Invalid number of parameters:\nUsage: zkeynew <circuit.r1cs> <pot.ptau> <circuit.zkey> [verification_key.json]\n"),
+    "r1cs_other_prime": (255, "", "r1cs curve not supported\n"),
+    "r1cs_n8_48": (255, "", "r1cs: only 256-bit fields are supported\n"),
+    "r1cs_custom_gates": (255, "", "r1cs custom gates are not supported: Groth16 cannot use them\n"),
+    "r1cs_is_a_ptau": (255, "", "Invalid file type. It should be r1cs and it us ptau\n"),
+    "ptau_version_2": (255, "", "Invalid version. It should be <=1 and it us 2\n"),
+    "ptau_cut_in_the_table": (255, "", "Unexpected end of file\n"),
+    "ptau_missing": (255, "", "open: No such file or directory\n"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EXACT))
+def test_zkeynew_exact_refusals_before_the_device(name, tmp_path, p2):
+    argv = exact_case(name, str(tmp_path), p2)
+    res = subprocess.run([ZKEYNEW, *argv], capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    assert (res.returncode, res.stdout, res.stderr) == EXACT[name]
+    assert not [x for x in os.listdir(str(tmp_path)) if x not in ("c.r1cs", "p.ptau")]

@@ -153,3 +153,63 @@ def test_ptauprepare_arguments_and_file_errors(tmp_path):
     assert res.returncode == 255 and "the same file" in res.stderr
     with open(ip, "rb") as f:
         assert f.read() == unprepared
+
+
+# ---------------------------------------------------------------- ptauprepare: the exact exit code, stdout and stderr
+def sections_of(data):
+    (n,) = struct.unpack_from("<I", data, 8)
+    at, out = 12, []
+    for _ in range(n):
+        sid, size = struct.unpack_from("<IQ", data, at)
+        out.append((sid, data[at + 12:at + 12 + size]))
+        at += 12 + size
+    return out
+
+
+def binfile(magic, version, secs):
+    out = [magic, struct.pack("<II", version, len(secs))]
+    for sid, payload in secs:
+        out += [struct.pack("<IQ", sid, len(payload)), payload]
+    return b"".join(out)
+
+
+@pytest.fixture(scope="module")
+def unprepared_sections():
+    return sections_of(ptau_bytes(1, drop=LAG))
+
+
+def exact_case(name, d, secs):
+    """-> argv of one refusal; the file is written into d, which is the program's directory"""
+    patch = lambda sid, f: binfile(b"ptau", 1, [(s, f(p) if s == sid else p) for s, p in secs])
+    data = {"usage": None,
+            "already_prepared": binfile(b"ptau", 1, secs + [(s, bytes(64)) for s in LAG]),     # sections 12 to 15 are not read
+            "no_section_4": binfile(b"ptau", 1, [(s, p) for s, p in secs if s != 4]),
+            "section_6_short": patch(6, lambda p: p[:64]),
+            "beta_g2_off_the_curve": patch(6, lambda p: p[:96] + (5).to_bytes(32, "little")),
+            "beta_g1_at_infinity": patch(5, lambda p: bytes(64) + p[64:]),
+            "version_2": binfile(b"ptau", 2, secs)}.get(name, binfile(b"ptau", 1, secs))
+    if data is not None:
+        with open(os.path.join(d, "in.ptau"), "wb") as f:
+            f.write(data)
+    return {"usage": (), "out_directory_missing": ("in.ptau", "nowhere/out.ptau"), "input_missing": ("other.ptau", "out.ptau")}.get(name, ("in.ptau", "out.ptau"))
+
+
+EXACT = {      # what the programs of the commit before the host helpers were shared printed: (exit code, stdout, stderr)
+    "usage": (255, "", "Invalid number of parameters:\nUsage: ptauprepare <in.ptau> <out.ptau>\n"),
+    "already_prepared": (255, "", "the ptau file is already prepared for phase 2 (it has sections 12 to 15)\n"),
+    "no_section_4": (255, "", "ptau has no section 4\n"),
+    "section_6_short": (255, "", "ptau section 6 is short\n"),
+    "beta_g2_off_the_curve": (255, "", "ptau betaG2 is not a point of the curve\n"),
+    "beta_g1_at_infinity": (255, "", "ptau betaTauG1[0] is not a point of the curve\n"),
+    "version_2": (255, "", "Invalid version. It should be <=1 and it us 2\n"),
+    "out_directory_missing": (255, "", "cannot write nowhere/out.ptau\n"),
+    "input_missing": (255, "", "open: No such file or directory\n"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EXACT))
+def test_ptauprepare_exact_refusals_before_the_device(name, tmp_path, unprepared_sections):
+    argv = exact_case(name, str(tmp_path), unprepared_sections)
+    res = subprocess.run([PTAUPREPARE, *argv], capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    assert (res.returncode, res.stdout, res.stderr) == EXACT[name]
+    assert sorted(os.listdir(str(tmp_path))) == ([] if name == "usage" else ["in.ptau"])

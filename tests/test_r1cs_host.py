@@ -133,3 +133,57 @@ def test_r1cs_object_needs_a_gpu():
     else:
         with pytest.raises(zk.ZkHipError):
             zk.R1cs(multiplier2_bytes())
+
+
+# ---------------------------------------------------------------- wtnscheck: the exact exit code, stdout and stderr
+def exact_case(name, d):
+    """-> argv of one refusal; the files are written into d, which is the program's directory"""
+    r1cs, wtns = multiplier2_bytes(), open(golden_path("multiplier2", "witness.wtns"), "rb").read()
+    head = 12 + 12                                    # section 1 leads both files: n8, the prime, then the counts
+    if name == "r1cs_other_prime":
+        r1cs = r1cs[:head + 4] + (BN254_R + 2).to_bytes(32, "little") + r1cs[head + 36:]
+    elif name == "r1cs_custom_gates":
+        r1cs = r1cs[:8] + struct.pack("<I", 4) + r1cs[12:] + struct.pack("<IQ", 4, 4) + bytes(4)
+    elif name == "r1cs_n8_48":
+        r1cs = r1cs[:head] + struct.pack("<I", 48) + r1cs[head + 4:]
+    elif name == "wtns_other_prime":
+        wtns = wtns[:head + 4] + (BN254_R + 2).to_bytes(32, "little") + wtns[head + 36:]
+    elif name == "wtns_n8_48":
+        wtns = wtns[:head] + struct.pack("<I", 48) + wtns[head + 4:]
+    elif name == "wtns_is_a_zkey":
+        wtns = open(golden_path("multiplier2", "circuit.zkey"), "rb").read()
+    elif name == "wtns_version_3":
+        wtns = wtns[:4] + struct.pack("<I", 3) + wtns[8:]
+    elif name == "wtns_of_another_circuit":
+        wtns = open(golden_path("r1cs_n8", "witness.wtns"), "rb").read()
+    elif name == "wtns_values_cut_short":             # section 2 holds one value less than the header's nVars
+        at = head + 40 + 4
+        size = int.from_bytes(wtns[at:at + 8], "little")
+        wtns = wtns[:at] + (size - 32).to_bytes(8, "little") + wtns[at + 8:-32]
+    for fname, data in (("c.r1cs", r1cs), ("w.wtns", wtns)):
+        if name != "wtns_missing" or fname != "w.wtns":
+            with open(os.path.join(d, fname), "wb") as f:
+                f.write(data)
+    return ("c.r1cs",) if name == "one_argument" else ("c.r1cs", "w.wtns")
+
+
+EXACT = {      # what the programs of the commit before the host helpers were shared printed: (exit code, stdout, stderr)
+    "one_argument": (255, "", "Invalid number of parameters:\nUsage: wtnscheck <circuit.r1cs> <witness.wtns>\n"),
+    "r1cs_other_prime": (255, "", "r1cs curve not supported\n"),
+    "r1cs_custom_gates": (255, "", "r1cs custom gates are not supported: Groth16 cannot use them\n"),
+    "r1cs_n8_48": (255, "", "r1cs: only 256-bit fields are supported\n"),
+    "wtns_other_prime": (255, "", "different wtns curve\n"),
+    "wtns_n8_48": (255, "", "wtns: only 256-bit fields are supported\n"),
+    "wtns_is_a_zkey": (255, "", "Invalid file type. It should be wtns and it us zkey\n"),
+    "wtns_version_3": (255, "", "Invalid version. It should be <=2 and it us 3\n"),
+    "wtns_of_another_circuit": (255, "", "witness does not match the r1cs (nVars 9, nWires 4)\n"),
+    "wtns_values_cut_short": (255, "", "witness does not match the r1cs (nVars 4, nWires 4)\n"),
+    "wtns_missing": (255, "", "open: No such file or directory\n"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EXACT))
+def test_wtnscheck_exact_refusals_before_the_device(name, tmp_path):
+    argv = exact_case(name, str(tmp_path))
+    res = subprocess.run([WTNSCHECK, *argv], capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    assert (res.returncode, res.stdout, res.stderr) == EXACT[name]

@@ -225,3 +225,83 @@ def test_verifier_reaches_the_device_only_with_good_inputs(files):
     """every input check passed: what is left is the device, which this environment hides"""
     r = run(files["vk"], files["public"], files["proof"])
     assert r.returncode == 255 and r.stdout == "" and "device" in r.stderr.lower(), (r.returncode, r.stderr)
+
+
+# ---------------------------------------------------------------- verifier: the exact exit code, stdout and stderr
+def exact_case(name, d):
+    """-> argv of one refusal; the files are written into d, which is the program's directory"""
+    vk, pub, proof = vk_json_of("multiplier2"), golden_json("multiplier2", "public.json"), golden_json("multiplier2", "proof.json")
+    key = "k.json"
+    if name == "coordinate_of_78_digits":
+        proof["pi_a"][1] = "9" * 78
+    elif name == "coordinate_2p256_in_the_key":
+        vk["vk_beta_2"][0][1] = str(1 << 256)
+    elif name == "ic_empty":
+        vk["IC"] = []
+    elif name == "ic_not_a_list":
+        vk["IC"] = "x"
+    elif name == "key_without_alpha":
+        del vk["vk_alpha_1"]
+    elif name == "public_not_a_list":
+        pub = {"a": 1}
+    elif name == "public_empty_string":
+        pub = [""]
+    elif name == "public_2p256":
+        pub = [str(1 << 256)]
+    elif name == "proof_not_an_object":
+        proof = [1]
+    elif name == "proof_point_too_short":
+        proof["pi_a"] = ["1"]
+    elif name == "proof_g2_coordinate_too_short":
+        proof["pi_b"][0] = ["1"]
+    elif name == "proof_curve":
+        proof["curve"] = "bls12381"
+    if name.startswith("zkey_"):
+        key = "k.zkey"
+        data = open(golden_path("multiplier2", "circuit.zkey"), "rb").read()
+        at = 12                                       # sections 1, 2, 3 lead the golden key
+        head = lambda at: int.from_bytes(data[at + 4:at + 12], "little")
+        s2 = at + 12 + head(at)
+        s3 = s2 + 12 + head(s2)
+        if name == "zkey_section_3_disagrees_with_nPublic":
+            end = s3 + 12 + head(s3)
+            data = data[:s3 + 4] + (head(s3) + 64).to_bytes(8, "little") + data[s3 + 12:end] + bytes(64) + data[end:]
+        elif name == "zkey_other_curve":
+            data = data[:s2 + 16] + RM.to_bytes(32, "little") + data[s2 + 48:]
+        with open(os.path.join(d, key), "wb") as f:
+            f.write(data)
+    elif name != "key_missing":
+        with open(os.path.join(d, key), "w") as f:
+            json.dump(vk, f)
+    for fname, j in (("public.json", pub), ("proof.json", proof)):
+        with open(os.path.join(d, fname), "w") as f:
+            json.dump(j, f)
+    return () if name == "usage" else (key, "public.json", "proof.json")
+
+
+EXACT = {      # what the programs of the commit before the host helpers were shared printed: (exit code, stdout, stderr)
+    "usage": (255, "", "Invalid number of parameters:\nUsage: verifier <verification_key.json | circuit.zkey> <public.json> <proof.json>\n"),
+    "coordinate_of_78_digits": (255, "", "pi_a[1] is not a decimal integer below 2^256\n"),
+    "coordinate_2p256_in_the_key": (255, "", "vk_beta_2[0][1] is not a decimal integer below 2^256\n"),
+    "ic_empty": (255, "", "k.json: IC is not a list of points\n"),
+    "ic_not_a_list": (255, "", "k.json: IC is not a list of points\n"),
+    "key_without_alpha": (255, "", 'k.json: no "vk_alpha_1"\n'),
+    "public_not_a_list": (255, "", "public.json: a list of public signals (or null) expected\n"),
+    "public_empty_string": (255, "", "public.json: public signal 0 is not a decimal integer below 2^256\n"),
+    "public_2p256": (255, "", "public.json: public signal 0 is not a decimal integer below 2^256\n"),
+    "proof_not_an_object": (255, "", "proof.json: a proof object expected\n"),
+    "proof_point_too_short": (255, "", "pi_a is not an array of at least 2 elements\n"),
+    "proof_g2_coordinate_too_short": (255, "", "pi_b[0] is not an array of at least 2 elements\n"),
+    "proof_curve": (255, "", 'proof.json: curve "bls12381" is not bn128\n'),
+    "zkey_section_3_disagrees_with_nPublic": (255, "", "zkey section 3 holds 192 bytes, nPublic = 1 implies 128\n"),
+    "zkey_other_curve": (255, "", "zkey curve not supported\n"),
+    "key_missing": (255, "", "k.json: cannot be opened\n"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EXACT))
+def test_verifier_exact_refusals_before_the_device(name, tmp_path):
+    argv = exact_case(name, str(tmp_path))
+    res = subprocess.run([VERIFIER, *argv], capture_output=True, text=True, timeout=60, cwd=str(tmp_path),
+                         env=dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES=""))
+    assert (res.returncode, res.stdout, res.stderr) == EXACT[name]

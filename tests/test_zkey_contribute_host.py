@@ -205,3 +205,55 @@ def test_python_zkey_contribute_refuses_before_the_device(tmp_path):
     with pytest.raises(ValueError, match="not a zkey file"):
         zkey_contribute(short, op, d=5)
     assert sorted(os.listdir(str(tmp_path))) == ["in.zkey", "short.zkey"]
+
+
+# ---------------------------------------------------------------- zkeycontribute: the exact exit code, stdout and stderr
+def exact_case(name, d):
+    """-> (argv, ZKHIP_CONTRIB_SCALAR) of one refusal; the files are written into d, which is the program's directory"""
+    secs = sections_of(golden_bytes("r1cs_n8", "circuit.zkey"))
+    patch = lambda sid, f: binfile(b"zkey", 1, [(s, f(p) if s == sid else p) for s, p in secs])
+    without = lambda sid: binfile(b"zkey", 1, [(s, p) for s, p in secs if s != sid])
+    data = {"usage": None,
+            "nPublic_exceeds_nVars": patch(2, lambda p: p[:76] + p[72:76] + p[80:]),        # nPublic := nVars
+            "section_4_without_count": patch(4, lambda p: p[:2]),
+            "section_3_long": patch(3, lambda p: p + bytes(64)),
+            "section_6_short": patch(6, lambda p: p[:-64]),
+            "section_7_long": patch(7, lambda p: p + bytes(128)),
+            "no_section_1": without(1),
+            "no_section_4": without(4)}.get(name, binfile(b"zkey", 1, secs))
+    if data is not None:
+        with open(os.path.join(d, "in.zkey"), "wb") as f:
+            f.write(data)
+    argv = {"usage": (), "out_directory_missing": ("in.zkey", "nowhere/out.zkey"),
+            "vk_directory_missing": ("in.zkey", "out.zkey", "nowhere/vk.json")}.get(name, ("in.zkey", "out.zkey"))
+    scalar = {"scalar_2p256": str(1 << 256), "scalar_r": str(RM), "scalar_zero": "0", "scalar_empty": "", "scalar_leading_space": " 5"}.get(name, "12345")
+    return argv, scalar
+
+
+BAD_SCALAR = "ZKHIP_CONTRIB_SCALAR is not a decimal number d with 0 < d < r\n"
+EXACT = {      # what the programs of the commit before the host helpers were shared printed: (exit code, stdout, stderr)
+    "usage": (255, "", "Invalid number of parameters:\nUsage: zkeycontribute <in.zkey> <out.zkey> [verification_key.json]\n"),
+    "nPublic_exceeds_nVars": (255, "", "zkey header: nPublic + 1 exceeds nVars\n"),
+    "section_4_without_count": (255, "", "zkey section 4 is short: it has no record count\n"),
+    "section_3_long": (255, "", "zkey section 3 is long: 192 bytes, the header implies 128\n"),
+    "section_6_short": (255, "", "zkey section 6 is short: 512 bytes, the header implies 576\n"),
+    "section_7_long": (255, "", "zkey section 7 is long: 1280 bytes, the header implies 1152\n"),
+    "no_section_1": (255, "", "zkey has no section 1\n"),
+    "no_section_4": (255, "", "zkey has no section 4\n"),
+    "out_directory_missing": (255, "", "cannot write nowhere/out.zkey\n"),
+    "vk_directory_missing": (255, "", "cannot write nowhere/vk.json\n"),
+    "scalar_2p256": (255, "", BAD_SCALAR),
+    "scalar_r": (255, "", BAD_SCALAR),
+    "scalar_zero": (255, "", BAD_SCALAR),
+    "scalar_empty": (255, "", BAD_SCALAR),
+    "scalar_leading_space": (255, "", BAD_SCALAR),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EXACT))
+def test_zkeycontribute_exact_refusals_before_the_device(name, tmp_path):
+    argv, scalar = exact_case(name, str(tmp_path))
+    res = subprocess.run([ZKEYCONTRIBUTE, *argv], capture_output=True, text=True, timeout=120, cwd=str(tmp_path),
+                         env=dict(os.environ, ZKHIP_CONTRIB_SCALAR=scalar))
+    assert (res.returncode, res.stdout, res.stderr) == EXACT[name]
+    assert sorted(os.listdir(str(tmp_path))) == ([] if name == "usage" else ["in.zkey"])

@@ -7,17 +7,8 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import rapidsnark_old_amd as zk
 from rapidsnark_old_amd import synth
-
-R_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-Q_MOD = 21888242871839275222246405745257275088696311157297823662689037894645226208583
-
-
-def binfile(path, magic, version, sections):
-    with open(path, "wb") as f:
-        f.write(magic + struct.pack("<II", version, len(sections)))
-        for typ, data in sections:
-            f.write(struct.pack("<IQ", typ, len(data)))
-            f.write(data)
+from rapidsnark_old_amd.binfile import write_container as binfile      # noqa: F401  (tools/cli_exit_ab.py and tests import it from here)
+from rapidsnark_old_amd.synth import R_MOD, Q_MOD
 
 
 def main():

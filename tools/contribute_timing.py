@@ -32,9 +32,9 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+from oracle.bn254 import R_MOD, Q_MOD  # noqa: E402
+
 BIN = os.path.join(ROOT, "rapidsnark-old_amd")
-R_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
-Q_MOD = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 K = 0x2B3C4D5E6F708192A3B4C5D6E7F8091A2B3C4D5E6F708192A3B4C5D6E7F80919 % R_MOD
 
 

@@ -26,8 +26,9 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+from oracle.bn254 import R_MOD as RM  # noqa: E402
+
 BIN = os.path.join(ROOT, "rapidsnark-old_amd")
-RM = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
 
 def run_zkeynew(r1cs, ptau, zkey, prof_dir=None):

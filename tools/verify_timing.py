@@ -29,7 +29,8 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-R_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+from oracle.bn254 import R_MOD  # noqa: E402
+
 KERNELS = ["k_verify_check", "k_verify_miller", "k_verify_final", "k_pair_check", "k_miller_groups", "k_final_exp"]
 
 
