@@ -1,6 +1,6 @@
 // Device-side moves of field elements and points between HBM and registers, and the per-lane double-and-add over
-// them: the one definition every kernel file uses (msm.hip, ntt.hip, nttpair.hip, fieldops.hip, synth.hip, r1cs.hip,
-// setup.hip, ptau_prepare.hip).  The plain 8 x 32-bit forms of field.hpp / curve.hpp only: msm.hip's Reg<>-converting
+// them: the one definition every kernel file uses (msm_*.hip, ntt.hip, nttpair.hip, fieldops.hip, synth.hip, r1cs.hip,
+// setup.hip, ptau_prepare.hip).  The plain 8 x 32-bit forms of field.hpp / curve.hpp only: msm_lanes.hpp's Reg<>-converting
 // load_affine / load_xyzz / store_xyzz*, its load_row_el and the twiddle loaders of ntt.hip / nttpair.hip stay with
 // their kernels.
 #pragma once

@@ -30,7 +30,7 @@ typedef XYZZ<Fq2h> G2P;
 static_assert(sizeof(G1A) == 64 && sizeof(G2A) == 128 && sizeof(G1P) == 128 && sizeof(G2P) == 256, "layout");
 
 // One bucket set's sum from its rc records: rc = 1: the sum itself; rc = c: T, S_0 .. S_{c-2} of the bit-sum
-// reduction (msm.hip): sum_k (k+1) B_k = T + sum_j 2^j S_j — a serial chain of c-1 doublings, microseconds here.
+// reduction (msm_reduce.hip): sum_k (k+1) B_k = T + sum_j 2^j S_j — a serial chain of c-1 doublings, microseconds here.
 template <class PT>
 static PT set_sum(const uint8_t *w, uint32_t rc) {
     PT acc = PT::inf(), s;

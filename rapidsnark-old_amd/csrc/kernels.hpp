@@ -1,4 +1,4 @@
-// Launchers of the gfx950 kernels (defined in ntt.hip, msm.hip, fieldops.hip).
+// Launchers of the gfx950 kernels (defined in ntt.hip, msm_*.hip, fieldops.hip).
 // All pointers are device pointers; all launches are asynchronous on `stream`.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,7 +29,7 @@ void launch_spmv_abc(Fr *a, Fr *b, Fr *c, CsrDev csr, const Fr *wtns, uint32_t n
 // hold 2 * (row_hi - row_lo) rows); the range check covers every record.
 void launch_csr_build(uint32_t *rowptr, uint32_t *col, Fr *val, uint32_t *cursor, uint32_t *err, const uint8_t *records,
                       uint64_t nCoefs, uint32_t n, uint32_t nVars, uint32_t row_lo, uint32_t row_hi, hipStream_t s);
-// exclusive scan: out[i] = sum counts[0..i), out[total] = grand total; out holds total + 1 + msm_scan_extra_words(total) words
+// exclusive scan (msm_sort.hip): out[i] = sum counts[0..i), out[total] = grand total; out holds total + 1 + msm_scan_extra_words(total) words
 void launch_exclusive_scan_u32(uint32_t *out, const uint32_t *counts, uint32_t total, hipStream_t s);
 
 // ---------------------------------------------------------------- ntt.hip
@@ -108,7 +108,7 @@ void launch_bitrev_permute(Fr *data, uint32_t logn, hipStream_t s);
 // h[i] = fromMontgomery(a[i]*b[i] - c[i])  (src/groth16.cpp:158-163)
 void launch_abc_to_h(Fr *h, const Fr *a, const Fr *b, const Fr *c, uint64_t n, hipStream_t s, uint32_t vectors = 1, uint64_t abc_stride = 0);
 
-// ---------------------------------------------------------------- msm.hip
+// ---------------------------------------------------------------- msm_sort.hip (plan, digits, sort, scan)
 struct MsmPlan {
     uint32_t c;          // window bits
     uint32_t W;          // digit windows = ceil(256 / c)
@@ -140,12 +140,14 @@ struct MsmSortBufs {
 MsmSortSizes msm_sort_sizes(uint64_t n, MsmPlan p);
 uint32_t msm_scan_extra_words(uint32_t total);
 void launch_msm_sort(const MsmSortBufs &b, const Fr *scalars, uint64_t n, MsmPlan p, hipStream_t s);
+// ---------------------------------------------------------------- msm_tables.hip
 // table: W*n affine points, rows [0, n) already hold P_i (internal form); fills rows [n, W*n).
 // tmp: (W-1)*n XYZZ, pref: (W-1)*n field elements (scratch).
 void launch_msm_precomp_g1(G1Affine *table, G1XYZZ *tmp, Fq *pref, uint64_t n, MsmPlan p, hipStream_t s);
 void launch_msm_precomp_g2(G2Affine *table, G2XYZZ *tmp, Fq2 *pref, uint64_t n, MsmPlan p, hipStream_t s);
+// ---------------------------------------------------------------- msm_accum.hip
 // Bucket sums, partial sums and reduction scratch in HBM: the accumulators' own nine 29-bit limbs per
-// coordinate (lazy, not canonical — msm.hip), all-zero = infinity.  G1: x | y | zz | zzz; G2: the four
+// coordinate (lazy, not canonical — msm_lanes.hpp), all-zero = infinity.  G1: x | y | zz | zzz; G2: the four
 // real components, then the four imaginary ones (what a lane of a lane pair loads in one go).
 struct alignas(16) G1Acc {
     int32_t l[36];
@@ -186,6 +188,7 @@ void launch_msm_accum_g2(G2Acc *buckets, const uint32_t *offsets, const uint32_t
                          uint32_t idx_min, uint32_t idx_sub, uint32_t total_buckets, uint64_t max_entries,
                          G2Acc *ws_part, uint32_t *ws_key, uint32_t *ws_flag, hipStream_t s, hipEvent_t *ev = nullptr,
                          AccumTail tail = AccumTail());
+// ---------------------------------------------------------------- msm_reduce.hip
 // window_sums[m*W + w] = sum_k (k+1) * buckets[m][w][k]  for n_msm bucket arrays laid back to back;
 // scratch: n_msm * W * nbuckets/REDUCE_CHUNK points
 void launch_msm_reduce_g1(G1XYZZ *window_sums, G1Acc *scratch, const G1Acc *buckets, uint32_t n_msm, MsmPlan p, hipStream_t s);
@@ -195,6 +198,7 @@ uint64_t msm_reduce_scratch_points(uint32_t n_msm, MsmPlan p);
 // set sum = T + sum_j 2^j S_j, finished on the host); layout [msm][set][record]
 uint32_t msm_wsum_rc(MsmPlan p);
 
+// ---------------------------------------------------------------- msm_tables.hip
 // MSM tables live in HBM as canonical words of x*2^261 (the 29-bit-limb kernels' Montgomery radix);
 // converts n coordinates in place from the zkey's x*2^256.
 void launch_fq_to_internal(Fq *coords, uint64_t n, hipStream_t s);

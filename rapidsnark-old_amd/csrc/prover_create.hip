@@ -282,7 +282,7 @@ void prover_create(zk_prover **out, const zk_zkey_view *z, const zk_opts *o) {
     p->table_mode = (p->flags & ZK_FLAG_PRECOMP_HALF) ? 2u : p->precomp ? 1u : 0u;
     p->sort_h.alloc(nh, wbits, p->table_mode, p->batch);
     alloc_slot(p.get(), 0);
-    // with window pre-computation a table holds W rows: row j = 2^(c*j) * P (msm.hip) — or, with ZK_FLAG_PRECOMP_HALF, the
+    // with window pre-computation a table holds W rows: row j = 2^(c*j) * P (msm_tables.hip) — or, with ZK_FLAG_PRECOMP_HALF, the
     // ceil(W/2) rows of the even windows
     const uint64_t rows_w = msm_table_rows(p->slot[0].sort_w.plan), rows_h = msm_table_rows(p->sort_h.plan);
     p->ptsA.alloc((nv ? nv : 1) * rows_w);

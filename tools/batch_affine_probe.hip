@@ -15,8 +15,11 @@
 // The operands of a batch are derived from two resident points by adding small constants to a limb (one instruction per
 // coordinate): a real kernel would have to hold 4 x 9 limbs per pair across the inversion (288 VGPRs at B = 8) or gather
 // every point twice — this probe leaves that out on purpose: it is the optimistic bound.
-#include "../rapidsnark-old_amd/csrc/msm.hip"
+#include "../rapidsnark-old_amd/csrc/field29.hpp"
+#include "../rapidsnark-old_amd/csrc/curve29.hpp"
+#include "../rapidsnark-old_amd/csrc/msm_lanes.hpp"
 #include <stdio.h>
+#include <vector>
 using namespace zk;
 
 typedef Fq29 FR;

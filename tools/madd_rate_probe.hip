@@ -2,8 +2,11 @@
 // bucket logic, operands in registers?  (tools/, not product code.)  Prints cycles per wave-level addition per SIMD at
 // 1..4 waves per SIMD, next to the 2318-instruction count and the cost-model figure of DESIGN.md section 6.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I rapidsnark-old_amd/csrc tools/madd_rate_probe.hip -o tools/madd_rate_probe
-#include "../rapidsnark-old_amd/csrc/msm.hip"
+#include "../rapidsnark-old_amd/csrc/field29.hpp"
+#include "../rapidsnark-old_amd/csrc/curve29.hpp"
+#include "../rapidsnark-old_amd/csrc/msm_lanes.hpp"
 #include <stdio.h>
+#include <vector>
 using namespace zk;
 
 template <int MAXW>

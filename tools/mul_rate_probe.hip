@@ -3,8 +3,11 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I rapidsnark-old_amd/csrc tools/mul_rate_probe.hip -o tools/mul_rate_probe     (default build)
 //   ... -DZK_STMT_MAD -o tools/mul_rate_probe_stmt            (one asm statement per MAD)
 //   ... -DZK_COMPILER_MAD -o tools/mul_rate_probe_c           (C column sums: what hipcc makes of them)
-#include "../rapidsnark-old_amd/csrc/msm.hip"
+#include "../rapidsnark-old_amd/csrc/field29.hpp"
+#include "../rapidsnark-old_amd/csrc/curve29.hpp"
+#include "../rapidsnark-old_amd/csrc/msm_lanes.hpp"
 #include <stdio.h>
+#include <vector>
 using namespace zk;
 
 // ---- Fq2 product in ONE lane, three ways (round 5: is a three-product Fq2 multiplication worth it on this arithmetic?)
