@@ -491,6 +491,60 @@ void zk_vkey_destroy(zk_vkey *vk);
 #define ZK_VERIFY_MALFORMED 2
 int zk_vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict);
 
+/* ---- Powers of Tau: check (is the .ptau a sequence of powers of one tau, are its Lagrange sections its own) ---- */
+/* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
+ * counterpart is the arithmetic half of snarkjs `powersoftau verify`.  The contribution transcript (section 7) is not read.
+ * Points are in the .ptau encoding (affine Montgomery, all-zero = infinity); scalars are 32 bytes LE in standard form and
+ * must be below r.  Points go through the device in chunks of ZKHIP_PTAU_CHUNK points (2^22 otherwise), so n is not
+ * bound by the HBM.  device -1: the current one.
+ * out[i] = 1 if G2 point i is in the order-r subgroup of the twist (infinity: 1), 0 if it is on the twist but outside.  A
+ * point off the twist or with a coordinate not below q is an error naming the lowest such index.  The test is
+ * [x+1] Q + psi([x] Q) + psi^2([x] Q) = psi^3([2x] Q) (x = 4965661367192848881, psi the twist's Frobenius map), exact
+ * for BN254; ZKHIP_SUBGROUP_PLAIN=1 computes the same bytes by [r] Q (the yardstick of the timing tool). */
+int zk_g2_in_subgroup(uint8_t *out, const uint8_t *points, uint64_t n, int32_t device);
+/* out = sum_(i<n) s^(first_exp + i) points[i], affine.  The scalars are made on the device, chunk by chunk.  Every point is
+ * checked as zk_g1_lagrange checks it (an error naming the lowest index); infinity is legal; n = 0 gives infinity. */
+int zk_g1_power_msm(uint8_t out[64], const uint8_t *points, uint64_t n, const uint8_t s[32], uint64_t first_exp, int32_t device);
+int zk_g2_power_msm(uint8_t out[128], const uint8_t *points, uint64_t n, const uint8_t s[32], uint64_t first_exp, int32_t device);
+/* out[j] = sum_(i < 2^log_n) s^i w^(ij), j < 2^log_n: the forward DFT of the powers of s, 32 bytes LE standard form, w
+ * the 2^log_n-th root of unity of zk_fr_ntt, log_n <= 28.  Exact for every s < r (0, 1 and s w^j = 1 included). */
+int zk_fr_power_dft(uint8_t *out, const uint8_t s[32], uint32_t log_n, int32_t device);
+/* The whole file.  sec[k] / sec_bytes[k]: section k of the mapped file (k = 2 .. 6 and 12 .. 15; NULL = absent). */
+typedef struct zk_ptau_file_view {
+    uint32_t power;
+    const void *sec[16];
+    uint64_t sec_bytes[16];
+} zk_ptau_file_view;              /* indices 2..6, 12..15 used; NULL = absent */
+typedef struct zk_ptau_check_sizes_t {
+    uint32_t prepared;            /* 1: sections 12 to 15 are there and will be checked */
+    uint64_t chunk_points;        /* points per chunk in effect */
+    uint64_t device_bytes;        /* an upper estimate of the HBM the check holds */
+} zk_ptau_check_sizes_t;
+typedef struct zk_ptau_report {
+    uint32_t verdict;             /* 0 OK, 1 INVALID, 2 MALFORMED */
+    uint32_t failed;              /* bit k set: the equation of section k (2,3,4,5,6) failed; bit 0: a generator */
+    uint32_t lagrange_failed[4];  /* sections 12..15: bit p set = level p failed */
+    uint32_t bad_section;
+    uint32_t bad_kind;            /* 1 coordinate >= q, 2 off curve, 3 not in subgroup, 4 infinity */
+    uint64_t bad_index;
+} zk_ptau_report;
+/* Checks the view without touching a device: power 1 .. 28 (1 .. 27 for a prepared file: level power + 1 of section 12
+ * needs a 2^(power+1)-th root of unity), a missing section, "ptau section N is short: ... bytes, power P needs ...", and
+ * a file with some but not all of sections 12 to 15. */
+int zk_ptau_check_sizes(const zk_ptau_file_view *ptau, zk_ptau_check_sizes_t *sizes);
+/* The check.  s32: the scalar of the random combination (2 <= s < r), NULL: drawn from getrandom() after the view is
+ * given, which is what makes the check sound; a fixed one is for tests.  OK exactly when
+ *   every coordinate is below q, every point on its curve, no point of sections 2 to 6 at infinity, every G2 point of
+ *   sections 3, 6 and 13 in the subgroup (else MALFORMED, naming section, kind and the lowest index of the first such
+ *   section in the order 2, 3, 4, 5, 6, 12, 13, 14, 15; no equation is evaluated then);
+ *   tauG1[0] = G1 and tauG2[0] = G2 (bit 0 of `failed`);
+ *   each of sections 2, 4, 5 is a sequence of powers of the tau of tauG2[1], section 3 of the tau of tauG1[1], and section
+ *   6 holds the beta of betaTauG1[0] (bits 2 .. 6 of `failed`; probability of a wrong pass below 2^29 / r);
+ *   every level of sections 12 to 15, when they are there, is the Lagrange form of its powers (lagrange_failed).
+ * Every failing equation is reported, not the first.  Free HBM is checked before anything is allocated.  The return
+ * value tells only whether the call ran. */
+int zk_ptau_check(const zk_ptau_file_view *ptau, const uint8_t *s32, int32_t device, zk_ptau_report *report);
+
 #ifdef __cplusplus
 }
 #endif

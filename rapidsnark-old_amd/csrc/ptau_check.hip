@@ -1,0 +1,794 @@
+// Is a Powers of Tau file sound?  (include/zkhip.h, section "Powers of Tau: check".)  Nothing in the reference corresponds
+// to it: its prover reads a finished .zkey (src/main_prover.cpp:57-72); the counterpart is the arithmetic half of snarkjs
+// `powersoftau verify` (the contribution transcript of section 7 is NOT read: DESIGN.md section 18 says why).
+//
+// What is proved about a file of N = 2^power (T = section 2, U = 3, A = 4, B = 5, beta2 = 6; G1, G2 the generators):
+//   points      every coordinate below q, every point on its curve, none of sections 2 to 6 at infinity, every G2 point of
+//               sections 3, 6 and 13 in the order-r subgroup;
+//   generators  T_0 = G1 and U_0 = G2 (host, byte compare);
+//   powers      with one scalar s drawn AFTER the file is mapped, a row P_0 .. P_(m-1) gives F = sum s^i P_i by ONE
+//               multi-scalar multiplication, and from it  lo = F - s^(m-1) P_(m-1) = sum_(i<m-1) s^i P_i  and
+//               hi = (F - P_0) / s = sum_(i<m-1) s^i P_(i+1).  The row is a geometric sequence of the ratio the other group's
+//               tau-point fixes iff  e(lo, U_1) = e(hi, G2)  (rows of G1; e(T_1, lo) = e(G1, hi) for the row of G2), up to the
+//               chance 2^29 / r that s is a root of a non-zero polynomial of degree < 2^29.  e(B_0, G2) = e(G1, beta2) ties
+//               section 6 to section 5.  The five equations are one zk_pairing(group = 2) call;
+//   Lagrange    when sections 12 to 15 are there: for every level p (n = 2^p)  sum_j c_j Lag_j = sum_(i<n) s^i P_i  with
+//               c_j = sum_(i<n) s^i w^(ij), the FORWARD DFT of the powers of s.  The right sides are prefixes of F (it is
+//               accumulated over the ranges [2^(p-1), 2^p)), the left sides one multi-scalar multiplication per level; two
+//               group elements are compared after normalisation, no pairing.
+//
+// The G2 subgroup test (k_g2_subgroup), the hot path: a file of power 28 has 2^28 points in section 3 and twice as many
+// in section 13.  With psi the twist's Frobenius map (pairing.hpp's frob_twist: conjugate, multiply x by xi^((q-1)/3) and
+// y by xi^((q-1)/2)) and x = BN_X,
+//     Q is in the subgroup  <=>  [x+1] Q + psi([x] Q) + psi^2([x] Q) = psi^3([2x] Q)
+// (psi acts on the subgroup as multiplication by q, and (x + 1) + x q + x q^2 - 2 x q^3 = 0 mod r).  One 63-bit
+// double-and-add instead of the 254 bits of [r] Q.  That the test is exact and not merely necessary is a finite check
+// (tests/test_gpu_ptau_check.py repeats it on the device): the twist's group is cyclic of order
+// r h2 with h2 a product of four distinct primes, an endomorphism acts on each prime-order part as a scalar, and the
+// criterion fails on a point of each of the four parts.  One lane per point; the bits of x are a compile-time constant, so
+// every branch on them is uniform and nothing is indexed at run time; psi on XYZZ conjugates the four coordinates and
+// costs two Fq2 products; the comparison is projective (four Fq2 products, no inversion).  Points of small order meet
+// P = +-Q and infinity inside [x] Q: curve.hpp's dbl / madd / add take every case.
+// ZKHIP_SUBGROUP_PLAIN=1 runs k_g2_subgroup<true>, [r] Q by devmem.hpp's scalar_mul_affine, what pairing.hip does: a second
+// route to the same bytes for the tests and the denominator of tools/ptau_check_timing.py.
+//
+// The multi-scalar multiplications are the library's own (msm_sort / msm_accum / msm_reduce, the sequence of
+// operators.hip's msm_generic) on points and scalars that are already on the device; the scalars s^i and c_j are made
+// there, chunk by chunk (a row of power 28 would need 8 GiB of them on the host).  Points come from the caller's mapping
+// in chunks of ZKHIP_PTAU_CHUNK points (2^22 otherwise); chunk sums are added on the host (host_tail.cpp).
+// c_j has the closed form (s^n - 1) / (s w^j - 1), and c_j = n where s w^j = 1: k_power_dft makes four of them per lane
+// with one inversion (Montgomery's trick inside the lane), exact for every s < r.
+//
+// Fields: curve.hpp's 8 x 32-bit Montgomery forms (R = 2^256), the .ptau's own bytes, as ptau_prepare.hip and scale.hip.
+#include <errno.h>
+#include <sys/random.h>
+
+#include "hiputil.hpp"
+#include "devmem.hpp"
+#include "ptcheck.hpp"
+#include "pairing.hpp"
+
+namespace {
+
+constexpr uint32_t NONE = NO_BAD_POINT;
+constexpr uint64_t DEFAULT_CHUNK = 1ull << 22;        // points per chunk: 512 MiB of G2 input
+constexpr uint32_t MAX_LOG_N = 28;
+constexpr uint32_t POW_BITS = 64;                     // entries of a table of squarings: base^(2^i), i < 64
+// w_(2^28), standard form (ntt.hip)
+const uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
+
+static_assert((BN_X >> 62) == 1, "x has 63 bits: the loop of k_g2_subgroup starts below bit 62");
+
+// ---------------------------------------------------------------- device: the subgroup test
+struct PsiConsts {
+    Fq2 gx, gy;                                       // xi^((q-1)/3), xi^((q-1)/2): pairing.hpp's gamma1[1], gamma1[2]
+};
+
+// psi on XYZZ: x = X / ZZ and y = Y / ZZZ, so conjugating all four and multiplying X and Y is psi of the affine point
+__device__ __forceinline__ G2XYZZ psi(const G2XYZZ &p, const PsiConsts &k) {
+    if (p.is_inf()) return p;
+    return G2XYZZ{Fq2::mul(f2_conj(p.x), k.gx), Fq2::mul(f2_conj(p.y), k.gy), f2_conj(p.zz), f2_conj(p.zzz)};
+}
+__device__ __forceinline__ bool same_point(const G2XYZZ &a, const G2XYZZ &b) {
+    if (a.is_inf() || b.is_inf()) return a.is_inf() && b.is_inf();
+    return Fq2::mul(a.x, b.zz) == Fq2::mul(b.x, a.zz) && Fq2::mul(a.y, b.zzz) == Fq2::mul(b.y, a.zzz);
+}
+
+// out[i] (when given) = 1 if pts[i] is in the order-r subgroup (infinity: 1), else 0; the lowest index outside goes to
+// *err (when given).  The points are on the twist (the caller's check runs first; on other bytes the result means nothing).
+template <bool PLAIN>
+__global__ __launch_bounds__(64) void k_g2_subgroup(uint8_t *out, uint32_t *err, const G2Affine *__restrict__ pts, uint64_t n, PsiConsts k) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const G2Affine Q = load_pt(pts + i);
+    bool ok = true;
+    if (!Q.is_inf()) {
+        if constexpr (PLAIN) {
+            Fr r;
+#pragma unroll
+            for (int j = 0; j < 8; j++) r.v[j] = FrParams::P[j];
+            ok = scalar_mul_affine(Q, r).is_inf();
+        } else {
+            G2XYZZ L = G2XYZZ::from_affine(Q);        // bit 62 of x
+#pragma unroll 1
+            for (int b = 61; b >= 0; b--) {
+                L = dbl(L);
+                if ((BN_X >> b) & 1) madd(L, Q);
+            }
+            G2XYZZ T = psi(L, k);                     // psi([x] Q)
+            madd(L, Q);                               // [x + 1] Q
+            add(L, T);
+            T = psi(T, k);
+            add(L, T);
+            T = dbl(psi(T, k));                       // psi^3([2x] Q)
+            ok = same_point(L, T);
+        }
+    }
+    if (out) out[i] = ok ? 1 : 0;
+    if (!ok && err) atomicMin(err, (uint32_t)i);
+}
+
+// ---------------------------------------------------------------- device: what a file's point may be
+// err[0]: the lowest index with a coordinate >= q, err[1]: off the curve, err[3]: at infinity where that is not legal
+// (err[2] is the subgroup kernel's)
+template <class F>
+__global__ __launch_bounds__(256) void k_ptau_classify(uint32_t *err, const Affine<F> *__restrict__ src, uint64_t n, F b, uint32_t inf_bad) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Affine<F> p = load_pt(src + i);
+    if (p.is_inf()) {
+        if (inf_bad) atomicMin(err + 3, (uint32_t)i);
+        return;
+    }
+    if (!(below_q(p.x) && below_q(p.y))) atomicMin(err + 0, (uint32_t)i);
+    else if (!(F::sqr(p.y) == F::add(F::mul(F::sqr(p.x), p.x), b))) atomicMin(err + 1, (uint32_t)i);
+}
+
+// ---------------------------------------------------------------- device: scalars
+// base^e for a lane's own e from the table of squarings tab[i] = base^(2^i) (Montgomery)
+__device__ __forceinline__ Fr pow_tab(const Fr *__restrict__ tab, uint64_t e) {
+    Fr acc = Fr::one();
+#pragma unroll 1
+    for (uint32_t b = 0; b < POW_BITS && (e >> b); b++)
+        if ((e >> b) & 1) acc = Fr::mul(acc, load_el(tab + b));
+    return acc;
+}
+
+// out[i] = base^(e0 + i), standard form (what the sort of a multi-scalar multiplication reads)
+__global__ __launch_bounds__(256) void k_fr_powers(Fr *out, const Fr *__restrict__ tab, uint64_t e0, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    store_el(out + i, Fr::from_mont(pow_tab(tab, e0 + i)));
+}
+
+// a^(r-2); the exponent is shifted, not indexed
+__device__ __forceinline__ Fr fr_inv_dev(const Fr &a) {
+    uint32_t e[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) e[i] = FrParams::P[i];
+    e[0] -= 2;
+    Fr result = Fr::one(), base = a;
+#pragma unroll 1
+    for (int i = 0; i < 254; i++) {
+        if (e[0] & 1u) result = Fr::mul(result, base);
+        base = Fr::sqr(base);
+#pragma unroll
+        for (int q = 0; q < 7; q++) e[q] = (e[q] >> 1) | (e[q + 1] << 31);
+        e[7] >>= 1;
+    }
+    return result;
+}
+
+// out[t] = c_(j0 + t) = sum_(i<n) s^i w^(i (j0 + t)) for t < cnt, standard form, n = 2^log_n and w its root of unity:
+// (s^n - 1) / (s w^j - 1), and n where s w^j = 1.  tab: the squarings of w_(2^28); w^j = w_(2^28)^(j << shift).
+// num = s^n - 1, nval = n, all Montgomery.  A lane makes DFT_PER_LANE consecutive values with one inversion.
+constexpr uint32_t DFT_PER_LANE = 4;
+__global__ __launch_bounds__(256) void k_power_dft(Fr *out, const Fr *__restrict__ tab, uint32_t shift, Fr s, Fr w, Fr num, Fr nval, uint64_t j0, uint64_t cnt) {
+    const uint64_t t0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * DFT_PER_LANE;
+    if (t0 >= cnt) return;
+    Fr x = Fr::mul(s, pow_tab(tab, (j0 + t0) << shift));                       // s w^j
+    Fr d[DFT_PER_LANE], pre[DFT_PER_LANE];
+    bool unit[DFT_PER_LANE];
+#pragma unroll
+    for (uint32_t k = 0; k < DFT_PER_LANE; k++) {
+        d[k] = Fr::sub(x, Fr::one());
+        unit[k] = d[k].is_zero();
+        if (unit[k]) d[k] = Fr::one();
+        pre[k] = k ? Fr::mul(pre[k - 1], d[k]) : d[k];
+        x = Fr::mul(x, w);
+    }
+    Fr inv = fr_inv_dev(pre[DFT_PER_LANE - 1]);
+#pragma unroll
+    for (int k = DFT_PER_LANE - 1; k >= 0; k--) {
+        const Fr ik = k ? Fr::mul(inv, pre[k - 1]) : inv;                       // 1 / d[k]
+        inv = Fr::mul(inv, d[k]);
+        if (t0 + k < cnt) store_el(out + t0 + k, Fr::from_mont(unit[k] ? nval : Fr::mul(num, ik)));
+    }
+}
+
+// ---------------------------------------------------------------- host: scalars
+bool below(const uint8_t a[32], const uint32_t p[8]) {
+    uint32_t w[8];
+    memcpy(w, a, 32);
+    for (int i = 7; i >= 0; i--)
+        if (w[i] != p[i]) return w[i] < p[i];
+    return false;
+}
+Fr fr_from_std(const uint8_t a[32]) {
+    Fr x;
+    memcpy(x.v, a, 32);
+    return Fr::to_mont(x);
+}
+Fr fr_small(uint64_t v) {
+    Fr x = Fr::zero();
+    x.v[0] = (uint32_t)v;
+    x.v[1] = (uint32_t)(v >> 32);
+    return Fr::to_mont(x);
+}
+void fr_to_std(uint8_t out[32], const Fr &a) {
+    const Fr x = Fr::from_mont(a);
+    memcpy(out, x.v, 32);
+}
+Fr fr_pow(Fr base, uint64_t e) {
+    Fr acc = Fr::one();
+    for (; e; e >>= 1) {
+        if (e & 1) acc = Fr::mul(acc, base);
+        base = Fr::sqr(base);
+    }
+    return acc;
+}
+Fr root_of_unity(uint32_t log_n) {                    // the 2^log_n-th root zk_fr_ntt uses
+    Fr w;
+    for (int i = 0; i < 8; i++) w.v[i] = ROOT_2_28_STD[i];
+    w = Fr::to_mont(w);
+    for (uint32_t i = log_n; i < MAX_LOG_N; i++) w = Fr::sqr(w);
+    return w;
+}
+
+uint64_t chunk_points() {
+    const char *e = getenv("ZKHIP_PTAU_CHUNK");
+    if (e && *e) {
+        char *end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (*end || v < 1 || v > (1ull << 28)) throw std::invalid_argument("ZKHIP_PTAU_CHUNK: a number of points from 1 to 2^28 expected");
+        return v;
+    }
+    return DEFAULT_CHUNK;
+}
+bool plain_subgroup() {
+    const char *e = getenv("ZKHIP_SUBGROUP_PLAIN");
+    return e && *e && strcmp(e, "0") != 0;
+}
+
+PsiConsts psi_consts() {
+    PairConsts pc;
+    pair_consts_init(pc);
+    return PsiConsts{pc.gamma1[1], pc.gamma1[2]};
+}
+
+// tab[i] = base^(2^i) on the device
+struct PowTable {
+    DevBuf<Fr> d;
+    void build(Fr base, hipStream_t s) {
+        Fr h[POW_BITS];
+        for (uint32_t i = 0; i < POW_BITS; i++) {
+            h[i] = base;
+            base = Fr::sqr(base);
+        }
+        d.alloc(POW_BITS);
+        HIP_TRY(hipMemcpyAsync(d.p, h, sizeof h, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));             // h leaves scope
+    }
+};
+
+// the scalars c_j of one transform size
+struct DftScalars {
+    uint32_t log_n, shift;
+    Fr s, w, num, nval;
+    DftScalars(const Fr &s_, uint32_t log_n_) : log_n(log_n_), shift(MAX_LOG_N - log_n_), s(s_), w(root_of_unity(log_n_)) {
+        Fr sn = s;
+        for (uint32_t i = 0; i < log_n; i++) sn = Fr::sqr(sn);
+        num = Fr::sub(sn, Fr::one());
+        nval = fr_small(1ull << log_n);
+    }
+    // d_out[t] = c_(j0 + t), t < cnt
+    void launch(Fr *d_out, const PowTable &wtab, uint64_t j0, uint64_t cnt, hipStream_t st) const {
+        const uint64_t lanes = (cnt + DFT_PER_LANE - 1) / DFT_PER_LANE;
+        ZK_LAUNCH(k_power_dft, dim3(nblocks(lanes, 256)), dim3(256), 0, st, d_out, wtab.d.p, shift, s, w, num, nval, j0, cnt);
+        ZK_LAUNCH_OK("power dft");
+    }
+};
+
+// ---------------------------------------------------------------- host: points as the file's bytes
+template <class F>
+struct Group;
+template <>
+struct Group<Fq> {
+    typedef G1Acc Acc;
+    static void add(uint8_t *acc, const uint8_t *in) { HostTail::add_affine_g1(acc, in); }
+    static void mul(uint8_t *out, const uint8_t *p, const uint8_t k[32]) {
+        if (zk_g1_mul(out, p, k) != 0) throw std::runtime_error(std::string("zk_g1_mul: ") + get_error());
+    }
+};
+template <>
+struct Group<Fq2> {
+    typedef G2Acc Acc;
+    static void add(uint8_t *acc, const uint8_t *in) { HostTail::add_affine_g2(acc, in); }
+    static void mul(uint8_t *out, const uint8_t *p, const uint8_t k[32]) {
+        if (zk_g2_mul(out, p, k) != 0) throw std::runtime_error(std::string("zk_g2_mul: ") + get_error());
+    }
+};
+template <class F>
+struct Pt {                                           // one affine point, the file's bytes
+    uint8_t b[sizeof(Affine<F>)];
+    Pt() { memset(b, 0, sizeof b); }
+    explicit Pt(const void *p) { memcpy(b, p, sizeof b); }
+    bool operator==(const Pt &o) const { return memcmp(b, o.b, sizeof b) == 0; }
+    Pt neg() const {
+        Affine<F> a;
+        memcpy(&a, b, sizeof a);
+        if (!a.is_inf()) a.y = F::neg(a.y);
+        return Pt(&a);
+    }
+    Pt operator+(const Pt &o) const {
+        Pt r = *this;
+        Group<F>::add(r.b, o.b);
+        return r;
+    }
+    Pt operator-(const Pt &o) const { return *this + o.neg(); }
+    Pt times(const Fr &k) const {
+        uint8_t k32[32];
+        fr_to_std(k32, k);
+        Pt r;
+        Group<F>::mul(r.b, b, k32);
+        return r;
+    }
+};
+
+// ---------------------------------------------------------------- host: a multi-scalar multiplication on device-resident inputs
+// The sequence of operators.hip's msm_generic; the buffers stay across calls of one size (the chunks of a row).
+template <class F>
+struct DevMsm {
+    typedef typename Group<F>::Acc Acc;
+    SortBufs sb;
+    DevBuf<Acc> buckets, scratch, ws;
+    DevBuf<XYZZ<F>> wsum;
+    DevBuf<uint32_t> wkey, wflag;
+    std::vector<uint8_t> w;
+    uint64_t n = 0, emax = 0;
+    uint32_t rc = 0;
+    void size(uint64_t n_) {
+        if (n_ == n) return;
+        n = 0;
+        sb.alloc(n_, 0);
+        emax = sb.max_entries();
+        const uint64_t slots = msm_accum_workspace_slots(emax);
+        ws.alloc(slots);
+        wkey.alloc(slots);
+        wflag.alloc(slots);
+        buckets.alloc(sb.total_buckets());
+        scratch.alloc(msm_reduce_scratch_points(1, sb.plan));
+        rc = msm_wsum_rc(sb.plan);
+        wsum.alloc((uint64_t)sb.plan.sets * rc);
+        w.resize((size_t)sb.plan.sets * rc * sizeof(XYZZ<F>));
+        n = n_;
+    }
+    // out = sum sc[i] pts[i], i < n_ (n_ >= 1).  pts: the file's form, converted in place to the kernels' own; sc: standard form
+    void run(uint8_t *out, Affine<F> *pts, const Fr *sc, uint64_t n_, hipStream_t s) {
+        size(n_);
+        launch_fq_to_internal(reinterpret_cast<Fq *>(pts), n_ * (sizeof(Affine<F>) / 32), s);
+        sb.run(sc, s);
+        if constexpr (sizeof(F) == sizeof(Fq)) {
+            launch_msm_accum_g1(buckets.p, sb.offsets.p, sb.entries.p, pts, 0, 0, sb.total_buckets(), emax, ws.p, wkey.p, wflag.p, s);
+            launch_msm_reduce_g1(wsum.p, scratch.p, buckets.p, 1, sb.plan, s);
+        } else {
+            launch_msm_accum_g2(buckets.p, sb.offsets.p, sb.entries.p, pts, 0, 0, sb.total_buckets(), emax, ws.p, wkey.p, wflag.p, s);
+            launch_msm_reduce_g2(wsum.p, scratch.p, buckets.p, 1, sb.plan, s);
+        }
+        HIP_TRY(hipMemcpyAsync(w.data(), wsum.p, w.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if constexpr (sizeof(F) == sizeof(Fq)) HostTail::combine_windows_g1(w.data(), sb.plan.sets, sb.plan.c, rc, out);
+        else HostTail::combine_windows_g2(w.data(), sb.plan.sets, sb.plan.c, rc, out);
+    }
+    // An upper estimate of the HBM of size(n_), made without a device: the sort's buffers are exact; the accumulation's
+    // workspace is bounded by a lane per ACC_CHUNK_MIN = 32 entries plus one full round of lanes, twice per level
+    static uint64_t bytes(uint64_t n_) {
+        const MsmPlan p = make_msm_plan(n_ ? n_ : 1, 0);
+        const MsmSortSizes z = msm_sort_sizes(n_, p);
+        const uint64_t sort = 2 * z.lo_u16 + 4 * (z.counts_u32 + z.starts_u32 + z.offsets_u32 + z.entries_u32 + z.codes_u32 + z.val_u32 + z.bin_counts_u32 + z.bin_starts_u32);
+        const uint64_t slots = 5 * ((n_ ? n_ : 1) * p.W / 32 + (1ull << 19));
+        return sort + slots * (sizeof(Acc) + 8) + ((uint64_t)p.sets * p.nbuckets + msm_reduce_scratch_points(1, p)) * sizeof(Acc) +
+               (uint64_t)p.sets * msm_wsum_rc(p) * sizeof(XYZZ<F>) + 65536;
+    }
+};
+
+// One group's buffers: a chunk of points, its scalars, the words of the checks, the multiplication's workspace
+template <class F>
+struct Engine {
+    typedef Affine<F> Aff;
+    hipStream_t s;
+    StreamUploader up;
+    uint64_t cap;
+    DevBuf<Aff> pts;
+    DevBuf<Fr> sc;
+    DevBuf<uint32_t> err;                             // four words
+    DevMsm<F> msm;
+    Engine(hipStream_t s_, uint64_t cap_) : s(s_), up(s_), cap(cap_ ? cap_ : 1) {
+        pts.alloc(cap);
+        sc.alloc(cap);
+        err.alloc(4);
+    }
+    static uint64_t bytes(uint64_t cap_) { return cap_ * (sizeof(Aff) + sizeof(Fr)) + DevMsm<F>::bytes(cap_) + 4096; }
+    void load(const uint8_t *src, uint64_t cnt) { up.copy(pts.p, src, cnt * sizeof(Aff)); }
+    // the lowest index of the loaded chunk that is not a point of the curve, NONE when there is none
+    uint32_t first_off_curve(uint64_t cnt) {
+        launch_point_check<F>(err.p, pts.p, cnt, s);
+        uint32_t bad = NONE;
+        HIP_TRY(hipMemcpyAsync(&bad, err.p, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return bad;
+    }
+    // acc += sum sc[i] pts[i] over the loaded chunk
+    void accumulate(Pt<F> &acc, uint64_t cnt) {
+        Pt<F> part;
+        msm.run(part.b, pts.p, sc.p, cnt, s);
+        acc = acc + part;
+    }
+};
+
+void launch_subgroup(uint8_t *d_out, uint32_t *d_err, const G2Affine *d_pts, uint64_t n, const PsiConsts &k, bool plain, hipStream_t s) {
+    if (!n) return;
+    if (plain) ZK_LAUNCH(k_g2_subgroup<true>, dim3(nblocks(n, 64)), dim3(64), 0, s, d_out, d_err, d_pts, n, k);
+    else ZK_LAUNCH(k_g2_subgroup<false>, dim3(nblocks(n, 64)), dim3(64), 0, s, d_out, d_err, d_pts, n, k);
+    ZK_LAUNCH_OK("g2 subgroup test");
+}
+
+// ---------------------------------------------------------------- the operators
+void g2_in_subgroup(uint8_t *out, const uint8_t *points, uint64_t n, int32_t device) {
+    if (!n) return;
+    if (!out || !points) throw std::invalid_argument("null argument");
+    const uint64_t chunk = chunk_points(), cap = n < chunk ? n : chunk;
+    const bool plain = plain_subgroup();
+    const PsiConsts k = psi_consts();
+    DeviceGuard g(resolve_device(device));
+    need_hbm("zk_g2_in_subgroup", cap * (sizeof(G2Affine) + 1) + 65536);
+    Stream st;
+    StreamUploader up(st.s);
+    DevBuf<G2Affine> pts;
+    DevBuf<uint8_t> flags;
+    DevBuf<uint32_t> err;
+    pts.alloc(cap);
+    flags.alloc(cap);
+    err.alloc(1);
+    for (uint64_t off = 0; off < n; off += cap) {
+        const uint64_t cnt = n - off < cap ? n - off : cap;
+        up.copy(pts.p, points + off * sizeof(G2Affine), cnt * sizeof(G2Affine));
+        launch_point_check<Fq2>(err.p, pts.p, cnt, st.s);
+        launch_subgroup(flags.p, nullptr, pts.p, cnt, k, plain, st.s);
+        uint32_t bad = NONE;
+        HIP_TRY(hipMemcpyAsync(&bad, err.p, 4, hipMemcpyDeviceToHost, st.s));
+        HIP_TRY(hipMemcpyAsync(out + off, flags.p, cnt, hipMemcpyDeviceToHost, st.s));
+        HIP_TRY(hipStreamSynchronize(st.s));
+        if (bad != NONE) throw std::invalid_argument("zk_g2_in_subgroup: point " + std::to_string(off + bad) + " is not on the curve");
+    }
+}
+
+Fr checked_scalar(const uint8_t s32[32], const char *who) {
+    if (!below(s32, FrParams::P)) throw std::invalid_argument(std::string(who) + ": the scalar is not below r");
+    return fr_from_std(s32);
+}
+
+template <class F>
+void power_msm(uint8_t *out, const uint8_t *points, uint64_t n, const uint8_t s32[32], uint64_t first_exp, int32_t device, const char *who) {
+    if (!out || !s32 || (n && !points)) throw std::invalid_argument("null argument");
+    const Fr s = checked_scalar(s32, who);
+    if (first_exp + n < first_exp) throw std::invalid_argument(std::string(who) + ": first_exp + n exceeds 2^64");
+    memset(out, 0, sizeof(Affine<F>));
+    if (!n) return;
+    const uint64_t chunk = chunk_points(), cap = n < chunk ? n : chunk;
+    DeviceGuard g(resolve_device(device));
+    need_hbm(who, Engine<F>::bytes(cap));
+    Stream st;
+    PowTable stab;
+    stab.build(s, st.s);
+    Engine<F> e(st.s, cap);
+    Pt<F> acc;
+    for (uint64_t off = 0; off < n; off += cap) {
+        const uint64_t cnt = n - off < cap ? n - off : cap;
+        e.load(points + off * sizeof(Affine<F>), cnt);
+        const uint32_t bad = e.first_off_curve(cnt);
+        if (bad != NONE) throw std::invalid_argument(std::string(who) + ": point " + std::to_string(off + bad) + " is not on the curve");
+        ZK_LAUNCH(k_fr_powers, dim3(nblocks(cnt, 256)), dim3(256), 0, st.s, e.sc.p, stab.d.p, first_exp + off, cnt);
+        ZK_LAUNCH_OK("powers");
+        e.accumulate(acc, cnt);
+    }
+    memcpy(out, acc.b, sizeof acc.b);
+}
+
+void fr_power_dft(uint8_t *out, const uint8_t s32[32], uint32_t log_n, int32_t device) {
+    if (!out || !s32) throw std::invalid_argument("null argument");
+    if (log_n > MAX_LOG_N) throw std::invalid_argument("zk_fr_power_dft: log_n " + std::to_string(log_n) + " exceeds 28");
+    const DftScalars ds(checked_scalar(s32, "zk_fr_power_dft"), log_n);
+    const uint64_t n = 1ull << log_n, chunk = chunk_points(), cap = n < chunk ? n : chunk;
+    DeviceGuard g(resolve_device(device));
+    need_hbm("zk_fr_power_dft", cap * sizeof(Fr) + 65536);
+    Stream st;
+    PowTable wtab;
+    wtab.build(root_of_unity(MAX_LOG_N), st.s);
+    DevBuf<Fr> d;
+    d.alloc(cap);
+    for (uint64_t off = 0; off < n; off += cap) {
+        const uint64_t cnt = n - off < cap ? n - off : cap;
+        ds.launch(d.p, wtab, off, cnt, st.s);
+        HIP_TRY(hipMemcpyAsync(out + off * sizeof(Fr), d.p, cnt * sizeof(Fr), hipMemcpyDeviceToHost, st.s));
+        HIP_TRY(hipStreamSynchronize(st.s));
+    }
+}
+
+// ---------------------------------------------------------------- the whole file
+constexpr uint32_t KIND_COORD = 1, KIND_CURVE = 2, KIND_SUBGROUP = 3, KIND_INFINITY = 4;
+constexpr int POWER_SECS[4] = {2, 3, 4, 5}, LAGRANGE_SECS[4] = {12, 13, 14, 15};
+
+struct FilePlan {
+    uint32_t power = 0;
+    bool prepared = false;
+    uint64_t n = 0, cap = 0, device_bytes = 0;
+    uint64_t points[16] = {};                         // per section
+    uint32_t top[16] = {};                            // the highest level (Lagrange sections) / prefix (power sections)
+};
+
+uint64_t point_bytes(int sec) { return sec == 3 || sec == 6 || sec == 13 ? 128 : 64; }
+
+void check_view(const zk_ptau_file_view *v, FilePlan &pl) {
+    if (!v) throw std::invalid_argument("null argument");
+    int have = 0, missing = 0;
+    for (int sec : LAGRANGE_SECS) {
+        if (v->sec[sec]) have++;
+        else if (!missing) missing = sec;
+    }
+    if (have && have < 4)
+        throw std::invalid_argument("ptau has only some of the Lagrange sections 12 to 15 (section " + std::to_string(missing) + " is missing): it is neither prepared for phase 2 nor not");
+    pl.prepared = have == 4;
+    const uint32_t max_power = pl.prepared ? 27 : 28;
+    if (v->power < 1 || v->power > max_power)
+        throw std::invalid_argument("ptau power " + std::to_string(v->power) + " is not supported (1 to " + std::to_string(max_power) +
+                                    (pl.prepared ? ": level power + 1 of section 12 needs a 2^(power+1)-th root of unity)" : ")"));
+    pl.power = v->power;
+    pl.n = 1ull << v->power;
+    const uint64_t n = pl.n;
+    pl.points[2] = 2 * n - 1;
+    pl.points[3] = pl.points[4] = pl.points[5] = n;
+    pl.points[6] = 1;
+    pl.top[2] = v->power + 1;
+    pl.top[3] = pl.top[4] = pl.top[5] = v->power;
+    if (pl.prepared) {
+        pl.points[12] = 4 * n - 1;
+        pl.points[13] = pl.points[14] = pl.points[15] = 2 * n - 1;
+        pl.top[12] = v->power + 1;
+        pl.top[13] = pl.top[14] = pl.top[15] = v->power;
+    }
+    for (int sec = 2; sec < 16; sec++) {
+        if (!pl.points[sec]) continue;
+        if (!v->sec[sec]) throw std::invalid_argument("ptau has no section " + std::to_string(sec));
+        const uint64_t need = pl.points[sec] * point_bytes(sec);
+        if (v->sec_bytes[sec] < need)
+            throw std::invalid_argument("ptau section " + std::to_string(sec) + " is short: " + std::to_string(v->sec_bytes[sec]) + " bytes, power " +
+                                        std::to_string(v->power) + " needs " + std::to_string(need));
+    }
+    const uint64_t chunk = chunk_points(), most = pl.prepared ? 2 * n : n;     // the largest range or level
+    pl.cap = most < chunk ? most : chunk;
+    pl.device_bytes = Engine<Fq>::bytes(pl.cap) + Engine<Fq2>::bytes(pl.cap) + 2 * POW_BITS * sizeof(Fr) + 65536;
+}
+
+void generators(Pt<Fq> &g1, Pt<Fq2> &g2) {
+    // (1, 2), and the generator of G2 of EIP-197, standard form
+    static const uint32_t G2_STD[4][8] = {
+        {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu},
+        {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u},
+        {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u},
+        {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u}};
+    const G1Affine a{fq_std(1), fq_std(2)};
+    const G2Affine b{Fq2{fq_std(G2_STD[0]), fq_std(G2_STD[1])}, Fq2{fq_std(G2_STD[2]), fq_std(G2_STD[3])}};
+    g1 = Pt<Fq>(&a);
+    g2 = Pt<Fq2>(&b);
+}
+
+void draw_scalar(uint8_t s32[32]) {
+    for (;;) {
+        size_t got = 0;
+        while (got < 32) {
+            const ssize_t k = getrandom(s32 + got, 32 - got, 0);
+            if (k < 0) {
+                if (errno == EINTR) continue;
+                throw std::runtime_error("zk_ptau_check: the random source failed");
+            }
+            got += (size_t)k;
+        }
+        bool small = s32[0] < 2;
+        for (int i = 1; i < 32 && small; i++) small = s32[i] == 0;
+        if (!small && below(s32, FrParams::P)) return;
+    }
+}
+
+struct Checker {
+    const zk_ptau_file_view *v;
+    const FilePlan &pl;
+    zk_ptau_report *rep;
+    hipStream_t st;
+    Fr s;
+    PowTable stab, wtab;
+    PsiConsts psi;
+    bool plain;
+    Engine<Fq> e1;
+    Engine<Fq2> e2;
+    Checker(const zk_ptau_file_view *v_, const FilePlan &pl_, zk_ptau_report *rep_, const Fr &s_, hipStream_t st_)
+        : v(v_), pl(pl_), rep(rep_), st(st_), s(s_), psi(psi_consts()), plain(plain_subgroup()), e1(st_, pl_.cap), e2(st_, pl_.cap) {
+        stab.build(s, st);
+        wtab.build(root_of_unity(MAX_LOG_N), st);
+    }
+    template <class F>
+    Engine<F> &engine() {
+        if constexpr (sizeof(F) == sizeof(Fq)) return e1;
+        else return e2;
+    }
+
+    // Loads points [first, first + cnt) of section `sec` and checks them; false: the report names a malformed point
+    template <class F>
+    bool load_checked(int sec, uint64_t first, uint64_t cnt) {
+        Engine<F> &e = engine<F>();
+        e.load(static_cast<const uint8_t *>(v->sec[sec]) + first * sizeof(Affine<F>), cnt);
+        HIP_TRY(hipMemsetAsync(e.err.p, 0xFF, 16, st));
+        ZK_LAUNCH(k_ptau_classify<F>, dim3(nblocks(cnt, 256)), dim3(256), 0, st, e.err.p, e.pts.p, cnt, curve_b<F>(), sec < 12 ? 1u : 0u);
+        ZK_LAUNCH_OK("ptau point check");
+        if constexpr (sizeof(F) == sizeof(Fq2)) {
+            if (sec == 3 || sec == 6 || sec == 13) launch_subgroup(nullptr, e.err.p + 2, e.pts.p, cnt, psi, plain, st);
+        }
+        uint32_t h[4];
+        HIP_TRY(hipMemcpyAsync(h, e.err.p, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        uint32_t kind = 0, idx = NONE;
+        for (uint32_t k = 0; k < 4; k++)              // the lowest index; of two kinds at one index the first (a point off the
+            if (h[k] < idx) {                         // curve has no meaningful subgroup verdict)
+                idx = h[k];
+                kind = k + 1;
+            }
+        if (!kind) return true;
+        rep->verdict = 2;
+        rep->bad_section = (uint32_t)sec;
+        rep->bad_kind = kind;
+        rep->bad_index = first + idx;
+        return false;
+    }
+
+    // prefix[p] = sum_(i < min(2^p, m)) s^i P_i of the m points of section `sec`, p <= top; false: malformed
+    template <class F>
+    bool power_row(int sec, std::vector<Pt<F>> &prefix) {
+        Engine<F> &e = engine<F>();
+        const uint64_t m = pl.points[sec];
+        const uint32_t top = pl.top[sec];
+        prefix.assign(top + 1, Pt<F>());
+        Pt<F> acc;
+        for (uint32_t p = 0; p <= top; p++) {
+            const uint64_t lo = p ? 1ull << (p - 1) : 0, full = 1ull << p, hi = full < m ? full : m;
+            for (uint64_t off = lo; off < hi; off += e.cap) {
+                const uint64_t cnt = hi - off < e.cap ? hi - off : e.cap;
+                if (!load_checked<F>(sec, off, cnt)) return false;
+                ZK_LAUNCH(k_fr_powers, dim3(nblocks(cnt, 256)), dim3(256), 0, st, e.sc.p, stab.d.p, off, cnt);
+                ZK_LAUNCH_OK("powers");
+                e.accumulate(acc, cnt);
+            }
+            prefix[p] = acc;
+        }
+        return true;
+    }
+
+    // bit p of the result: level p of Lagrange section `sec` is not the Lagrange form of the row with these prefixes
+    template <class F>
+    bool lagrange_section(int sec, const std::vector<Pt<F>> &prefix, uint32_t &failed) {
+        Engine<F> &e = engine<F>();
+        failed = 0;
+        for (uint32_t p = 0; p <= pl.top[sec]; p++) {
+            const uint64_t n = 1ull << p, base = n - 1;
+            const DftScalars ds(s, p);
+            Pt<F> acc;
+            for (uint64_t off = 0; off < n; off += e.cap) {
+                const uint64_t cnt = n - off < e.cap ? n - off : e.cap;
+                if (!load_checked<F>(sec, base + off, cnt)) return false;
+                ds.launch(e.sc.p, wtab, off, cnt, st);
+                e.accumulate(acc, cnt);
+            }
+            if (!(acc == prefix[p])) failed |= 1u << p;
+        }
+        return true;
+    }
+};
+
+// lo = F - s^(m-1) P_(m-1), hi = (F - P_0) / s
+template <class F>
+void shifted_sums(Pt<F> &lo, Pt<F> &hi, const Pt<F> &sum, const void *row, uint64_t m, const Fr &s) {
+    const uint8_t *b = static_cast<const uint8_t *>(row);
+    lo = sum - Pt<F>(b + (m - 1) * sizeof(Affine<F>)).times(fr_pow(s, m - 1));
+    hi = (sum - Pt<F>(b)).times(Fr::inv(s));
+}
+
+void ptau_check(const zk_ptau_file_view *v, const uint8_t *s32_in, int32_t device, zk_ptau_report *rep) {
+    if (!rep) throw std::invalid_argument("null argument");
+    memset(rep, 0, sizeof *rep);
+    FilePlan pl;
+    check_view(v, pl);                                // the file is checked before the device is touched
+    uint8_t s32[32];
+    if (s32_in) {
+        memcpy(s32, s32_in, 32);
+        bool small = s32[0] < 2;
+        for (int i = 1; i < 32 && small; i++) small = s32[i] == 0;
+        if (small || !below(s32, FrParams::P)) throw std::invalid_argument("zk_ptau_check: the check scalar must be at least 2 and below r");
+    } else {
+        draw_scalar(s32);                             // after the file is mapped: its maker did not know s
+    }
+    const Fr s = fr_from_std(s32);
+    Pt<Fq> g1;
+    Pt<Fq2> g2;
+    generators(g1, g2);
+    const uint8_t *T = static_cast<const uint8_t *>(v->sec[2]), *U = static_cast<const uint8_t *>(v->sec[3]);
+    uint32_t failed = 0;
+    if (!(Pt<Fq>(T) == g1) || !(Pt<Fq2>(U) == g2)) failed |= 1u;
+
+    const int dev = resolve_device(device);
+    DeviceGuard g(dev);
+    need_hbm("zk_ptau_check", pl.device_bytes);
+    Stream st;
+    Checker c(v, pl, rep, s, st.s);
+    std::vector<Pt<Fq>> pre2, pre4, pre5;
+    std::vector<Pt<Fq2>> pre3;
+    if (!c.power_row<Fq>(2, pre2) || !c.power_row<Fq2>(3, pre3) || !c.power_row<Fq>(4, pre4) || !c.power_row<Fq>(5, pre5)) return;
+    if (!c.load_checked<Fq2>(6, 0, 1)) return;
+    uint32_t lag[4] = {0, 0, 0, 0};
+    if (pl.prepared) {
+        if (!c.lagrange_section<Fq>(12, pre2, lag[0]) || !c.lagrange_section<Fq2>(13, pre3, lag[1]) || !c.lagrange_section<Fq>(14, pre4, lag[2]) ||
+            !c.lagrange_section<Fq>(15, pre5, lag[3]))
+            return;
+    }
+
+    // the five equations, each a product of two pairings that must be 1
+    const Pt<Fq> T1(T + 64), B0(v->sec[5]);
+    const Pt<Fq2> U1(U + 128), beta2(v->sec[6]);
+    Pt<Fq> lo2, hi2, lo4, hi4, lo5, hi5;
+    Pt<Fq2> lo3, hi3;
+    shifted_sums(lo2, hi2, pre2.back(), v->sec[2], pl.points[2], s);
+    shifted_sums(lo3, hi3, pre3.back(), v->sec[3], pl.points[3], s);
+    shifted_sums(lo4, hi4, pre4.back(), v->sec[4], pl.points[4], s);
+    shifted_sums(lo5, hi5, pre5.back(), v->sec[5], pl.points[5], s);
+    const Pt<Fq> ng1 = g1.neg();
+    const Pt<Fq> p1[10] = {lo2, hi2.neg(), T1, ng1, lo4, hi4.neg(), lo5, hi5.neg(), B0, ng1};
+    const Pt<Fq2> p2[10] = {U1, g2, lo3, hi3, U1, g2, U1, g2, g2, beta2};
+    static const uint32_t bit[5] = {2, 3, 4, 5, 6};
+    uint8_t b1[10 * 64], b2[10 * 128], gt[5 * 384];
+    for (int i = 0; i < 10; i++) {
+        memcpy(b1 + 64 * i, p1[i].b, 64);
+        memcpy(b2 + 128 * i, p2[i].b, 128);
+    }
+    if (zk_pairing(gt, b1, b2, 10, 2, dev) != 0) throw std::runtime_error(std::string("zk_ptau_check: ") + get_error());
+    for (int e = 0; e < 5; e++) {
+        const uint8_t *o = gt + 384 * e;
+        bool one = o[0] == 1;
+        for (int i = 1; i < 384 && one; i++) one = o[i] == 0;
+        if (!one) failed |= 1u << bit[e];
+    }
+    rep->failed = failed;
+    for (int i = 0; i < 4; i++) rep->lagrange_failed[i] = lag[i];
+    rep->verdict = failed || lag[0] || lag[1] || lag[2] || lag[3] ? 1 : 0;
+}
+
+}   // namespace
+
+extern "C" {
+
+int zk_g2_in_subgroup(uint8_t *out, const uint8_t *points, uint64_t n, int32_t device) {
+    return guarded([&] { g2_in_subgroup(out, points, n, device); });
+}
+int zk_g1_power_msm(uint8_t out[64], const uint8_t *points, uint64_t n, const uint8_t s[32], uint64_t first_exp, int32_t device) {
+    return guarded([&] { power_msm<Fq>(out, points, n, s, first_exp, device, "zk_g1_power_msm"); });
+}
+int zk_g2_power_msm(uint8_t out[128], const uint8_t *points, uint64_t n, const uint8_t s[32], uint64_t first_exp, int32_t device) {
+    return guarded([&] { power_msm<Fq2>(out, points, n, s, first_exp, device, "zk_g2_power_msm"); });
+}
+int zk_fr_power_dft(uint8_t *out, const uint8_t s[32], uint32_t log_n, int32_t device) {
+    return guarded([&] { fr_power_dft(out, s, log_n, device); });
+}
+
+int zk_ptau_check_sizes(const zk_ptau_file_view *ptau, zk_ptau_check_sizes_t *sizes) {
+    return guarded([&] {
+        if (!sizes) throw std::invalid_argument("null argument");
+        FilePlan pl;
+        check_view(ptau, pl);
+        sizes->prepared = pl.prepared ? 1 : 0;
+        sizes->chunk_points = pl.cap;
+        sizes->device_bytes = pl.device_bytes;
+    });
+}
+
+int zk_ptau_check(const zk_ptau_file_view *ptau, const uint8_t *s32, int32_t device, zk_ptau_report *report) {
+    return guarded([&] { ptau_check(ptau, s32, device, report); });
+}
+
+}   // extern "C"

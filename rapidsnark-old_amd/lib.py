@@ -105,6 +105,19 @@ class zk_vkey_view(C.Structure):
                 ("IC", C.c_void_p), ("nPublic", C.c_uint32)]
 
 
+class zk_ptau_file_view(C.Structure):
+    _fields_ = [("power", C.c_uint32), ("sec", C.c_void_p * 16), ("sec_bytes", C.c_uint64 * 16)]
+
+
+class zk_ptau_check_sizes_t(C.Structure):
+    _fields_ = [("prepared", C.c_uint32), ("chunk_points", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class zk_ptau_report(C.Structure):
+    _fields_ = [("verdict", C.c_uint32), ("failed", C.c_uint32), ("lagrange_failed", C.c_uint32 * 4), ("bad_section", C.c_uint32),
+                ("bad_kind", C.c_uint32), ("bad_index", C.c_uint64)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -146,9 +159,11 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_groth16_setup_sizes", "zk_groth16_setup",
            "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare",
            "zk_g1_scale", "zk_g1_scale_plan", "zk_zkey_contribute_sizes", "zk_zkey_contribute",
-           "zk_pairing", "zk_vkey_create", "zk_vkey_destroy", "zk_vkey_verify"]
+           "zk_pairing", "zk_vkey_create", "zk_vkey_destroy", "zk_vkey_verify",
+           "zk_g2_in_subgroup", "zk_g1_power_msm", "zk_g2_power_msm", "zk_fr_power_dft", "zk_ptau_check_sizes", "zk_ptau_check"]
 ZK_SCALE_PLAN_MAX = 130
 ZK_VERIFY_OK, ZK_VERIFY_INVALID, ZK_VERIFY_MALFORMED = 0, 1, 2
+ZK_PTAU_OK, ZK_PTAU_INVALID, ZK_PTAU_MALFORMED = 0, 1, 2
 
 
 def load_library():
@@ -249,6 +264,13 @@ def load_library():
         lib.zk_vkey_destroy.argtypes = [C.c_void_p]
         lib.zk_vkey_destroy.restype = None
         lib.zk_vkey_verify.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p]
+    if hasattr(lib, "zk_ptau_check"):
+        lib.zk_g2_in_subgroup.argtypes = [u8p, u8p, C.c_uint64, C.c_int32]
+        lib.zk_g1_power_msm.argtypes = [u8p, u8p, C.c_uint64, u8p, C.c_uint64, C.c_int32]
+        lib.zk_g2_power_msm.argtypes = [u8p, u8p, C.c_uint64, u8p, C.c_uint64, C.c_int32]
+        lib.zk_fr_power_dft.argtypes = [u8p, u8p, C.c_uint32, C.c_int32]
+        lib.zk_ptau_check_sizes.argtypes = [C.POINTER(zk_ptau_file_view), C.POINTER(zk_ptau_check_sizes_t)]
+        lib.zk_ptau_check.argtypes = [C.POINTER(zk_ptau_file_view), u8p, C.c_int32, C.POINTER(zk_ptau_report)]
     _LIB = lib
     return lib
 
@@ -465,6 +487,54 @@ def g1_scale_plan(k):
     kk = _scalar32(k)
     check(load_library().zk_g1_scale_plan(_ptr(kk), a, b, ZK_SCALE_PLAN_MAX, C.byref(n)))
     return list(a[:n.value]), list(b[:n.value])
+
+
+def _need(name):
+    fn = getattr(load_library(), name, None)
+    if fn is None:
+        raise ZkHipError("%s is not in this build of libzkhip.so" % name)
+    return fn
+
+
+def g2_in_subgroup(points, device=-1):
+    """zk_g2_in_subgroup: n x 128 B affine Montgomery G2 points -> numpy uint8 [n], 1 = in the order-r subgroup of the twist
+    (infinity: 1), 0 = on the twist but outside.  Raises ZkHipError naming the index of a point that is not on the twist."""
+    pts = _buf(points)
+    if pts.size % 128:
+        raise ValueError("points: a multiple of 128 bytes expected")
+    out = np.zeros(pts.size // 128, dtype=np.uint8)
+    check(_need("zk_g2_in_subgroup")(_ptr(out) if out.size else None, _ptr(pts) if pts.size else None, out.size, device))
+    return out
+
+
+def _power_msm(name, nb, points, s, first_exp, device):
+    pts = _buf(points)
+    if pts.size % nb:
+        raise ValueError("points: a multiple of %d bytes expected" % nb)
+    out = np.zeros(nb, dtype=np.uint8)
+    ss = _scalar32(s)
+    check(_need(name)(_ptr(out), _ptr(pts) if pts.size else None, pts.size // nb, _ptr(ss), first_exp, device))
+    return out.tobytes()
+
+
+def g1_power_msm(points, s, first_exp=0, device=-1):
+    """sum_i s^(first_exp + i) P_i over n x 64 B affine Montgomery G1 points (zk_g1_power_msm) -> 64 bytes, affine.  The
+    scalars are made on the device.  s: int below r."""
+    return _power_msm("zk_g1_power_msm", 64, points, s, first_exp, device)
+
+
+def g2_power_msm(points, s, first_exp=0, device=-1):
+    return _power_msm("zk_g2_power_msm", 128, points, s, first_exp, device)
+
+
+def fr_power_dft(s, log_n, device=-1):
+    """[sum_(i < 2^log_n) s^i w^(ij) for j < 2^log_n] (zk_fr_power_dft): the forward DFT of the powers of s, a list of ints,
+    w the root of unity of fr_ntt."""
+    out = np.zeros(32 << log_n, dtype=np.uint8)
+    ss = _scalar32(s)
+    check(_need("zk_fr_power_dft")(_ptr(out), _ptr(ss), log_n, device))
+    raw = out.tobytes()
+    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
 
 
 def g1_mul(p, k):

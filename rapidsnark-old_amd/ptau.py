@@ -125,6 +125,18 @@ class PtauFile:
                 setattr(v, name + "_bytes", s.size)
         return v
 
+    def file_view(self):
+        """-> zk_ptau_file_view (sections 2 to 6 and 12 to 15 as pointers into this object's memory).  A missing section
+        stays NULL: the library names it."""
+        v = L.zk_ptau_file_view()
+        v.power = self.power
+        for sid in (2, 3, 4, 5, 6) + LAGRANGE:
+            if sid in self.sections:
+                s = self.section(sid)
+                v.sec[sid] = s.ctypes.data if s.size else None
+                v.sec_bytes[sid] = s.size
+        return v
+
     def close(self):
         self.raw = None
         if self._map is not None:
@@ -226,6 +238,58 @@ def prepare_phase2(src, dst, device=-1):
     finally:
         if own:
             pf.close()
+
+
+# ---------------------------------------------------------------- is the file sound
+class PtauReport:
+    """What zk_ptau_check found.  ok; verdict (0 OK, 1 INVALID, 2 MALFORMED); failed: the set of section ids (2 .. 6) whose
+    equation failed, 0 for a generator; lagrange_failed: {12 .. 15: set of levels}; for a malformed point bad_section,
+    bad_index and bad_kind (1 coordinate >= q, 2 off the curve, 3 not in the subgroup, 4 infinity)."""
+
+    def __init__(self, rep, prepared):
+        self.verdict = int(rep.verdict)
+        self.ok = self.verdict == L.ZK_PTAU_OK
+        self.prepared = bool(prepared)
+        self.failed = {k for k in range(32) if rep.failed >> k & 1}
+        self.lagrange_failed = {sid: {p for p in range(32) if rep.lagrange_failed[i] >> p & 1} for i, sid in enumerate(LAGRANGE)}
+        self.bad_section, self.bad_index, self.bad_kind = int(rep.bad_section), int(rep.bad_index), int(rep.bad_kind)
+
+    def __repr__(self):
+        return "PtauReport(verdict=%d, failed=%r, lagrange_failed=%r, bad=(%d, %d, %d))" % (
+            self.verdict, sorted(self.failed), {k: sorted(v) for k, v in self.lagrange_failed.items() if v},
+            self.bad_section, self.bad_index, self.bad_kind)
+
+
+def ptau_check_sizes(ptau):
+    """-> zk_ptau_check_sizes as a dict (prepared, chunk_points, device_bytes); raises ZkHipError with the library's message
+    (unsupported power, missing or short section, some but not all of sections 12 to 15).  No device is touched."""
+    pf, own = _open_ptau(ptau)
+    try:
+        fv = pf.file_view()
+        z = L.zk_ptau_check_sizes_t()
+        L.check(L.load_library().zk_ptau_check_sizes(C.byref(fv), C.byref(z)))
+    finally:
+        if own:
+            pf.close()
+    return {name: int(getattr(z, name)) for name, _ in L.zk_ptau_check_sizes_t._fields_}
+
+
+def ptau_check(ptau, s=None, device=-1):
+    """Is the .ptau (path, bytes or PtauFile) sound: zk_ptau_check on the GPU -> PtauReport.  s: the scalar of the random
+    combination, drawn by the library when None (a fixed one is for tests).  The contribution transcript is not checked."""
+    lib = L.load_library()
+    pf, own = _open_ptau(ptau)
+    try:
+        fv = pf.file_view()
+        z = L.zk_ptau_check_sizes_t()
+        L.check(lib.zk_ptau_check_sizes(C.byref(fv), C.byref(z)))
+        rep = L.zk_ptau_report()
+        ss = L._scalar32(s) if s is not None else None
+        L.check(lib.zk_ptau_check(C.byref(fv), L._ptr(ss) if ss is not None else None, device, C.byref(rep)))
+    finally:
+        if own:
+            pf.close()
+    return PtauReport(rep, z.prepared)
 
 
 # ---------------------------------------------------------------- the setup
