@@ -545,6 +545,76 @@ int zk_ptau_check_sizes(const zk_ptau_file_view *ptau, zk_ptau_check_sizes_t *si
  * value tells only whether the call ran. */
 int zk_ptau_check(const zk_ptau_file_view *ptau, const uint8_t *s32, int32_t device, zk_ptau_report *report);
 
+/* ---- Is this .zkey the key of this circuit over this Powers of Tau file ------------------ */
+/* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
+ * counterpart is the arithmetic half of snarkjs `zkey verify circuit.r1cs pot.ptau circuit.zkey`.  Section 10 of the key
+ * (the contribution transcript) is NOT read: a key that passes is the circuit's key over this .ptau for SOME delta; that
+ * anybody honest contributed to that delta is not shown.  No second key is made: with one scalar s, p_w = s^w over the
+ * wires, and a = A'.p, b = B.p, c = C.p (row sums over the domain; A' = A plus the public-input rows), the sum
+ * sum_w s^w (key point of wire w) of every section equals a multi-scalar multiplication of a Lagrange level of the .ptau by
+ * a, b or c.  Every item is a polynomial identity in s of degree < 2^29: a wrong key passes one with probability < 2^29 / r.
+ * zk_zkey_verify_view: the prover's view of the key plus what it does not read, gamma2 and section 3 (IC). */
+typedef struct zk_zkey_verify_view {
+    zk_zkey_view key;
+    const void *vk_gamma2;                  /* G2, section 2 */
+    const void *pointsIC;                   /* section 3: (nPublic + 1) x G1 */
+    uint64_t pointsIC_bytes;
+} zk_zkey_verify_view;
+/* the named items: bits of `failed` and `not_checked` */
+enum {
+    ZK_ZV_ALPHA1 = 0, ZK_ZV_BETA1, ZK_ZV_BETA2,   /* section 2 equals alphaTauG1[0], betaTauG1[0], betaG2 of the .ptau (bytes) */
+    ZK_ZV_GAMMA2,                                 /* gamma2 is the G2 generator, what snarkjs writes */
+    ZK_ZV_DELTA,                                  /* e(delta1, G2) e(-G1, delta2) = 1 */
+    ZK_ZV_COEFS,                                  /* section 4 against the circuit (zk_r1cs_match_zkey) */
+    ZK_ZV_A, ZK_ZV_B1, ZK_ZV_B2,                  /* sum s^w A_w = MSM(T12, a); B1: (T12, b); B2: (T13, b) in G2 */
+    ZK_ZV_IC,                                     /* sum_(w <= nPublic) s^w IC_w = MSM(T15, a_pub) + MSM(T14, b_pub) + MSM(T12, c_pub) */
+    ZK_ZV_C,                                      /* e(sum_(w > nPublic) s^w C_w, delta2) e(-K_priv, G2) = 1 */
+    ZK_ZV_H,                                      /* e(sum s^i H_i, delta2) e(-sum s^i T12'[2i + 1], G2) = 1 */
+    ZK_ZV_ITEMS
+};
+/* the shapes of the three files that must agree: bits of `shape_failed` */
+enum { ZK_ZV_SHAPE_NVARS = 0, ZK_ZV_SHAPE_NPUBLIC, ZK_ZV_SHAPE_DOMAIN, ZK_ZV_SHAPE_PTAU_UNPREPARED, ZK_ZV_SHAPE_PTAU_POWER };
+typedef struct zk_zkey_verify_sizes_t {
+    uint32_t log_domain;          /* k: the key's domain is 2^k; when that cannot hold the circuit (shape_failed), the smallest
+                                   * k >= 1 with 2^k >= nConstraints + nPublic + 1 */
+    uint32_t shape_failed;        /* what zk_zkey_verify would report without touching a device; 0: the files fit */
+    uint64_t chunk_points;        /* points per chunk in effect (ZKHIP_ZKEY_VERIFY_CHUNK, 2^22 otherwise) */
+    uint64_t device_bytes;        /* an upper estimate of the HBM the check holds */
+} zk_zkey_verify_sizes_t;
+/* Set rep->size = sizeof(zk_zkey_verify_report) before the call (only `size` bytes are written). */
+typedef struct zk_zkey_verify_report {
+    uint32_t size;
+    uint32_t verdict;             /* 0 OK, 1 INVALID, 2 MALFORMED */
+    uint32_t failed;              /* bit ZK_ZV_*: the item does not hold */
+    uint32_t not_checked;         /* bit ZK_ZV_C, ZK_ZV_H: not evaluated because delta failed */
+    uint32_t shape_failed;        /* bit ZK_ZV_SHAPE_*: the files do not fit each other (verdict 1, nothing else evaluated) */
+    uint32_t bad_section;         /* MALFORMED: the lowest-numbered section of the key (2, 3, 5 .. 9) with a bad point, */
+    uint32_t bad_kind;            /*   its kind (1 coordinate >= q, 2 off curve, 3 not in subgroup, 4 infinity) */
+    uint64_t bad_index;           /*   and its lowest index (section 2: alpha1, beta1, beta2, gamma2, delta1, delta2 = 0 .. 5) */
+    uint64_t coef_rows_differing; /* rows of A and B in which section 4 and the circuit differ */
+    uint32_t coef_first_row;      /* the lowest such row; UINT32_MAX: none */
+    uint32_t delta_is_generator;  /* delta2 is the G2 generator: a phase-2 starting key, not safe to prove with */
+} zk_zkey_verify_report;
+/* Checks the three views against each other without touching a device.  Errors: a null section, a section shorter than
+ * the key's header implies, a .r1cs section that does not walk, a Lagrange section shorter than the .ptau's power needs, a
+ * domain above 2^27.  Shapes that disagree between well-formed files (nVars, nPublic, a domain that is no power of two or
+ * below nConstraints + nPublic + 1, a .ptau that is not prepared or of a power below k) are no error: they are reported in
+ * shape_failed.  device_bytes: the term arrays of the
+ * circuit (zk_r1cs_create and zk_r1cs_match_zkey), the masked powers, six Fr vectors over the domain, levels k of
+ * sections 12 to 15 and level k + 1 of section 12, and two chunked multiplication engines (G1 and G2). */
+int zk_zkey_verify_sizes(const zk_r1cs_view *r1cs, const zk_ptau_view *ptau, const zk_zkey_verify_view *zkey, zk_zkey_verify_sizes_t *sizes);
+/* The check.  s32: the scalar (2 <= s < r), NULL: drawn from getrandom() after the views are given, which is what makes
+ * the check sound; a fixed one is for tests.  First every point of the key's sections 2, 3 and 5 to 9 is checked as
+ * zk_ptau_check checks a file's: coordinates below q, on the curve or twist, the G2 points of section 7 and beta2, gamma2,
+ * delta2 in the subgroup (ZKHIP_SUBGROUP_PLAIN honoured); infinity is legal in sections 3 and 5 to 9 and not in section 2.
+ * A bad point gives MALFORMED and no equation is evaluated.  Then every item of ZK_ZV_* is evaluated and every one that
+ * fails is reported; when delta fails, C and H are reported in not_checked.  The .ptau's own levels are taken on trust
+ * (zk_ptau_check answers for them).  Key sections go through the device in chunks on the engines of zk_ptau_check; chunk
+ * sums are added on the host.  Free HBM is checked against zk_zkey_verify_sizes' estimate before anything is allocated.
+ * The return value tells only whether the call ran. */
+int zk_zkey_verify(const zk_r1cs_view *r1cs, const zk_ptau_view *ptau, const zk_zkey_verify_view *zkey, const uint8_t *s32, int32_t device,
+                   zk_zkey_verify_report *report);
+
 #ifdef __cplusplus
 }
 #endif

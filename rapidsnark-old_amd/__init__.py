@@ -16,6 +16,7 @@ from .lib import (ZkHipError, load_library, library_path, fr_mul_vec, fq_mul_vec
 from .prover import Prover, MultiProver, prove_files                 # noqa: F401
 from .r1cs import R1cs, R1csReport, write_r1cs                      # noqa: F401
 from .ptau import PtauFile, PtauReport, groth16_setup, prepare_phase2, ptau_check, ptau_check_sizes, write_trapdoor_ptau      # noqa: F401
+from .zkverify import ZkeyVerifyReport, zkey_verify, zkey_verify_sizes      # noqa: F401
 from .verify import VerificationKey, pairing, groth16_verify, load_proof, load_public      # noqa: F401
 from . import synth                                     # noqa: F401
 from .dist import gather_partials, ShardedChain                        # noqa: F401

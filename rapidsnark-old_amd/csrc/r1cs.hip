@@ -24,6 +24,7 @@
 #include <sys/random.h>
 #include <mutex>
 #include "r1cs_section.hpp"
+#include "r1cs_internal.hpp"
 #include "field29.hpp"
 #include "devmem.hpp"
 
@@ -256,6 +257,11 @@ void walk_constraints(const zk_r1cs_view *v, std::vector<uint64_t> &lc_off, std:
     if (pos != size) throw std::invalid_argument("r1cs constraints section is longer than its constraints");
     rowptr.assign(3 * m + 1, 0);
     for (uint64_t r = 0; r < 3 * m; r++) rowptr[r + 1] = rowptr[r] + len[r];
+}
+
+R1csDev r1cs_dev(zk_r1cs *r) { return R1csDev{r->device, r->stream, r->nWires, r->nPublic, r->m, r->nnz, r->rows.p}; }
+void r1cs_spmv(zk_r1cs *r, const Fr *x) {
+    if (r->m) r->spmv(x);
 }
 
 // Segments of every pass (host, create time).  Pass 0's input is the terms of all rows in order; a row of L inputs

@@ -118,6 +118,20 @@ class zk_ptau_report(C.Structure):
                 ("bad_kind", C.c_uint32), ("bad_index", C.c_uint64)]
 
 
+class zk_zkey_verify_view(C.Structure):
+    _fields_ = [("key", zk_zkey_view), ("vk_gamma2", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsIC_bytes", C.c_uint64)]
+
+
+class zk_zkey_verify_sizes_t(C.Structure):
+    _fields_ = [("log_domain", C.c_uint32), ("shape_failed", C.c_uint32), ("chunk_points", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class zk_zkey_verify_report(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("verdict", C.c_uint32), ("failed", C.c_uint32), ("not_checked", C.c_uint32), ("shape_failed", C.c_uint32),
+                ("bad_section", C.c_uint32), ("bad_kind", C.c_uint32), ("bad_index", C.c_uint64), ("coef_rows_differing", C.c_uint64),
+                ("coef_first_row", C.c_uint32), ("delta_is_generator", C.c_uint32)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -160,7 +174,8 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare",
            "zk_g1_scale", "zk_g1_scale_plan", "zk_zkey_contribute_sizes", "zk_zkey_contribute",
            "zk_pairing", "zk_vkey_create", "zk_vkey_destroy", "zk_vkey_verify",
-           "zk_g2_in_subgroup", "zk_g1_power_msm", "zk_g2_power_msm", "zk_fr_power_dft", "zk_ptau_check_sizes", "zk_ptau_check"]
+           "zk_g2_in_subgroup", "zk_g1_power_msm", "zk_g2_power_msm", "zk_fr_power_dft", "zk_ptau_check_sizes", "zk_ptau_check",
+           "zk_zkey_verify_sizes", "zk_zkey_verify"]
 ZK_SCALE_PLAN_MAX = 130
 ZK_VERIFY_OK, ZK_VERIFY_INVALID, ZK_VERIFY_MALFORMED = 0, 1, 2
 ZK_PTAU_OK, ZK_PTAU_INVALID, ZK_PTAU_MALFORMED = 0, 1, 2
@@ -271,6 +286,11 @@ def load_library():
         lib.zk_fr_power_dft.argtypes = [u8p, u8p, C.c_uint32, C.c_int32]
         lib.zk_ptau_check_sizes.argtypes = [C.POINTER(zk_ptau_file_view), C.POINTER(zk_ptau_check_sizes_t)]
         lib.zk_ptau_check.argtypes = [C.POINTER(zk_ptau_file_view), u8p, C.c_int32, C.POINTER(zk_ptau_report)]
+    if hasattr(lib, "zk_zkey_verify"):
+        lib.zk_zkey_verify_sizes.argtypes = [C.POINTER(zk_r1cs_view), C.POINTER(zk_ptau_view), C.POINTER(zk_zkey_verify_view),
+                                             C.POINTER(zk_zkey_verify_sizes_t)]
+        lib.zk_zkey_verify.argtypes = [C.POINTER(zk_r1cs_view), C.POINTER(zk_ptau_view), C.POINTER(zk_zkey_verify_view), u8p, C.c_int32,
+                                       C.POINTER(zk_zkey_verify_report)]
     _LIB = lib
     return lib
 
