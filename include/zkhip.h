@@ -174,6 +174,12 @@ typedef struct zk_prover_plan {
     uint64_t kernel_launches_last_proof;   /* kernel launches the most recently submitted proof took (0 before the first; a graph replay counts as none) */
     uint32_t table_rows_h, table_rows_w;   /* rows of n points per table (x the zkey's table memory): windows_* with ZK_FLAG_PRECOMP, ceil(windows_* / 2) with _HALF, else 1 */
     uint32_t bucket_sets_h, bucket_sets_w; /* bucket sets (= bucket reductions) per MSM: 1 with ZK_FLAG_PRECOMP, 2 with _HALF, windows_* with plain tables */
+    /* A.w / B.w (src/groth16.cpp:62-85): rows of more than spmv_row_cut terms are summed chunk by chunk, a wave each, instead
+     * of by the row's one lane.  A sharded prover counts the rows it computes. */
+    uint32_t spmv_row_cut;                 /* the cut in effect (ZKHIP_SPMV_ROW_CUT at create, else the built-in one; 0: no row is long) */
+    uint32_t spmv_long_rows;               /* local rows of A and B above it */
+    uint32_t spmv_longest_row;             /* terms of the longest local row */
+    uint32_t spmv_chunks;                  /* chunks of up to 1024 terms the long rows make; 0 = the lane-per-row kernel alone */
 } zk_prover_plan;
 int zk_prover_info(zk_prover *p, zk_prover_plan *plan);
 int zk_prove_msm_collect(zk_prover *p, zk_msm_sums *partial);
@@ -218,6 +224,9 @@ int zk_multi_prove(zk_multi_prover *mp, const uint8_t *wtns, const uint8_t *r32,
 int zk_multi_prove_submit(zk_multi_prover *mp, const uint8_t *wtns, const uint8_t *r32, const uint8_t *s32);
 int zk_multi_prove_collect(zk_multi_prover *mp, zk_proof *out);
 int zk_multi_prover_info(zk_multi_prover *mp, uint32_t *n_shards, uint32_t *chain_partitioned);
+/* zk_prover_info of shard `shard` (< n_shards): with a partitioned chain every shard holds its own block of rows, so the
+ * spmv_* fields differ from shard to shard. */
+int zk_multi_prover_shard_info(zk_multi_prover *mp, uint32_t shard, zk_prover_plan *plan);
 /* (b) One process per GPU (torch.distributed over RCCL): a prover created with shard_index/shard_count and
  *     ZK_FLAG_PARTITIONED_CHAIN is driven step by step, and the CALLER moves the blocks between the steps
  *     with FOUR all_to_all_single per proof on two buffers it owns and registers here (3 polynomials x

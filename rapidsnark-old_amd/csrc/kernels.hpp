@@ -18,17 +18,30 @@ struct CsrDev {
     const uint32_t *rowptr;   // 2n+1
     const uint32_t *col;      // nnz: signal index s
     const Fr *val;            // nnz: coefficient (value*R^2 as stored in the zkey)
+    // rows of more than `cut` terms (csr_long.hpp fills these in; chunks == 0: the key has none and nothing below is read)
+    const uint4 *chunk_desc = nullptr;   // chunks x {row, first term, terms, partial slot}; a row's slots are contiguous
+    const uint4 *long_desc = nullptr;    // long_rows x {row, first partial slot, partials, first term}
+    uint32_t chunks = 0, long_rows = 0, cut = 0;
 };
+constexpr uint32_t SPMV_LANE_TERMS = 16;        // terms per lane of a chunk's wave (r1cs_section.hpp's SEG_TERMS): chunks of 1024
+constexpr uint32_t SPMV_ROW_CUT = 16;           // rows above this many terms are long unless ZKHIP_SPMV_ROW_CUT says otherwise (the sweep of profiles/spmv_timing.txt)
+uint32_t spmv_row_cut();                        // the cut in effect: the environment's, else SPMV_ROW_CUT; 0 = no row is long
+// csr.chunks == 0: one launch of k_spmv_abc, as ever.  Otherwise three launches (fieldops.hip) and `partials`, vectors x
+// csr.chunks elements that belong to this call alone (a proof slot's), is written.
 void launch_spmv_abc(Fr *a, Fr *b, Fr *c, CsrDev csr, const Fr *wtns, uint32_t n, hipStream_t s, uint32_t vectors = 1, uint64_t abc_stride = 0,
-                     uint64_t wtns_stride = 0);     // vectors > 1: a batched submission, vector v at + v * stride
+                     uint64_t wtns_stride = 0, Fr *partials = nullptr);     // vectors > 1: a batched submission, vector v at + v * stride
 // Row-sorted CSR from the zkey's coefficient records (section 4 after its u32 count: 44-byte packed
 // {u32 matrix, u32 row, u32 signal, 32-byte value}, src/groth16.hpp:27-35), built on the device.
 // rowptr: 2n + 1 words + msm_scan_extra_words(2n) of scan scratch; cursor: 2n words of scratch;
-// err: one word, set non-zero when a record is out of range (matrix > 1, row >= n, signal >= nVars).
+// err: four words.  [0] is set non-zero when a record is out of range (matrix > 1, row >= n, signal >= nVars); [1] = rows of
+// more than row_cut terms (row_cut 0: none), [2] = the chunks of SPMV_CHUNK terms they make, [3] = the longest row.
 // Only the rows [row_lo, row_hi) of both matrices are kept (local row = row - row_lo; rowptr/cursor then
 // hold 2 * (row_hi - row_lo) rows); the range check covers every record.
 void launch_csr_build(uint32_t *rowptr, uint32_t *col, Fr *val, uint32_t *cursor, uint32_t *err, const uint8_t *records,
-                      uint64_t nCoefs, uint32_t n, uint32_t nVars, uint32_t row_lo, uint32_t row_hi, hipStream_t s);
+                      uint64_t nCoefs, uint32_t n, uint32_t nVars, uint32_t row_lo, uint32_t row_hi, uint32_t row_cut, hipStream_t s);
+// the long rows' list and chunk descriptors (CsrDev), from the counts launch_csr_build reported; counters: two words of scratch
+void launch_csr_long_rows(uint4 *long_desc, uint4 *chunk_desc, uint32_t *counters, const uint32_t *rowptr, uint32_t rows, uint32_t row_cut,
+                          uint32_t long_rows, uint32_t chunks, hipStream_t s);
 // exclusive scan (msm_sort.hip): out[i] = sum counts[0..i), out[total] = grand total; out holds total + 1 + msm_scan_extra_words(total) words
 void launch_exclusive_scan_u32(uint32_t *out, const uint32_t *counts, uint32_t total, hipStream_t s);
 

@@ -5,6 +5,7 @@
 #include <memory>
 #include <mutex>
 #include "hiputil.hpp"
+#include "csr_long.hpp"
 
 static void need_device() { need_device_count(); }
 
@@ -62,7 +63,7 @@ int zk_fr_coef_accumulate(uint8_t *a, uint8_t *b, const void *coefs, uint64_t nC
         DevBuf<Fr> val, w, ab;
         raw.alloc(nCoefs ? nCoefs * 44 : 4);
         cursor.alloc(rows);
-        err.alloc(1);
+        err.alloc(4);
         rowptr.alloc((size_t)rows + 1 + msm_scan_extra_words(rows));
         col.alloc(nCoefs ? nCoefs : 1);
         val.alloc(nCoefs ? nCoefs : 1);
@@ -70,13 +71,18 @@ int zk_fr_coef_accumulate(uint8_t *a, uint8_t *b, const void *coefs, uint64_t nC
         ab.alloc(3 * (size_t)domainSize);
         if (nCoefs) HIP_TRY(hipMemcpy(raw.p, (const uint8_t *)coefs + 4, nCoefs * 44, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(w.p, wtns, (size_t)nVars * 32, hipMemcpyHostToDevice));
-        launch_csr_build(rowptr.p, col.p, val.p, cursor.p, err.p, raw.p, nCoefs, domainSize, nVars, 0, domainSize, 0);
+        const uint32_t row_cut = spmv_row_cut();
+        launch_csr_build(rowptr.p, col.p, val.p, cursor.p, err.p, raw.p, nCoefs, domainSize, nVars, 0, domainSize, row_cut, 0);
         launch_fr_to_internal(val.p, nCoefs, 2, 0);
-        uint32_t bad = 0;
-        HIP_TRY(hipMemcpy(&bad, err.p, 4, hipMemcpyDeviceToHost));
-        if (bad) throw std::invalid_argument("zkey coefficient record out of range");
-        CsrDev csr{rowptr.p, col.p, val.p};
-        launch_spmv_abc(ab.p, ab.p + domainSize, ab.p + 2 * (size_t)domainSize, csr, w.p, domainSize, 0);
+        uint32_t bad[4] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpy(bad, err.p, 16, hipMemcpyDeviceToHost));
+        if (bad[0]) throw std::invalid_argument("zkey coefficient record out of range");
+        CsrLong lr;                    // rows above the cut (the transposed records of zkgen: the constant wire's row)
+        DevBuf<Fr> part;
+        lr.build(rowptr.p, rows, row_cut, bad, 0);
+        if (lr.chunks) part.alloc(lr.chunks);
+        const CsrDev csr = lr.view(rowptr.p, col.p, val.p);
+        launch_spmv_abc(ab.p, ab.p + domainSize, ab.p + 2 * (size_t)domainSize, csr, w.p, domainSize, 0, 1, 0, 0, part.p);
         launch_fr_from_internal(ab.p, 2 * (size_t)domainSize, 0);
         HIP_TRY(hipMemcpy(a, ab.p, (size_t)domainSize * 32, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(b, ab.p + domainSize, (size_t)domainSize * 32, hipMemcpyDeviceToHost));

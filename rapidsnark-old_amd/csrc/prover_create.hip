@@ -39,6 +39,7 @@ void alloc_slot(zk_prover *p, int i) {
     q.acc_ws_g2.alloc(slots);
     q.acc_key_all.alloc(4 * slots + slots_h);
     q.acc_flag_all.alloc(4 * slots + slots_h);
+    if (p->csr_long.chunks) q.spmv_part.alloc((uint64_t)p->csr_long.chunks * p->batch);
     for (int m = 0; m < 5; m++) {          // A, B1, C at m*slots; H behind them; B2 last
         const uint64_t at = m < 3 ? m * slots : (m == 3 ? 3 * slots : 3 * slots + slots_h);
         if (m < 4) q.acc_ws_g1[m] = q.acc_ws_g1_all.p + at;
@@ -238,24 +239,25 @@ void prover_create(zk_prover **out, const zk_zkey_view *z, const zk_opts *o) {
     // a partitioned prover keeps the rows of its own block only
     {
         const uint64_t nnz = z->nCoefs;
-        const uint32_t rows = 2 * (uint32_t)p->nloc;
+        const uint32_t rows = 2 * (uint32_t)p->nloc, row_cut = spmv_row_cut();
         DevBuf<uint8_t> raw;
         DevBuf<uint32_t> cursor, err;
         raw.alloc(nnz ? nnz * 44 : 4);
         cursor.alloc(rows);
-        err.alloc(1);
+        err.alloc(4);
         p->csr_rowptr.alloc((size_t)rows + 1 + msm_scan_extra_words(rows));
         p->csr_col.alloc(nnz ? nnz : 1);
         p->csr_val.alloc(nnz ? nnz : 1);
         if (nnz) up.copy(raw.p, (const uint8_t *)z->coefs + 4, nnz * 44);
         clk.lap("coefficient records upload", s);
         launch_csr_build(p->csr_rowptr.p, p->csr_col.p, p->csr_val.p, cursor.p, err.p, raw.p, nnz, z->domainSize, z->nVars,
-                         p->part ? (uint32_t)p->sh.lo : 0u, p->part ? (uint32_t)p->sh.hi : z->domainSize, s);
+                         p->part ? (uint32_t)p->sh.lo : 0u, p->part ? (uint32_t)p->sh.hi : z->domainSize, row_cut, s);
         launch_fr_to_internal(p->csr_val.p, nnz, 2, s);      // value*2^512 -> value*2^522 (see k_spmv_abc); unused tail entries are zero
-        uint32_t bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, err.p, 4, hipMemcpyDeviceToHost, s));
+        uint32_t bad[4] = {0, 0, 0, 0};      // + the long rows among the local rows, their chunks, the longest row
+        HIP_TRY(hipMemcpyAsync(bad, err.p, 16, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (bad) throw std::invalid_argument("zkey coefficient record out of range");
+        if (bad[0]) throw std::invalid_argument("zkey coefficient record out of range");
+        p->csr_long.build(p->csr_rowptr.p, rows, row_cut, bad, s);
         clk.lap("CSR build (device)", s);
     }
 
@@ -497,6 +499,8 @@ int zk_prover_info(zk_prover *p, zk_prover_plan *plan) {
             o.device_bytes_in_use = tot - fr; o.device_bytes_total = tot;
         }
         o.kernel_launches_last_proof = p->launches_last_proof;
+        o.spmv_row_cut = p->csr_long.cut; o.spmv_long_rows = p->csr_long.long_rows;
+        o.spmv_longest_row = p->csr_long.longest; o.spmv_chunks = p->csr_long.chunks;
         const uint32_t nb = plan->size < sizeof o ? plan->size : (uint32_t)sizeof o;
         o.size = nb;
         memcpy(plan, &o, nb);

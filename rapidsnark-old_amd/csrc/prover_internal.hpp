@@ -34,6 +34,7 @@
 #include "hipcheck.hpp"
 #include "kernels.hpp"
 #include "hiputil.hpp"
+#include "csr_long.hpp"
 #include "tail_pool.hpp"
 
 namespace zkp {
@@ -77,6 +78,7 @@ struct zk_prover {
     // resident data
     DevBuf<uint32_t> csr_rowptr, csr_col;
     DevBuf<Fr> csr_val;
+    CsrLong csr_long;          // the local rows above the long-row cut and their chunk descriptors (csr_long.hpp); none: chunks == 0
     DevBuf<TwEntry> tw_fwd, tw_inv;
     DevBuf<Fr> tw_coset, tw_ninv;
     NttPair pair;               // nttpair.hip: tables of the coset-evaluation pipeline for this prover's block (pair.L == 0: not used)
@@ -122,6 +124,7 @@ struct zk_prover {
         // pinned staging copy a pageable caller buffer goes through.  One per slot, so that proof
         // k+1's upload runs (on its own stream) while proof k is still computing.
         DevBuf<Fr> wtns_dev;              // batch x nVars
+        DevBuf<Fr> spmv_part;             // batch x csr_long.chunks partial sums of the long rows (a key without long rows: not allocated)
         uint8_t *wtns_pin = nullptr;
         uint8_t *pin_ring = nullptr;          // two upload pieces of pinned memory: the staging of a lone proof on a slot that has no wtns_pin yet
         StageJob stage[ZK_MAX_BATCH];
@@ -142,7 +145,7 @@ struct zk_prover {
         // HBM of the slot's proof workspace (the witness buffer aside), as alloc_slot made it
         size_t device_bytes() const {
             return sort_w.bytes() + buckets_g1.bytes() + buckets_g2.bytes() + scratch_g1.bytes() + acc_ws_g1_all.bytes() + acc_key_all.bytes()
-                 + acc_flag_all.bytes() + scratch_g2.bytes() + acc_ws_g2.bytes() + wsum_g1.bytes() + wsum_g2.bytes();
+                 + acc_flag_all.bytes() + scratch_g2.bytes() + acc_ws_g2.bytes() + wsum_g1.bytes() + wsum_g2.bytes() + spmv_part.bytes();
         }
         // Give the slot's device and pinned memory back (events stay).  Only for a slot no proof is using: zk_prover_reserve
         // does this to the slots beyond a ring that a failed, deeper reservation left allocated.
@@ -151,7 +154,7 @@ struct zk_prover {
             sort_w.release();
             buckets_g1.release(); buckets_g2.release(); scratch_g1.release(); acc_ws_g1_all.release();
             acc_key_all.release(); acc_flag_all.release(); scratch_g2.release(); acc_ws_g2.release();
-            wsum_g1.release(); wsum_g2.release(); wtns_dev.release();
+            wsum_g1.release(); wsum_g2.release(); wtns_dev.release(); spmv_part.release();
             if (w1) { (void)hipHostFree(w1); w1 = nullptr; }
             if (w2) { (void)hipHostFree(w2); w2 = nullptr; }
             if (wtns_pin) { (void)hipHostFree(wtns_pin); wtns_pin = nullptr; }

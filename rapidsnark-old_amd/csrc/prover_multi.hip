@@ -236,6 +236,11 @@ int zk_multi_prover_info(zk_multi_prover *mp, uint32_t *n_shards, uint32_t *chai
     });
 }
 
+int zk_multi_prover_shard_info(zk_multi_prover *mp, uint32_t shard, zk_prover_plan *plan) {
+    if (!mp || shard >= mp->shard.size()) return guarded([&] { throw std::invalid_argument("no such shard"); });
+    return zk_prover_info(mp->shard[shard], plan);
+}
+
 int zk_shard_info(zk_prover *p, uint64_t *block_elems, uint32_t *chain_partitioned) {
     return guarded([&] {
         if (!p) throw std::invalid_argument("null argument");

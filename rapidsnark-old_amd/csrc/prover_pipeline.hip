@@ -395,9 +395,10 @@ int phase_front(zk_prover *p, const Fr *d_wtns, const uint8_t *h_wtns, const uin
     // 1-3: a = A.w, b = B.w, c = a o b   (src/groth16.cpp:52-96) — on the rows this prover holds
     const uint64_t nl = p->nloc;
     Fr *abc = c.abc;
-    CsrDev csr{p->csr_rowptr.p, p->csr_col.p, p->csr_val.p};
-    // (a batch: vector v's a|b|c behind vector v-1's; unused vectors are skipped)
-    launch_spmv_abc(abc, abc + nl, abc + 2 * nl, csr, d_wtns, (uint32_t)nl, s, q.count, 3 * nl, p->nVars);
+    const CsrDev csr = p->csr_long.view(p->csr_rowptr.p, p->csr_col.p, p->csr_val.p);
+    // (a batch: vector v's a|b|c behind vector v-1's; unused vectors are skipped.  A key with long rows: three launches, the
+    // partial sums in the slot's own buffer)
+    launch_spmv_abc(abc, abc + nl, abc + 2 * nl, csr, d_wtns, (uint32_t)nl, s, q.count, 3 * nl, p->nVars, q.spmv_part.p);
     c.mark(1);
     if (p->part && !p->have_peers && p->pk_use) launch_chunk_pack(p->pk_use, abc, 3, p->logn, p->log_shards, s);   // -> all_to_all #1
     p->phase_open = si;

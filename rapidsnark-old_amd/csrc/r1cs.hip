@@ -25,6 +25,7 @@
 #include <mutex>
 #include "r1cs_section.hpp"
 #include "r1cs_internal.hpp"
+#include "csr_long.hpp"
 #include "field29.hpp"
 #include "devmem.hpp"
 
@@ -392,7 +393,7 @@ void r1cs_match(zk_r1cs *r, const zk_zkey_view *z, uint64_t *rows_differing, uin
     const uint32_t rows = 2 * n;
     raw.alloc(nCoefs ? nCoefs * 44 : 4);
     cursor.alloc(rows);
-    err.alloc(1);
+    err.alloc(4);
     rowptr.alloc((size_t)rows + 1 + msm_scan_extra_words(rows));
     col.alloc(nCoefs ? nCoefs : 1);
     val.alloc(nCoefs ? nCoefs : 1);
@@ -401,21 +402,28 @@ void r1cs_match(zk_r1cs *r, const zk_zkey_view *z, uint64_t *rows_differing, uin
     StreamUploader up(r->stream);
     if (nCoefs) up.copy(raw.p, (const uint8_t *)z->coefs + 4, nCoefs * 44);
     HIP_TRY(hipMemcpyAsync(r->w.p, x.data(), x.size(), hipMemcpyHostToDevice, r->stream));
-    launch_csr_build(rowptr.p, col.p, val.p, cursor.p, err.p, raw.p, nCoefs, n, r->nWires, 0, n, r->stream);
+    const uint32_t row_cut = spmv_row_cut();
+    launch_csr_build(rowptr.p, col.p, val.p, cursor.p, err.p, raw.p, nCoefs, n, r->nWires, 0, n, row_cut, r->stream);
     launch_fr_to_internal(val.p, nCoefs, 2, r->stream);
-    CsrDev csr{rowptr.p, col.p, val.p};
-    launch_spmv_abc(ab.p, ab.p + n, ab.p + 2 * (size_t)n, csr, r->w.p, n, r->stream);
+    uint32_t bad[4] = {0, 0, 0, 0};       // the record check, and the key's long rows (fieldops.hip)
+    HIP_TRY(hipMemcpyAsync(bad, err.p, 16, hipMemcpyDeviceToHost, r->stream));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (bad[0]) throw std::invalid_argument("zkey coefficient record out of range");
+    CsrLong lr;
+    DevBuf<Fr> part;
+    lr.build(rowptr.p, rows, row_cut, bad, r->stream);
+    if (lr.chunks) part.alloc(lr.chunks);
+    const CsrDev csr = lr.view(rowptr.p, col.p, val.p);
+    launch_spmv_abc(ab.p, ab.p + n, ab.p + 2 * (size_t)n, csr, r->w.p, n, r->stream, 1, 0, 0, part.p);
     if (r->m) r->spmv(r->w.p);
     HIP_TRY(hipMemsetAsync(cnt.p, 0, 8, r->stream));
     HIP_TRY(hipMemsetAsync(cnt.p + 2, 0xFF, 4, r->stream));
     ZK_LAUNCH(k_r1cs_match, dim3(strided(n)), dim3(256), 0, r->stream, (unsigned long long *)cnt.p, cnt.p + 2, ab.p, r->rows.p, r->w.p, n, r->m,
               r->nPublic, r->k522);
     ZK_LAUNCH_OK("r1cs match");
-    uint32_t res[3], bad = 0;
+    uint32_t res[3];
     HIP_TRY(hipMemcpyAsync(res, cnt.p, 12, hipMemcpyDeviceToHost, r->stream));
-    HIP_TRY(hipMemcpyAsync(&bad, err.p, 4, hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    if (bad) throw std::invalid_argument("zkey coefficient record out of range");
     *rows_differing = (uint64_t)res[0] | ((uint64_t)res[1] << 32);
     *first_row = res[2];
 }

@@ -49,7 +49,8 @@ class zk_prover_plan(C.Structure):
                 ("depth_resident_witness", C.c_uint32), ("batch", C.c_uint32), ("shard_index", C.c_uint32), ("shard_count", C.c_uint32),
                 ("chain_partitioned", C.c_uint32), ("device_bytes_in_use", C.c_uint64), ("device_bytes_total", C.c_uint64),
                 ("kernel_launches_last_proof", C.c_uint64), ("table_rows_h", C.c_uint32), ("table_rows_w", C.c_uint32),
-                ("bucket_sets_h", C.c_uint32), ("bucket_sets_w", C.c_uint32)]
+                ("bucket_sets_h", C.c_uint32), ("bucket_sets_w", C.c_uint32),
+                ("spmv_row_cut", C.c_uint32), ("spmv_long_rows", C.c_uint32), ("spmv_longest_row", C.c_uint32), ("spmv_chunks", C.c_uint32)]
 
 
 class zk_r1cs_view(C.Structure):
@@ -138,10 +139,19 @@ class zk_setup_out(C.Structure):
 
 
 def prover_info(lib, handle):
-    """zk_prover_info -> dict: the launch plan zk_prover_create chose (window bits, A|B1|C in one launch, lanes, depths)."""
+    """zk_prover_info -> dict: the launch plan zk_prover_create chose (window bits, A|B1|C in one launch, lanes, depths,
+    the long-row cut of A.w / B.w and what it found: spmv_row_cut, spmv_long_rows, spmv_longest_row, spmv_chunks)."""
     plan = zk_prover_plan()
     plan.size = C.sizeof(zk_prover_plan)
     check(lib.zk_prover_info(handle, C.byref(plan)))
+    return {name: int(getattr(plan, name)) for name, _ in zk_prover_plan._fields_ if name != "size"}
+
+
+def multi_prover_shard_info(lib, handle, shard):
+    """zk_multi_prover_shard_info -> prover_info's dict for one shard of a zk_multi_prover"""
+    plan = zk_prover_plan()
+    plan.size = C.sizeof(zk_prover_plan)
+    check(lib.zk_multi_prover_shard_info(handle, shard, C.byref(plan)))
     return {name: int(getattr(plan, name)) for name, _ in zk_prover_plan._fields_ if name != "size"}
 
 
@@ -168,7 +178,7 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_fq_mul_vec", "zk_fr_coef_accumulate", "zk_fr_ntt", "zk_fr_abc_to_h", "zk_msm_g1", "zk_msm_g2", "zk_proof_to_json",
            "zk_public_to_json", "zk_synth_chain_g1", "zk_synth_chain_g2", "zk_fixed_base_g1", "zk_fixed_base_g2", "zk_g1_mul", "zk_g2_mul", "zk_assemble",
            "zk_multi_prover_create", "zk_multi_prover_destroy", "zk_multi_prove", "zk_multi_prove_submit", "zk_multi_prove_collect",
-           "zk_multi_prover_info", "zk_shard_info", "zk_shard_set_exchange", "zk_shard_begin", "zk_shard_step",
+           "zk_multi_prover_info", "zk_multi_prover_shard_info", "zk_shard_info", "zk_shard_set_exchange", "zk_shard_begin", "zk_shard_step",
            "zk_r1cs_create", "zk_r1cs_destroy", "zk_r1cs_check", "zk_r1cs_check_dev", "zk_r1cs_match_zkey",
            "zk_groth16_setup_sizes", "zk_groth16_setup",
            "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare",
@@ -232,6 +242,7 @@ def load_library():
     lib.zk_multi_prove_submit.argtypes = [C.c_void_p, u8p, u8p, u8p]
     lib.zk_multi_prove_collect.argtypes = [C.c_void_p, C.POINTER(zk_proof)]
     lib.zk_multi_prover_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.zk_multi_prover_shard_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(zk_prover_plan)]
     lib.zk_shard_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.zk_shard_set_exchange.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.zk_shard_begin.argtypes = [C.c_void_p, u8p, C.c_void_p, u8p, u8p, C.c_void_p]

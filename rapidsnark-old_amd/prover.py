@@ -203,6 +203,10 @@ class MultiProver:
         self.n_shards, self.chain_partitioned = ns.value, bool(part.value)
         self._pending = []
 
+    def shard_info(self, shard):
+        """The launch plan of one shard (Prover.info's dict)."""
+        return L.multi_prover_shard_info(self._lib, self._h, shard)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.zk_multi_prover_destroy(self._h)

@@ -36,6 +36,10 @@ class MultiProverFromView:
         L.check(self.lib.zk_multi_prover_info(self.h, C.byref(ns), C.byref(part)))
         self.n_shards, self.chain_partitioned = ns.value, bool(part.value)
 
+    def shard_info(self, shard):
+        """zk_multi_prover_shard_info: the plan of one shard, as a dict."""
+        return self.L.multi_prover_shard_info(self.lib, self.h, shard)
+
     def prove(self, w, r, s):
         out = self.L.zk_proof()
         ra, sa = ProverFromView._k32(r), ProverFromView._k32(s)

@@ -145,7 +145,50 @@ def _semaphore_like_circuit(m, n_in, n_public, rng, prng):
             w_rows[:n_in], w_rows[n_in:])
 
 
-def generate(k, n_public=2, seed=0, circuit_like=False, semaphore_like=False):
+def constraint_count(k, n_public=2, circuit_like=False, semaphore_like=False):
+    """-> (constraints m, input signals n_in) of generate()'s circuit on a 2^k domain"""
+    n = 1 << k
+    n_in = 64 if semaphore_like else max(n_public + 1, n // 8)                 # input signals (incl. the public ones)
+    return (3 * n // 4 + 5 if (circuit_like or semaphore_like) else n) - 1 - n_in, n_in
+
+
+def check_long_rows(long_rows, m):
+    """generate()'s long_rows option as a list of (count, terms), or ValueError: counts and terms are positive, and the
+    constraints the picks extend (two picks each) exist."""
+    out = [(int(c), int(t)) for c, t in long_rows]
+    if any(c < 1 or t < 1 for c, t in out):
+        raise ValueError("long_rows: count and terms must be at least 1")
+    picks = sum(c for c, _ in out)
+    if (picks + 1) // 2 > m:
+        raise ValueError("long_rows: %d picks extend %d constraints, the circuit has %d" % (picks, (picks + 1) // 2, m))
+    if sum(c * t for c, t in out) >= 1 << 31:
+        raise ValueError("long_rows: too many terms")
+    return out
+
+
+def _long_row_records(long_rows, recA, recB, m, n_in, k, seed):
+    """The records that extend the linear sides long_rows picks: pick j (counted over all of long_rows) extends constraint
+    chosen[j // 2], matrix A for even j and B for odd j, to `terms` terms: random input signals, full-size coefficients, the
+    first of them on a signal the side already reads (the same (row, signal) pair twice: the loaders must add them up)."""
+    rng = np.random.default_rng(0x10A6E0000 + 131 * k + seed)
+    picks = [t for c, t in long_rows for _ in range(c)]
+    chosen = rng.choice(m, size=(len(picks) + 1) // 2, replace=False).astype(np.uint32)
+    extra = [[], []]
+    for j, terms in enumerate(picks):
+        mat, row = j & 1, chosen[j // 2]
+        have = (recB if mat else recA)
+        have = have[have["c"] == row]
+        e = terms - have.size
+        if e <= 0:
+            continue
+        sig = rng.integers(1, 1 + n_in, size=e, dtype=np.uint32)
+        sig[0] = have["s"][0] if have.size else sig[0]
+        vals = _mul(synth.random_fr_bytes(rng, e).reshape(-1), _const(MONT ** 3, e))          # value * R^2
+        extra[mat].append(_records(mat, np.full(e, row, np.uint32), sig, vals))
+    return extra
+
+
+def generate(k, n_public=2, seed=0, circuit_like=False, semaphore_like=False, long_rows=()):
     """-> dict with the zkey sections (numpy uint8), the witness, the trapdoor and the vectors the
     trapdoor check needs.  Needs a GPU.
 
@@ -156,14 +199,21 @@ def generate(k, n_public=2, seed=0, circuit_like=False, semaphore_like=False):
 
     semaphore_like: the shape class of BASELINE configs[4] (Semaphore / iden3 auth; no such key exists in this image) — see
     _semaphore_like_circuit: 64 inputs, nVars = 3/4 of the domain + 5, chains of x^5 S-box rounds between Merkle-style muxes,
-    nearly every signal a full-size field element; the witness is computed on the host (the constraints form one long chain)."""
+    nearly every signal a full-size field element; the witness is computed on the host (the constraints form one long chain).
+
+    long_rows: a sequence of (count, terms) — the rows real circom keys have and the shapes above lack (Num2Bits: 254 terms;
+    linear sums left by constraint simplification: thousands).  Each of the `count` picks extends one linear side of a
+    constraint to `terms` terms (_long_row_records): matrix A for the even picks, B for the odd ones, and picks 2j, 2j + 1
+    extend the same constraint.  Composes with circuit_like; () leaves the key as it is without the option."""
     n = 1 << k
-    n_in = 64 if semaphore_like else max(n_public + 1, n // 8)                 # input signals (incl. the public ones)
+    m, n_in = constraint_count(k, n_public, circuit_like, semaphore_like)            # constraints = internal signals
     if semaphore_like and n_in < n_public + 8:
         raise ValueError("semaphore_like needs at most 56 public signals")
-    m = (3 * n // 4 + 5 if (circuit_like or semaphore_like) else n) - 1 - n_in      # constraints = internal signals
     if m < 1 or m + n_public + 1 > n:
         raise ValueError("domain too small")
+    long_rows = check_long_rows(long_rows, m)
+    if long_rows and semaphore_like:
+        raise ValueError("long_rows: not with semaphore_like (its witness is a chain evaluated on the host)")
     n_vars = 1 + n_in + m                            # = n (circuit_like: 3n/4 + 5)
     rng = np.random.default_rng(0x2C6E0000 + 131 * k + seed)
     import random
@@ -215,6 +265,9 @@ def generate(k, n_public=2, seed=0, circuit_like=False, semaphore_like=False):
     if circuit_like or semaphore_like:              # a real zkey holds no zero coefficients
         recA = recA[recA["v"].max(axis=1) > 0]
         recB = recB[recB["v"].max(axis=1) > 0]
+    if long_rows:
+        xa, xb = _long_row_records(long_rows, recA, recB, m, n_in, k, seed)
+        recA, recB = np.concatenate([recA] + xa), np.concatenate([recB] + xb)
     rec = np.concatenate([recA, recB])
     rec = rec[rng.permutation(rec.size)]            # the loader must not rely on any order
     coefs = _image(rec)

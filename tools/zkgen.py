@@ -2,7 +2,7 @@
 """zkgen — write a trapdoor-VALID Groth16 key at a benchmark size (needs a GPU).
 
     python tools/zkgen.py <log2n> <outdir> [--npublic N] [--seed S] [--circuit-like | --semaphore-like] [--r1cs] [--prove]
-                          [--ptau POWER [--unprepared]]
+                          [--ptau POWER [--unprepared]] [--long-rows COUNTxTERMS ...]
 
 Writes <outdir>/circuit.zkey, witness.wtns, verification_key.json, toxic.json (see
 rapidsnark-old_amd/zkgen.py); --r1cs also the circuit as circom's circuit.r1cs (for `wtnscheck` / ZKHIP_R1CS); --ptau POWER
@@ -22,7 +22,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def long_rows_arg(text):
+    """COUNTxTERMS -> (count, terms), both at least 1"""
+    try:
+        count, terms = (int(x) for x in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected COUNTxTERMS, e.g. 3x254")
+    if count < 1 or terms < 1:
+        raise argparse.ArgumentTypeError("COUNTxTERMS: both at least 1")
+    return count, terms
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("log2n", type=int)
     ap.add_argument("outdir")
@@ -35,11 +46,27 @@ def main():
                                                                   "nearly every signal full-size (zkgen.generate; use --npublic 4)")
     ap.add_argument("--ptau", type=int, metavar="POWER", help="also write pot.ptau of this power from the key's tau, alpha, beta (test input only)")
     ap.add_argument("--unprepared", action="store_true", help="with --ptau: leave the Lagrange sections 12 to 15 out (an input for `ptauprepare`)")
-    args = ap.parse_args()
+    ap.add_argument("--long-rows", type=long_rows_arg, action="append", default=[], metavar="COUNTxTERMS",
+                    help="extend COUNT linear sides to TERMS terms each, A and B in turn, two per constraint (zkgen.generate long_rows; repeatable)")
+    args = ap.parse_args(argv)
+    if args.long_rows:
+        from rapidsnark_old_amd import zkgen
+        if args.semaphore_like:
+            ap.error("--long-rows: not with --semaphore-like")
+        try:
+            zkgen.check_long_rows(args.long_rows, zkgen.constraint_count(args.log2n, args.npublic, args.circuit_like, args.semaphore_like)[0])
+        except ValueError as e:
+            ap.error(str(e))
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     import rapidsnark_old_amd as zk
     from rapidsnark_old_amd import zkgen, synth
     t = time.time()
-    key = zkgen.generate(args.log2n, args.npublic, args.seed, circuit_like=args.circuit_like, semaphore_like=args.semaphore_like)
+    key = zkgen.generate(args.log2n, args.npublic, args.seed, circuit_like=args.circuit_like, semaphore_like=args.semaphore_like,
+                         long_rows=args.long_rows)
     t_gen = time.time() - t
     t = time.time()
     zkgen.write_all(key, args.outdir)
