@@ -554,6 +554,53 @@ int zk_ptau_check_sizes(const zk_ptau_file_view *ptau, zk_ptau_check_sizes_t *si
  * value tells only whether the call ran. */
 int zk_ptau_check(const zk_ptau_file_view *ptau, const uint8_t *s32, int32_t device, zk_ptau_report *report);
 
+/* ---- Powers of Tau: contribute (n points times n scalars; tau^i, alpha tau^i, beta tau^i onto a .ptau) ---- */
+/* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
+ * counterpart is the arithmetic of snarkjs `powersoftau new` / `powersoftau contribute`.
+ * The operator: out[i] = scalars[i] points[i].  Points in the .ptau / .zkey encoding (affine Montgomery, all-zero =
+ * infinity, which stays all-zero), scalars 32 bytes LE each in standard form, as zk_g1_scale takes its one.  A scalar >= r
+ * is an error naming the lowest such index ("zk_g1_mul_vec: scalar 5 is not below r"), found before a device is touched.
+ * Every point is checked before it is used: coordinates below q, on its curve and, in G2, in the order-r subgroup (the
+ * endomorphism the kernel uses is a multiplication by a constant only there); one that fails is an error naming the
+ * lowest such index and what is wrong, "zk_g2_mul_vec: point 37 is not in the subgroup".  n = 0 is legal.  The points go
+ * through the device in chunks (ZKHIP_PTAU_CONTRIB_CHUNK=<points> in the environment sets their length, 2^20
+ * otherwise) on two buffer sets, so n is not bound by the HBM.  Each lane splits its scalar by BN254's endomorphism
+ * (zk_glv_split) and runs 128 doublings instead of 254; ZKHIP_MULVEC_PLAIN=1 computes the same bytes by the plain 254-bit
+ * double-and-add (the yardstick of the timing tool).  device -1: the current one. */
+int zk_g1_mul_vec(uint8_t *out, const uint8_t *points, const uint8_t *scalars, uint64_t n, int32_t device);
+int zk_g2_mul_vec(uint8_t *out, const uint8_t *points, const uint8_t *scalars, uint64_t n, int32_t device);
+/* out[i] = factor base^(first_exp + i) points[i]: the same with scalars made on the device, so that none crosses PCIe.
+ * base and factor: 32 bytes LE standard form, below r.  first_exp + n must not exceed 2^64. */
+int zk_g1_power_scale(uint8_t *out, const uint8_t *points, uint64_t n, const uint8_t base[32], uint64_t first_exp, const uint8_t factor[32], int32_t device);
+int zk_g2_power_scale(uint8_t *out, const uint8_t *points, uint64_t n, const uint8_t base[32], uint64_t first_exp, const uint8_t factor[32], int32_t device);
+/* What a lane makes of its scalar, on the host (the same code; no device): k = k1 + k2 lambda (mod r) with
+ * 0 < k1, k2 < 2^128, 16 bytes LE each (lambda = 4407920970296243842393367215006156084916469457145843978461).  k >= r is an
+ * error. */
+int zk_glv_split(const uint8_t k[32], uint8_t k1[16], uint8_t k2[16]);
+/* The contribution to a .ptau that is not yet prepared for phase 2: the view's sections 2 to 6 (zk_ptau_file_view; one
+ * that has any of sections 12 to 15 is refused: contribute before `ptauprepare`). */
+typedef struct zk_ptau_contrib_sizes {
+    uint64_t tau_g1_bytes, tau_g2_bytes, alpha_tau_g1_bytes, beta_tau_g1_bytes, beta_g2_bytes;   /* of the output sections 2 .. 6 */
+    uint64_t chunk_points;        /* points per chunk in effect */
+    uint64_t device_bytes;        /* HBM the call holds: two buffer sets of one chunk each, of the larger group */
+} zk_ptau_contrib_sizes;
+typedef struct zk_ptau_contrib_out {
+    uint8_t *tau_g1, *tau_g2, *alpha_tau_g1, *beta_tau_g1, *beta_g2;                             /* sections 2, 3, 4, 5, 6 */
+} zk_ptau_contrib_out;
+/* Checks the view without touching a device: a power outside 1 .. 28, a prepared file, a missing section, "ptau section N
+ * is short: ... bytes, power P needs ...". */
+int zk_ptau_contribute_sizes(const zk_ptau_file_view *ptau, zk_ptau_contrib_sizes *sizes);
+/* tauG1[i] <- tau^i tauG1[i] (i < 2^(power+1) - 1), tauG2[i] <- tau^i tauG2[i], alphaTauG1[i] <- alpha tau^i alphaTauG1[i],
+ * betaTauG1[i] <- beta tau^i betaTauG1[i] (i < 2^power) with zk_g*_power_scale's kernel, chunk by chunk (the caller
+ * buffers may be a mapping of the output file), betaG2 <- beta betaG2 on the host (the code of zk_g2_mul).  tau, alpha,
+ * beta: 32 bytes LE standard form; 0 and values >= r are errors.  Free HBM is checked before anything is allocated.  A point
+ * that is malformed (as above; in a .ptau infinity is malformed too) is an error naming its section and index, "ptau
+ * section 4: point 5 is not on the curve".  The three scalars, the table of squarings of tau on the device and everything
+ * derived from them are zeroed in host and device memory before the call returns; no message of zk_last_error contains
+ * them.  Section 7 (the contribution transcript) is the caller's: this is arithmetic, not a ceremony protocol. */
+int zk_ptau_contribute(const zk_ptau_file_view *ptau, const uint8_t tau[32], const uint8_t alpha[32], const uint8_t beta[32], int32_t device,
+                       zk_ptau_contrib_out *out);
+
 /* ---- Is this .zkey the key of this circuit over this Powers of Tau file ------------------ */
 /* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
  * counterpart is the arithmetic half of snarkjs `zkey verify circuit.r1cs pot.ptau circuit.zkey`.  Section 10 of the key

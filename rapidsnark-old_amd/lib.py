@@ -119,6 +119,15 @@ class zk_ptau_report(C.Structure):
                 ("bad_kind", C.c_uint32), ("bad_index", C.c_uint64)]
 
 
+class zk_ptau_contrib_sizes(C.Structure):
+    _fields_ = [("tau_g1_bytes", C.c_uint64), ("tau_g2_bytes", C.c_uint64), ("alpha_tau_g1_bytes", C.c_uint64), ("beta_tau_g1_bytes", C.c_uint64),
+                ("beta_g2_bytes", C.c_uint64), ("chunk_points", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class zk_ptau_contrib_out(C.Structure):
+    _fields_ = [("tau_g1", C.c_void_p), ("tau_g2", C.c_void_p), ("alpha_tau_g1", C.c_void_p), ("beta_tau_g1", C.c_void_p), ("beta_g2", C.c_void_p)]
+
+
 class zk_zkey_verify_view(C.Structure):
     _fields_ = [("key", zk_zkey_view), ("vk_gamma2", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsIC_bytes", C.c_uint64)]
 
@@ -185,7 +194,8 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_g1_scale", "zk_g1_scale_plan", "zk_zkey_contribute_sizes", "zk_zkey_contribute",
            "zk_pairing", "zk_vkey_create", "zk_vkey_destroy", "zk_vkey_verify",
            "zk_g2_in_subgroup", "zk_g1_power_msm", "zk_g2_power_msm", "zk_fr_power_dft", "zk_ptau_check_sizes", "zk_ptau_check",
-           "zk_zkey_verify_sizes", "zk_zkey_verify"]
+           "zk_zkey_verify_sizes", "zk_zkey_verify",
+           "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute"]
 ZK_SCALE_PLAN_MAX = 130
 ZK_VERIFY_OK, ZK_VERIFY_INVALID, ZK_VERIFY_MALFORMED = 0, 1, 2
 ZK_PTAU_OK, ZK_PTAU_INVALID, ZK_PTAU_MALFORMED = 0, 1, 2
@@ -302,6 +312,14 @@ def load_library():
                                              C.POINTER(zk_zkey_verify_sizes_t)]
         lib.zk_zkey_verify.argtypes = [C.POINTER(zk_r1cs_view), C.POINTER(zk_ptau_view), C.POINTER(zk_zkey_verify_view), u8p, C.c_int32,
                                        C.POINTER(zk_zkey_verify_report)]
+    if hasattr(lib, "zk_ptau_contribute"):
+        lib.zk_g1_mul_vec.argtypes = [u8p, u8p, u8p, C.c_uint64, C.c_int32]
+        lib.zk_g2_mul_vec.argtypes = [u8p, u8p, u8p, C.c_uint64, C.c_int32]
+        lib.zk_g1_power_scale.argtypes = [u8p, u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_int32]
+        lib.zk_g2_power_scale.argtypes = [u8p, u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_int32]
+        lib.zk_glv_split.argtypes = [u8p, u8p, u8p]
+        lib.zk_ptau_contribute_sizes.argtypes = [C.POINTER(zk_ptau_file_view), C.POINTER(zk_ptau_contrib_sizes)]
+        lib.zk_ptau_contribute.argtypes = [C.POINTER(zk_ptau_file_view), u8p, u8p, u8p, C.c_int32, C.POINTER(zk_ptau_contrib_out)]
     _LIB = lib
     return lib
 
@@ -518,6 +536,59 @@ def g1_scale_plan(k):
     kk = _scalar32(k)
     check(load_library().zk_g1_scale_plan(_ptr(kk), a, b, ZK_SCALE_PLAN_MAX, C.byref(n)))
     return list(a[:n.value]), list(b[:n.value])
+
+
+def _mul_vec_points(name, nb, points, scalars, device):
+    pts, sc = _buf(points), _scalars_le(scalars)
+    if pts.size % nb:
+        raise ValueError("points: a multiple of %d bytes expected" % nb)
+    n = pts.size // nb
+    if sc.size != 32 * n:
+        raise ValueError("scalars: one of 32 bytes for each of the %d points expected" % n)
+    out = np.zeros(pts.size, dtype=np.uint8)
+    check(_need(name)(_ptr(out) if n else None, _ptr(pts) if n else None, _ptr(sc) if n else None, n, device))
+    return out
+
+
+def g1_mul_vec(points, scalars, device=-1):
+    """[k_i * P_i] on the GPU (zk_g1_mul_vec): n x 64 B affine Montgomery points and n scalars (ints below r, or a uint8 array
+    of n x 32 B little-endian) -> numpy uint8 [n * 64], all-zero = infinity.  Every lane splits its own scalar by BN254's
+    endomorphism.  Raises ZkHipError naming the index of a scalar that is not below r or of a point that is not on the curve."""
+    return _mul_vec_points("zk_g1_mul_vec", 64, points, scalars, device)
+
+
+def g2_mul_vec(points, scalars, device=-1):
+    """zk_g2_mul_vec: the same over n x 128 B G2 points, which must be in the order-r subgroup (the error names the index)."""
+    return _mul_vec_points("zk_g2_mul_vec", 128, points, scalars, device)
+
+
+def _power_scale(name, nb, points, base, first_exp, factor, device):
+    pts = _buf(points)
+    if pts.size % nb:
+        raise ValueError("points: a multiple of %d bytes expected" % nb)
+    out = np.zeros(pts.size, dtype=np.uint8)
+    b, f = _scalar32(base), _scalar32(factor)
+    check(_need(name)(_ptr(out) if pts.size else None, _ptr(pts) if pts.size else None, pts.size // nb, _ptr(b), first_exp, _ptr(f), device))
+    return out
+
+
+def g1_power_scale(points, base, first_exp=0, factor=1, device=-1):
+    """[factor * base^(first_exp + i) * P_i] (zk_g1_power_scale): the scalars are made on the device.  base, factor: ints
+    below r."""
+    return _power_scale("zk_g1_power_scale", 64, points, base, first_exp, factor, device)
+
+
+def g2_power_scale(points, base, first_exp=0, factor=1, device=-1):
+    return _power_scale("zk_g2_power_scale", 128, points, base, first_exp, factor, device)
+
+
+def glv_split(k):
+    """zk_glv_split -> (k1, k2) with k = k1 + k2 lambda mod r and 0 < k1, k2 < 2^128: what a lane of zk_g*_mul_vec makes of
+    its scalar.  No device is touched.  Raises ZkHipError for k >= r."""
+    kk = _scalar32(k)
+    a, b = np.zeros(16, dtype=np.uint8), np.zeros(16, dtype=np.uint8)
+    check(_need("zk_glv_split")(_ptr(kk), _ptr(a), _ptr(b)))
+    return int.from_bytes(a.tobytes(), "little"), int.from_bytes(b.tobytes(), "little")
 
 
 def _need(name):

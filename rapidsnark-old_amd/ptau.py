@@ -13,10 +13,17 @@ in G1 and 128 B in G2, all-zero = infinity.
 prepare_phase2(src, dst) is `snarkjs powersoftau prepare phase2` on the GPU: sections 12 to 15 from sections 2 to 5, an
 inverse DFT over the points themselves (csrc/ptau_prepare.hip), for a ceremony's own output, whose tau nobody knows.
 
+ptau_new(power, path) writes the file a ceremony starts from (`snarkjs powersoftau new`: every point a generator), and
+ptau_contribute(src, dst) is the arithmetic of `snarkjs powersoftau contribute` on the GPU (csrc/mulvec.hip): sections 2 to
+5 times the powers of a new tau (and alpha, beta), section 6 times beta.  Section 7 is copied, not extended: the result is
+a sound file if one contributor forgot their scalars, not a transcript `snarkjs powersoftau verify` accepts.
+
 groth16_setup(r1cs, ptau) makes the phase-2 starting key of snarkjs `groth16 setup` / `zkey new` from these sections on the
 GPU (gamma = delta = 1) as the key dict zkgen.write_zkey / zkgen.verification_key take."""
 import ctypes as C
 import mmap
+import os
+import secrets
 import struct
 
 import numpy as np
@@ -197,6 +204,82 @@ def write_trapdoor_ptau(power, tau, alpha, beta, path, prepared=True):
             (15, L.fixed_base_g1(g1, a_k(lag13, beta))),
         ]
     write_container(path, b"ptau", 1, sections)
+
+
+# ---------------------------------------------------------------- a new file and a contribution to it
+def ptau_new(power, path):
+    """What `snarkjs powersoftau new bn128 power path` writes (and the program `ptaunew`, byte for byte): sections 2, 4, 5
+    filled with the generator of G1, 3 and 6 with that of G2, section 7 a contribution count of zero.  tau = alpha = beta =
+    1: contribute before use.  No device is touched."""
+    if not 1 <= power <= 28:
+        raise ValueError("power must be in 1 .. 28")
+    g1 = np.frombuffer(synth.g1_gen_bytes(), dtype=np.uint8)
+    g2 = np.frombuffer(synth.g2_gen_bytes(), dtype=np.uint8)
+    n = 1 << power
+    head = np.frombuffer(b"ptau" + struct.pack("<I", 1), dtype=np.uint8)
+    hdr = np.frombuffer(struct.pack("<I", 32) + int(Q_MOD).to_bytes(32, "little") + struct.pack("<II", power, power), dtype=np.uint8)
+    rows = [(2, g1, 2 * n - 1), (3, g2, n), (4, g1, n), (5, g1, n), (6, g2, 1)]
+    secs = [(1, hdr.size, hdr)] + [(sid, g.size * cnt, None) for sid, g, cnt in rows] + [(7, 4, np.zeros(4, np.uint8))]
+    with rewrite_mapped(path, head, secs) as (o, starts):
+        for (sid, g, cnt), at in zip(rows, starts[1:6]):
+            o[at:at + g.size * cnt].reshape(cnt, g.size)[:] = g
+        del o
+
+
+def ptau_contribute_sizes(src):
+    """-> zk_ptau_contribute_sizes as a dict (the byte sizes of the output sections 2 to 6, chunk_points, device_bytes);
+    raises ZkHipError with the library's message (unsupported power, prepared file, missing or short section).  No device
+    is touched."""
+    pf, own = _open_ptau(src)
+    try:
+        fv = pf.file_view()
+        z = L.zk_ptau_contrib_sizes()
+        L.check(L.load_library().zk_ptau_contribute_sizes(C.byref(fv), C.byref(z)))
+    finally:
+        if own:
+            pf.close()
+    return {name: int(getattr(z, name)) for name, _ in L.zk_ptau_contrib_sizes._fields_}
+
+
+def ptau_contribute(src, dst, tau=None, alpha=None, beta=None, device=-1):
+    """One contribution to a .ptau on the GPU (zk_ptau_contribute), the arithmetic of `snarkjs powersoftau contribute`.
+    src: path of a file that is not prepared for phase 2; dst: path.  tau, alpha, beta: ints with 0 < s < r; None draws the
+    scalar from `secrets` (2 <= s < r), and a file is safe only if somebody's drawn scalars were forgotten.  dst holds the
+    magic and version of src and its sections 1 to 7 in src's order: 1 and 7 byte for byte (the transcript is COPIED, not
+    extended), 2 to 6 from the library.  It is written as dst + ".partial" through a mapping and renamed at the end: a
+    failure (ZkHipError with the library's message, ValueError for bad scalars or dst = src) leaves neither file."""
+    given = []
+    for name, s in (("tau", tau), ("alpha", alpha), ("beta", beta)):
+        while s is None:
+            s = secrets.randbits(254)
+            s = s if 2 <= s < R_MOD else None
+        s = int(s)
+        if not 0 < s < R_MOD:
+            raise ValueError("the contribution scalar %s must satisfy 0 < s < r" % name)
+        given.append(s)
+    if os.path.exists(dst) and os.path.samefile(src, dst):
+        raise ValueError("the input and the output are the same file")
+    lib = L.load_library()
+    pf = PtauFile(src)
+    try:
+        fv = pf.file_view()
+        z = L.zk_ptau_contrib_sizes()
+        L.check(lib.zk_ptau_contribute_sizes(C.byref(fv), C.byref(z)))
+        made = {2: z.tau_g1_bytes, 3: z.tau_g2_bytes, 4: z.alpha_tau_g1_bytes, 5: z.beta_tau_g1_bytes, 6: z.beta_g2_bytes}
+        keep = sorted((pos, size, sid) for sid, (pos, size) in pf.sections.items() if 1 <= sid <= 7)
+        secs = [(sid, int(made[sid]), None) if sid in made else (sid, size, pf.raw[pos:pos + size]) for pos, size, sid in keep]
+        with rewrite_mapped(dst, pf.raw[:8], secs) as (o, starts):
+            where = {sid: at for (sid, _, _), at in zip(secs, starts)}
+            out = L.zk_ptau_contrib_out(*(o[where[sid]:].ctypes.data for sid in (2, 3, 4, 5, 6)))
+            ss = [L._scalar32(s) for s in given]
+            try:
+                L.check(lib.zk_ptau_contribute(C.byref(fv), L._ptr(ss[0]), L._ptr(ss[1]), L._ptr(ss[2]), device, C.byref(out)))
+            finally:
+                for a in ss:
+                    a[:] = 0
+            del o
+    finally:
+        pf.close()
 
 
 # ---------------------------------------------------------------- prepare phase 2
