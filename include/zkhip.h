@@ -500,6 +500,22 @@ void zk_vkey_destroy(zk_vkey *vk);
 #define ZK_VERIFY_MALFORMED 2
 int zk_vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict);
 
+/* Two routes to the same verdicts and bytes.  Up to ZKHIP_VERIFY_COOP_MAX proofs (zk_vkey_verify) or ZKHIP_PAIRING_COOP_MAX
+ * groups (zk_pairing) a call runs one workgroup per proof or group, which is what a lone proof needs; larger calls run a
+ * lane per proof, which is what a batch needs.  Both variables are decimal, read at every call; 0: never cooperative;
+ * anything that is not a number from 0 to 2^24 is an error of the call. */
+#define ZK_VERIFY_PATH_LANES 0   /* a lane per proof: k_verify_check / _miller / _final */
+#define ZK_VERIFY_PATH_COOP  1   /* a workgroup per proof: k_verify_coop */
+typedef struct {
+    uint32_t coop_max;        /* the threshold the last call used */
+    uint32_t last_path;       /* ZK_VERIFY_PATH_* of the last zk_vkey_verify on this key */
+    uint32_t last_launches;   /* kernel launches of that call */
+    uint32_t reserved;
+    uint64_t proofs_coop, proofs_lanes;   /* totals since zk_vkey_create */
+} zk_vkey_plan;
+int zk_vkey_info(zk_vkey *vk, zk_vkey_plan *plan);
+int zk_pairing_last_path(void);   /* ZK_VERIFY_PATH_* of this thread's last zk_pairing, -1 before the first */
+
 /* ---- Powers of Tau: check (is the .ptau a sequence of powers of one tau, are its Lagrange sections its own) ---- */
 /* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
  * counterpart is the arithmetic half of snarkjs `powersoftau verify`.  The contribution transcript (section 7) is not read.

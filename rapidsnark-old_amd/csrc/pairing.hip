@@ -14,8 +14,8 @@
 //
 // Checks before any pairing (k_pair_check, k_verify_check): coordinates below q, y^2 = x^3 + 3 in G1, y^2 = x^3 + 3/xi on
 // the twist, and membership of the order-r subgroup of the twist by [r] Q = infinity (devmem.hpp's scalar_mul_affine over
-// the 254 bits of r: the plain test, about as many Fq products as the Miller loop itself; an endomorphism test would be
-// several times cheaper and is not built).  Public signals below r.  vk_x = IC_0 + sum pub_j IC_j per lane, by the same
+// the 254 bits of r: the plain test, about as many Fq products as the Miller loop itself; the cooperative kernels of
+// pairing_coop.hip use ptengine.hpp's endomorphism test, several times cheaper; these kernels are left as they were).  Public signals below r.  vk_x = IC_0 + sum pub_j IC_j per lane, by the same
 // scalar_mul_affine and curve.hpp's add, which take every special case; vk_x = infinity is legal and contributes 1.
 //
 // Field form: field.hpp's 8 x 32-bit Montgomery words, the form of the .zkey's and the proof's own bytes and of every
@@ -28,25 +28,16 @@
 #include "devmem.hpp"
 #include "ptcheck.hpp"
 #include "pairing.hpp"
+#include "paircheck.hpp"
+#include "pairing_coop.hpp"
 
 namespace {
 
 constexpr uint64_t DEFAULT_CHUNK = 1ull << 16;        // jobs per chunk
-constexpr uint32_t ST_OK = 0, ST_MALFORMED = 1;       // k_verify_check's word per proof
 
 static_assert(sizeof(G1Affine) == 64 && sizeof(G2Affine) == 128 && sizeof(Fq12) == 384 && sizeof(G2Proj) == 192 && sizeof(Line) == 192, "layout");
 
 // ---------------------------------------------------------------- device: checks
-__device__ __forceinline__ bool below_r(const Fr &a) {
-    uint32_t bw = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) (void)subb(a.v[i], FrParams::P[i], bw);
-    return bw != 0;
-}
-template <class F>
-__device__ __forceinline__ bool on_curve(const Affine<F> &p, const F &b) {
-    return below_q(p.x) && below_q(p.y) && F::sqr(p.y) == F::add(F::mul(F::sqr(p.x), p.x), b);
-}
 __device__ __noinline__ bool in_subgroup(const G2Affine &Q) {   // [r] Q = infinity
     Fr r;
 #pragma unroll
@@ -81,25 +72,7 @@ __global__ void k_pair_consts(PairConsts *k) {
 __global__ __launch_bounds__(64) void k_line_table(Line *tab, const G2Affine *Q, uint32_t n, const PairConsts *k) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
-    const G2Affine q = load_pt(Q + j);
-    G2Proj T{q.x, q.y, Fq2::one()};
-    Line *out = tab + (uint64_t)j * MILLER_LINES;
-    Line l;
-    int at = 0;
-    for (int i = 0; i < 64; i++) {
-        step_dbl(T, l, *k);
-        out[at++] = l;
-        if (ate_bit(i)) {
-            step_add(T, l, q);
-            out[at++] = l;
-        }
-    }
-    G2Affine q1, q2;
-    frob_twist(q1, q2, q, *k);
-    step_add(T, l, q1);
-    out[at++] = l;
-    step_add(T, l, q2);
-    out[at++] = l;
+    line_table(tab + (uint64_t)j * MILLER_LINES, load_pt(Q + j), *k);
 }
 
 // ---------------------------------------------------------------- device: Miller loops
@@ -158,12 +131,6 @@ __global__ __launch_bounds__(64) void k_final_exp(uint8_t *out, const Fq12 *f, u
 }
 
 // ---------------------------------------------------------------- device: verification
-__device__ __forceinline__ G1Affine g1_to_affine(const G1XYZZ &p) {
-    if (p.is_inf()) return G1Affine::inf();
-    const Fq t = Fq::inv(Fq::mul(p.zz, p.zzz));       // x = X/ZZ, y = Y/ZZZ by one inversion
-    return G1Affine{Fq::mul(p.x, Fq::mul(t, p.zzz)), Fq::mul(p.y, Fq::mul(t, p.zz))};
-}
-
 // status[i], and vk_x of proof i when it is well-formed.  proofs: A 64 | B 128 | C 64; publics: n x nPublic x 32 B
 __global__ __launch_bounds__(64) void k_verify_check(uint32_t *status, G1Affine *vkx, const uint8_t *__restrict__ proofs, const Fr *__restrict__ publics,
                                                      uint64_t n, uint32_t nPublic, const G1Affine *__restrict__ ic, Fq b1, Fq2 b2) {
@@ -257,6 +224,15 @@ uint64_t chunk_jobs() {
     return DEFAULT_CHUNK;
 }
 
+// The largest calls that take the cooperative path (pairing_coop.hip), read at every call like the chunk.  The defaults are
+// the measured crossovers of profiles/verify_latency_timing.txt.
+constexpr uint64_t DEFAULT_VERIFY_COOP_MAX = 1024, DEFAULT_PAIRING_COOP_MAX = 256;
+constexpr uint64_t COOP_MAX_PAIRS = 8192;             // 19 KiB of lines a pair or a proof: a call with more of them goes the
+constexpr uint64_t COOP_MAX_PROOFS = 8192;            // lane way whatever the threshold, in chunks and constant memory
+uint64_t verify_coop_max() { return coop_threshold("ZKHIP_VERIFY_COOP_MAX", "proofs", DEFAULT_VERIFY_COOP_MAX); }
+uint64_t pairing_coop_max() { return coop_threshold("ZKHIP_PAIRING_COOP_MAX", "groups", DEFAULT_PAIRING_COOP_MAX); }
+thread_local int t_pairing_path = -1;
+
 struct Consts {
     DevBuf<PairConsts> k;
     void make(hipStream_t s) {
@@ -281,6 +257,37 @@ struct CheckWords {
     }
 };
 
+// every group on a workgroup of its own: one launch, the point checks inside it
+void pairing_coop(uint8_t *out, const uint8_t *g1, const uint8_t *g2, uint64_t n_pairs, uint32_t group, uint64_t jobs) {
+    need_hbm("zk_pairing", n_pairs * (sizeof(G1Affine) + sizeof(G2Affine) + MILLER_LINES * sizeof(Line) + 1) + jobs * sizeof(Fq12) + 65536);
+    Stream st;
+    hipStream_t s = st.s;
+    Consts kc;
+    kc.make(s);
+    DevBuf<G1Affine> d1;
+    DevBuf<G2Affine> d2;
+    DevBuf<Line> dl;
+    DevBuf<uint8_t> dskip, dout;
+    DevBuf<uint32_t> derr;
+    uint32_t h[3];
+    d1.alloc(n_pairs);
+    d2.alloc(n_pairs);
+    dl.alloc(n_pairs * MILLER_LINES);
+    dskip.alloc(n_pairs);
+    dout.alloc(jobs * sizeof(Fq12));
+    derr.alloc(3);
+    HIP_TRY(hipMemcpyAsync(d1.p, g1, n_pairs * sizeof(G1Affine), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d2.p, g2, n_pairs * sizeof(G2Affine), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(derr.p, 0xFF, 12, s));
+    launch_pairing_coop(dout.p, d1.p, d2.p, dl.p, dskip.p, derr.p, n_pairs, group, COOP_FINAL | COOP_CHECK, kc.k.p, s);
+    HIP_TRY(hipMemcpyAsync(h, derr.p, 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h[0] != NO_BAD_POINT) throw std::invalid_argument("pairing: G1 point " + std::to_string(h[0]) + " is not on the curve");
+    if (h[1] != NO_BAD_POINT) throw std::invalid_argument("pairing: G2 point " + std::to_string(h[1]) + " is not on the curve");
+    if (h[2] != NO_BAD_POINT) throw std::invalid_argument("pairing: G2 point " + std::to_string(h[2]) + " is not in the subgroup");
+    HIP_TRY(hipMemcpy(out, dout.p, jobs * sizeof(Fq12), hipMemcpyDeviceToHost));
+}
+
 void pairing(uint8_t *out, const uint8_t *g1, const uint8_t *g2, uint64_t n_pairs, uint32_t group, int32_t device) {
     if (!group) throw std::invalid_argument("zk_pairing: group is 0");
     if (!n_pairs) return;
@@ -289,7 +296,13 @@ void pairing(uint8_t *out, const uint8_t *g1, const uint8_t *g2, uint64_t n_pair
     const uint64_t cap_jobs = jobs < chunk ? jobs : chunk;
     if (cap_jobs > (1ull << 31) / group) throw std::invalid_argument("zk_pairing: a chunk of " + std::to_string(cap_jobs) + " groups of " + std::to_string(group) + " pairs is too large");
     const uint64_t cap_pairs = cap_jobs * group < n_pairs ? cap_jobs * group : n_pairs;
+    const bool coop = jobs <= pairing_coop_max() && n_pairs <= COOP_MAX_PAIRS;
     DeviceGuard g(resolve_device(device));
+    t_pairing_path = coop ? ZK_VERIFY_PATH_COOP : ZK_VERIFY_PATH_LANES;
+    if (coop) {
+        pairing_coop(out, g1, g2, n_pairs, group, jobs);
+        return;
+    }
     need_hbm("zk_pairing", cap_pairs * (sizeof(G1Affine) + sizeof(G2Affine) + sizeof(G2Proj)) + cap_jobs * 2 * sizeof(Fq12) + 65536);
     Stream st;
     hipStream_t s = st.s;
@@ -334,6 +347,15 @@ struct zk_vkey {
     DevBuf<G1Affine> ic;
     DevBuf<Line> tab;
     DevBuf<Fq12> ml_ab;
+    // the cooperative path's own, kept between calls: a stream and buffers for `cap` proofs, grown when a call brings more
+    struct Coop {
+        std::unique_ptr<Stream> st;
+        DevBuf<uint8_t> dp, dv;
+        DevBuf<Fr> dpub;
+        DevBuf<Line> lines;
+        uint64_t cap = 0;
+    } coop;
+    zk_vkey_plan plan{};
 };
 
 namespace {
@@ -362,10 +384,14 @@ zk_vkey *vkey_create(const zk_vkey_view *v, int32_t device) {
     hipStream_t s = st.s;
     DevBuf<G1Affine> d1;
     DevBuf<G2Affine> d2;
-    DevBuf<G2Proj> dT;
+    DevBuf<Line> dl;                                  // the cooperative Miller loop's lines of beta, its skip byte and error words
+    DevBuf<uint8_t> dskip;
+    DevBuf<uint32_t> derr;
     d1.alloc(n1);
     d2.alloc(3);
-    dT.alloc(1);
+    dl.alloc(MILLER_LINES);
+    dskip.alloc(1);
+    derr.alloc(3);
     HIP_TRY(hipMemcpyAsync(d1.p, v->vk_alpha1, sizeof(G1Affine), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d1.p + 1, v->IC, (n1 - 1) * sizeof(G1Affine), hipMemcpyHostToDevice, s));
     for (int i = 0; i < 3; i++) HIP_TRY(hipMemcpyAsync(d2.p + i, g2s[i], sizeof(G2Affine), hipMemcpyHostToDevice, s));
@@ -381,8 +407,16 @@ zk_vkey *vkey_create(const zk_vkey_view *v, int32_t device) {
     vk->ml_ab.alloc(1);
     HIP_TRY(hipMemcpyAsync(vk->ic.p, d1.p + 1, (n1 - 1) * sizeof(G1Affine), hipMemcpyDeviceToDevice, s));
     ZK_LAUNCH(k_line_table, dim3(1), dim3(64), 0, s, vk->tab.p, d2.p + 1, 2u, vk->kc.k.p);
-    ZK_LAUNCH(k_miller_groups, dim3(1), dim3(64), 0, s, vk->ml_ab.p, d1.p, d2.p, dT.p, (uint64_t)1, 1u, vk->kc.k.p);
+    // the Miller value of (alpha, beta): the cooperative loop, or a lane of k_miller_groups when ZKHIP_PAIRING_COOP_MAX is 0
+    // (read once, after every check of the key, so a key's own error comes before a malformed variable's)
+    const bool coop_ab = pairing_coop_max() != 0;
+    DevBuf<G2Proj> dT;
+    if (!coop_ab) {
+        dT.alloc(1);
+        ZK_LAUNCH(k_miller_groups, dim3(1), dim3(64), 0, s, vk->ml_ab.p, d1.p, d2.p, dT.p, (uint64_t)1, 1u, vk->kc.k.p);
+    }
     ZK_LAUNCH_OK("verification key set-up");
+    if (coop_ab) launch_pairing_coop(reinterpret_cast<uint8_t *>(vk->ml_ab.p), d1.p, d2.p, dl.p, dskip.p, derr.p, 1, 1, 0, vk->kc.k.p, s);
     HIP_TRY(hipStreamSynchronize(s));
     return vk.release();
 }
@@ -392,8 +426,35 @@ void vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uin
     if (!n) return;
     if (!proofs || !verdict || (vk->nPublic && !publics)) throw std::invalid_argument("null argument");
     std::lock_guard<std::mutex> lock(vk->mu);
+    const uint64_t coop_max = verify_coop_max();
     const uint64_t chunk = chunk_jobs(), cap = n < chunk ? n : chunk, pub_bytes = (uint64_t)vk->nPublic * 32;
     DeviceGuard g(vk->device);
+    vk->plan.coop_max = (uint32_t)coop_max;
+    if (n <= coop_max && n <= COOP_MAX_PROOFS) {
+        zk_vkey::Coop &c = vk->coop;
+        if (!c.st) c.st.reset(new Stream);
+        if (c.cap < n) {
+            need_hbm("zk_vkey_verify", n * (256 + pub_bytes + 1 + MILLER_LINES * sizeof(Line)) + 65536);
+            c.cap = 0;
+            c.dp.alloc(n * 256);
+            c.dv.alloc(n);
+            c.dpub.alloc(n * vk->nPublic);
+            c.lines.alloc(n * MILLER_LINES);
+            c.cap = n;
+        }
+        hipStream_t s = c.st->s;
+        HIP_TRY(hipMemcpyAsync(c.dp.p, proofs, n * 256, hipMemcpyHostToDevice, s));
+        if (pub_bytes) HIP_TRY(hipMemcpyAsync(c.dpub.p, publics, n * pub_bytes, hipMemcpyHostToDevice, s));
+        launch_verify_coop(c.dv.p, c.dp.p, c.dpub.p, n, vk->nPublic, vk->ic.p, vk->tab.p, vk->ml_ab.p, vk->kc.k.p, c.lines.p, s);
+        HIP_TRY(hipMemcpyAsync(verdict, c.dv.p, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        vk->plan.last_path = ZK_VERIFY_PATH_COOP;
+        vk->plan.last_launches = 1;
+        vk->plan.proofs_coop += n;
+        return;
+    }
+    vk->plan.last_path = ZK_VERIFY_PATH_LANES;
+    vk->plan.last_launches = 0;
     need_hbm("zk_vkey_verify", cap * (256 + pub_bytes + 4 + sizeof(G1Affine) + sizeof(Fq12) + 1) + 65536);
     Stream st;
     hipStream_t s = st.s;
@@ -419,6 +480,8 @@ void vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uin
         ZK_LAUNCH_OK("verification");
         HIP_TRY(hipMemcpyAsync(verdict + off, dv.p, cnt, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
+        vk->plan.last_launches += 3;
+        vk->plan.proofs_lanes += cnt;
     }
 }
 
@@ -446,6 +509,16 @@ void zk_vkey_destroy(zk_vkey *vk) {
     delete vk;
     if (had) (void)hipSetDevice(prev);
 }
+
+int zk_vkey_info(zk_vkey *vk, zk_vkey_plan *plan) {
+    return guarded([&] {
+        if (!vk || !plan) throw std::invalid_argument("null argument");
+        std::lock_guard<std::mutex> lock(vk->mu);
+        *plan = vk->plan;
+    });
+}
+
+int zk_pairing_last_path(void) { return t_pairing_path; }
 
 int zk_vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict) {
     return guarded([&] { vkey_verify(vk, proofs, publics, n, verdict); });

@@ -328,6 +328,27 @@ constexpr int popcount64(u64 v) { return v ? (int)(v & 1) + popcount64(v >> 1) :
 constexpr int MILLER_LINES = 64 + popcount64(ATE_LOW) + 2;
 ZK_HD bool ate_bit(int i) { return (ATE_LOW >> (63 - i)) & 1; }
 
+// out[i], i < MILLER_LINES: line i of the loop over q in that schedule, to be evaluated at any P (f12_mul_line_at)
+ZK_NI void line_table(Line *out, const G2Affine &q, const PairConsts &k) {
+    G2Proj T{q.x, q.y, Fq2::one()};
+    Line l;
+    int at = 0;
+    for (int i = 0; i < 64; i++) {
+        step_dbl(T, l, k);
+        out[at++] = l;
+        if (ate_bit(i)) {
+            step_add(T, l, q);
+            out[at++] = l;
+        }
+    }
+    G2Affine q1, q2;
+    frob_twist(q1, q2, q, k);
+    step_add(T, l, q1);
+    out[at++] = l;
+    step_add(T, l, q2);
+    out[at++] = l;
+}
+
 // ---------------------------------------------------------------- the final exponentiation
 ZK_NI void f12_pow_x(Fq12 &r, const Fq12 &a) {        // a^x, x = BN_X (63 bits), square and multiply from the top
     Fq12 t = a;

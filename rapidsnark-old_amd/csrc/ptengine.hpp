@@ -35,6 +35,23 @@ __device__ __forceinline__ bool same_point(const G2XYZZ &a, const G2XYZZ &b) {
     return Fq2::mul(a.x, b.zz) == Fq2::mul(b.x, a.zz) && Fq2::mul(a.y, b.zzz) == Fq2::mul(b.y, a.zzz);
 }
 
+// Q (on the twist, not infinity) is in the order-r subgroup: psi^3([2x] Q) = [x + 1] Q + psi([x] Q) + psi^2([x] Q)
+__device__ __forceinline__ bool g2_in_subgroup(const G2Affine &Q, const PsiConsts &k) {
+    G2XYZZ L = G2XYZZ::from_affine(Q);                // bit 62 of x
+#pragma unroll 1
+    for (int b = 61; b >= 0; b--) {
+        L = dbl(L);
+        if ((BN_X >> b) & 1) madd(L, Q);
+    }
+    G2XYZZ T = psi(L, k);                             // psi([x] Q)
+    madd(L, Q);                                       // [x + 1] Q
+    add(L, T);
+    T = psi(T, k);
+    add(L, T);
+    T = dbl(psi(T, k));                               // psi^3([2x] Q)
+    return same_point(L, T);
+}
+
 // out[i] (when given) = 1 if pts[i] is in the order-r subgroup (infinity: 1), else 0; the lowest index outside goes to
 // *err (when given).  The points are on the twist (the caller's check runs first; on other bytes the result means nothing).
 template <bool PLAIN>
@@ -50,19 +67,7 @@ __global__ __launch_bounds__(64) void k_g2_subgroup(uint8_t *out, uint32_t *err,
             for (int j = 0; j < 8; j++) r.v[j] = FrParams::P[j];
             ok = scalar_mul_affine(Q, r).is_inf();
         } else {
-            G2XYZZ L = G2XYZZ::from_affine(Q);        // bit 62 of x
-#pragma unroll 1
-            for (int b = 61; b >= 0; b--) {
-                L = dbl(L);
-                if ((BN_X >> b) & 1) madd(L, Q);
-            }
-            G2XYZZ T = psi(L, k);                     // psi([x] Q)
-            madd(L, Q);                               // [x + 1] Q
-            add(L, T);
-            T = psi(T, k);
-            add(L, T);
-            T = dbl(psi(T, k));                       // psi^3([2x] Q)
-            ok = same_point(L, T);
+            ok = g2_in_subgroup(Q, k);
         }
     }
     if (out) out[i] = ok ? 1 : 0;

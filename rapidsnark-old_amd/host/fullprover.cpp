@@ -114,6 +114,8 @@ FullProver::FullProver(std::string zkeyFileNames[], int size) {
                                                     hdr->vk_beta2, hdr->vk_delta1, hdr->vk_delta2, zkey->getSectionData(4),
                                                     zkey->getSectionData(5), zkey->getSectionData(6), zkey->getSectionData(7),
                                                     zkey->getSectionData(8), zkey->getSectionData(9), sizes, /*precompDefault=*/true, dev, batch, reserve));
+        if (SelfVerify::enabled())
+            for (int dev : workerDevices) c.selfKey.emplace_back(new SelfVerify::Key(*hdr, zkey->getSectionData(3), zkey->getSectionSize(3), dev));
         // libzkhip copied everything it needs to the GPU: only the scalar header fields are kept
         // (the vk pointers into the mapping die with `zkey` and are never used again here)
         hdr->vk_alpha1 = hdr->vk_beta1 = hdr->vk_beta2 = hdr->vk_gamma2 = hdr->vk_delta1 = hdr->vk_delta2 = nullptr;
@@ -220,7 +222,12 @@ void FullProver::runSingle(JobPtr job) {
         }
         uint8_t r[32], s[32];
         const bool haveR = scalarFromEnv("ZKHIP_FIXED_R", r), haveS = scalarFromEnv("ZKHIP_FIXED_S", s);
-        if (run) proofJson = circuits[job->circuit].replica[0]->prove(job->wtnsData, haveR ? r : nullptr, haveS ? s : nullptr)->toJson();   // HOT PATH (fullprover.cpp:155)
+        if (run) {
+            Circuit &c = circuits[job->circuit];
+            auto proof = c.replica[0]->prove(job->wtnsData, haveR ? r : nullptr, haveS ? s : nullptr);   // HOT PATH (fullprover.cpp:155)
+            if (!c.selfKey.empty()) c.selfKey[0]->require(proof->raw, job->wtnsData);
+            proofJson = proof->toJson();
+        }
     } catch (std::exception &e) {   // reference catches runtime_error only: a JSON error kills it (Q3)
         error = e.what();
     }
@@ -426,25 +433,37 @@ void FullProver::deviceLoop(size_t worker) {
                 jobs = fifo.front();
             }
             std::vector<std::string> proofJson(jobs.size());
+            std::vector<std::string> refused(jobs.size());    // ZKHIP_SELFVERIFY: a job whose proof does not verify fails alone
             std::string error;
             try {
-                Groth16::Prover &pr = *circuits[jobs[0]->circuit].replica[worker];
-                if (jobs.size() == 1 && pr.batch() == 1) {
-                    proofJson[0] = pr.collect()->toJson();
-                } else {
-                    auto proofs = pr.collectBatch((uint32_t)jobs.size());
-                    for (size_t k = 0; k < jobs.size(); k++) proofJson[k] = proofs[k]->toJson();
+                Circuit &c = circuits[jobs[0]->circuit];
+                Groth16::Prover &pr = *c.replica[worker];
+                std::vector<std::unique_ptr<Groth16::Proof>> proofs;
+                if (jobs.size() == 1 && pr.batch() == 1) proofs.push_back(pr.collect());
+                else proofs = pr.collectBatch((uint32_t)jobs.size());
+                if (!c.selfKey.empty()) {                     // one verification call for the whole submission
+                    std::vector<zk_proof> raw(jobs.size());
+                    std::vector<const uint8_t *> wit(jobs.size());
+                    for (size_t k = 0; k < jobs.size(); k++) {
+                        raw[k] = proofs[k]->raw;
+                        wit[k] = jobs[k]->wtnsData;
+                    }
+                    const std::vector<uint8_t> v = c.selfKey[worker]->verdicts(raw.data(), wit.data(), jobs.size());
+                    for (size_t k = 0; k < jobs.size(); k++)
+                        if (v[k] != ZK_VERIFY_OK) refused[k] = SelfVerify::message(v[k]);
                 }
+                for (size_t k = 0; k < jobs.size(); k++) proofJson[k] = proofs[k]->toJson();
             } catch (std::exception &e) {
                 error = e.what();
             }
             {
                 std::lock_guard<std::mutex> guard(mtx);
                 for (size_t k = 0; k < jobs.size(); k++) {
+                    const std::string &why = error.empty() ? refused[k] : error;
                     jobs[k]->wtns.reset();
-                    jobs[k]->proof = error.empty() ? proofJson[k] : "null";
-                    jobs[k]->error = error;
-                    jobs[k]->status = error.empty() ? success : failed;
+                    jobs[k]->proof = why.empty() ? proofJson[k] : "null";
+                    jobs[k]->error = why;
+                    jobs[k]->status = why.empty() ? success : failed;
                 }
             }
             {

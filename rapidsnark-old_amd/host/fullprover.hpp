@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "groth16.hpp"
+#include "selfverify.hpp"
 #include "zkfile.hpp"
 
 class FullProver {
@@ -53,6 +54,7 @@ private:
     struct Circuit {
         std::vector<std::unique_ptr<Groth16::Prover>> replica;   // one per worker GPU
         std::unique_ptr<ZKeyUtils::Header> header;               // scalar fields only (vk pointers are cleared after create)
+        std::vector<std::unique_ptr<SelfVerify::Key>> selfKey;   // ZKHIP_SELFVERIFY: one per replica, made at load; else empty
     };
     struct Job {
         uint64_t id = 0;

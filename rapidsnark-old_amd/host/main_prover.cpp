@@ -6,21 +6,26 @@
 // Extras via the environment, so argv stays identical: ZKHIP_FIXED_R / ZKHIP_FIXED_S = 64 hex
 // digits (32-byte little-endian scalars) make the proof deterministic for parity tests;
 // ZKHIP_R1CS=<circuit.r1cs> checks, before proving, that the .zkey was made from that circuit and
-// that the witness satisfies every constraint (on failure: one line, exit -1, no output files).
+// that the witness satisfies every constraint (on failure: one line, exit -1, no output files);
+// ZKHIP_SELFVERIFY=1 verifies the proof against the .zkey's own verification key before either file is written (on
+// failure: "proof failed self-verification (verdict N)", exit -1, no output files).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
 #include <fstream>
 #include <iostream>
+#include <memory>
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <unistd.h>
 
 #include "cli.hpp"
 #include "groth16.hpp"
 #include "r1cs_check.hpp"
+#include "selfverify.hpp"
 #include "zkfile.hpp"
 
 namespace {
@@ -79,13 +84,17 @@ struct Lap {
 
 // ZKHIP_R1CS: the .r1cs must be the zkey's circuit (A and B as linear maps, zk_r1cs_match_zkey) and the witness must
 // satisfy it (zk_r1cs_check), on the device the prover will use; the checker is gone before the prover is created
-void check_against_r1cs(const char *r1csPath, BinFileUtils::BinFile &zkey, const ZKeyUtils::Header &zh, const uint8_t *witness) {
-    int32_t device = -1;
-    if (const char *dev = getenv("ZKHIP_DEVICE")) device = atoi(dev);
-    else if (const char *devs = getenv("ZKHIP_DEVICES")) {
+int32_t prover_device() {
+    if (const char *dev = getenv("ZKHIP_DEVICE")) return atoi(dev);
+    if (const char *devs = getenv("ZKHIP_DEVICES")) {
         const std::vector<int32_t> list = Groth16::parseDeviceList(devs);
-        if (!list.empty()) device = list[0];
+        if (!list.empty()) return list[0];
     }
+    return -1;
+}
+
+void check_against_r1cs(const char *r1csPath, BinFileUtils::BinFile &zkey, const ZKeyUtils::Header &zh, const uint8_t *witness) {
+    const int32_t device = prover_device();
     R1csCheck::Checker checker(r1csPath, device);
     zk_zkey_view v{};
     v.nVars = zh.nVars;
@@ -121,6 +130,24 @@ int run(const std::string &zkeyPath, const std::string &wtnsPath, const std::str
         check_against_r1cs(r1csPath, *zkey, *zh, static_cast<const uint8_t *>(wtns->getSectionData(2)));
         lap("r1cs check");
     }
+    // ZKHIP_SELFVERIFY: the verification key is made on a thread beside makeProver and joined after prove()
+    std::unique_ptr<SelfVerify::Key> selfKey;
+    std::exception_ptr selfKeyError;
+    std::thread selfKeyThread;
+    if (SelfVerify::enabled())
+        selfKeyThread = std::thread([&] {
+            try {
+                selfKey.reset(new SelfVerify::Key(*zh, zkey->getSectionData(3), zkey->getSectionSize(3), prover_device()));
+            } catch (...) {
+                selfKeyError = std::current_exception();
+            }
+        });
+    struct Joiner {
+        std::thread &t;
+        ~Joiner() {
+            if (t.joinable()) t.join();
+        }
+    } joiner{selfKeyThread};
     uint64_t bytes[6];
     for (uint32_t sec = 4; sec <= 9; sec++) bytes[sec - 4] = zkey->getSectionSize(sec);
     auto prover = Groth16::makeProver(zh->nVars, zh->nPublic, zh->domainSize, zh->nCoefs, zh->vk_alpha1, zh->vk_beta1, zh->vk_beta2,
@@ -139,6 +166,12 @@ int run(const std::string &zkeyPath, const std::string &wtnsPath, const std::str
     auto proof = prover->prove(witness, r ? r->b : nullptr, s ? s->b : nullptr);
 
     lap("prove");
+    if (selfKeyThread.joinable()) {
+        selfKeyThread.join();
+        if (selfKeyError) std::rethrow_exception(selfKeyError);
+        selfKey->require(proof->raw, witness);
+        lap("self-verify");
+    }
     write_text(proofPath, proof->toJson());
     write_text(publicPath, public_signals_json(witness, zh->nPublic));
     lap("write json");

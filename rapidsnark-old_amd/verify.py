@@ -107,6 +107,11 @@ def pairing(g1_bytes_, g2_bytes_, group=1, device=-1):
     return out
 
 
+def pairing_last_path():
+    """zk_pairing_last_path: 0 (a lane per group) or 1 (a workgroup per group) for this thread's last pairing(), -1 before the first."""
+    return int(L.load_library().zk_pairing_last_path())
+
+
 class VerificationKey:
     """A Groth16 verification key on the device (zk_vkey): .verify(proofs, publics) -> one verdict per proof."""
 
@@ -205,6 +210,15 @@ class VerificationKey:
         out = np.zeros(n, dtype=np.uint8)
         L.check(L.load_library().zk_vkey_verify(self._h, L._ptr(p) if n else None, L._ptr(s) if s.size else None, n, L._ptr(out) if n else None))
         return out
+
+    def info(self):
+        """zk_vkey_info: which path the last verify() took (last_path: 0 a lane per proof, 1 a workgroup per proof), the
+        threshold it used, its kernel launches, and the proofs sent down each path since the key was made."""
+        if not self._h:
+            raise L.ZkHipError("the verification key is closed")
+        plan = L.zk_vkey_plan()
+        L.check(L.load_library().zk_vkey_info(self._h, C.byref(plan)))
+        return {name: int(getattr(plan, name)) for name, _ in L.zk_vkey_plan._fields_ if name != "reserved"}
 
     def close(self):
         if getattr(self, "_h", None):
