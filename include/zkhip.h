@@ -494,7 +494,8 @@ void zk_vkey_destroy(zk_vkey *vk);
  * public signal not below r.  proofs: n x 256 bytes, A 64 | B 128 | C 64 (the layout of zk_proof); publics: n x nPublic x
  * 32 bytes little-endian standard form (may be NULL when nPublic = 0).  The return value tells only whether the call ran.
  * Proofs go through the device in chunks of ZKHIP_VERIFY_CHUNK (2^16 otherwise): the device memory held does not grow
- * with n.  Calls on one key are serialised.  Each proof gets its own verdict; nothing is batched by random combination. */
+ * with n.  Calls on one key are serialised.  Each proof gets its own verdict from its own equation; nothing is batched by random
+ * combination here (zk_vkey_verify_batch below does that, and still gives each proof its own verdict). */
 #define ZK_VERIFY_OK 0
 #define ZK_VERIFY_INVALID 1
 #define ZK_VERIFY_MALFORMED 2
@@ -515,6 +516,39 @@ typedef struct {
 } zk_vkey_plan;
 int zk_vkey_info(zk_vkey *vk, zk_vkey_plan *plan);
 int zk_pairing_last_path(void);   /* ZK_VERIFY_PATH_* of this thread's last zk_pairing, -1 before the first */
+
+/* Batch verification by random linear combination, every proof's own verdict kept.  Arguments, layouts, verdict codes and
+ * the return convention are zk_vkey_verify's.  Inside a chunk of ZKHIP_VERIFY_CHUNK proofs, consecutive proofs form groups
+ * of ZKHIP_VERIFY_GROUP (decimal, 1 to 2^24, read at every call, anything else is an error of the call; 1024 otherwise; a
+ * group never straddles a chunk and a chunk's last group may be short).  Malformed proofs are found first, by zk_vkey_verify's
+ * criteria, get MALFORMED and take no part in any sum.  With a scalar r_i per proof, R = sum r_i, S_j = sum r_i pub_ij,
+ * X = R IC_0 + sum S_j IC_j and Cs = sum r_i C_i over a group's well-formed proofs, the group passes iff
+ *     prod_i e(r_i A_i, B_i) e(-R alpha, beta) e(-X, gamma) e(-Cs, delta) = 1:
+ * one Miller loop and two 128-bit G1 multiplications per proof, one final exponentiation per group.  A passing group gives
+ * OK to its well-formed proofs.  The well-formed proofs of a failing group are verified one by one by zk_vkey_verify's own
+ * code (all failed groups of a chunk in one pass), which gives each OK or INVALID.  So a valid proof always gets OK, and an
+ * INVALID one gets OK only if its group passes, which at most one of the 2^128 - 1 values of its scalar allows: with
+ * scalars the prover cannot foresee, a probability of at most 1 / (2^128 - 1) per group.
+ * scalars16 is FOR TESTS ONLY: n x 16 bytes little-endian, r_i of proof i; a zero scalar is an error of the call.  NULL:
+ * the library draws them with getrandom() after the call has its inputs, 16 bytes each, redrawn while zero.  Scalars an
+ * adversary knows or can predict before fixing the proofs are unsound: two wrong proofs whose errors cancel under those
+ * scalars (r_i d_i + r_j d_j = 0) pass as a group and both get OK.  Never pass constants, counters or a seeded generator.
+ * report (may be NULL; set report->size = sizeof first, as for zk_zkey_verify_report): groups counts the groups with at
+ * least one well-formed proof, the ones whose equation was evaluated; proofs_rechecked the proofs sent through the
+ * per-proof code; launches every kernel launch of the call.  In zk_vkey_plan a batch call leaves last_path =
+ * ZK_VERIFY_PATH_BATCH and last_launches = report->launches; rechecked proofs ran on the per-proof paths and count in
+ * proofs_lanes / proofs_coop, the others in neither.  The lines of beta are made by a key's first batch call. */
+#define ZK_VERIFY_PATH_BATCH 2   /* the last call on the key was zk_vkey_verify_batch */
+typedef struct {
+    uint32_t size;              /* sizeof, set by the caller */
+    uint32_t group;             /* the group size the call used */
+    uint64_t groups, groups_failed;
+    uint64_t proofs_rechecked;  /* well-formed proofs of failed groups, sent through the per-proof path */
+    uint64_t malformed;
+    uint32_t launches, reserved;
+} zk_vkey_batch_report;
+int zk_vkey_verify_batch(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, const uint8_t *scalars16, uint8_t *verdict,
+                         zk_vkey_batch_report *report /* may be NULL */);
 
 /* ---- Powers of Tau: check (is the .ptau a sequence of powers of one tau, are its Lagrange sections its own) ---- */
 /* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the

@@ -30,6 +30,7 @@
 #include "pairing.hpp"
 #include "paircheck.hpp"
 #include "pairing_coop.hpp"
+#include "pairing_internal.hpp"
 
 namespace {
 
@@ -212,8 +213,10 @@ __global__ __launch_bounds__(64) void k_verify_final(uint8_t *verdict, const Fq1
     verdict[i] = f12_is_one(r) ? ZK_VERIFY_OK : ZK_VERIFY_INVALID;
 }
 
+}   // namespace
+
 // ---------------------------------------------------------------- host
-uint64_t chunk_jobs() {
+uint64_t zkp::chunk_jobs() {
     const char *e = getenv("ZKHIP_VERIFY_CHUNK");
     if (e && *e) {
         char *end = nullptr;
@@ -224,6 +227,14 @@ uint64_t chunk_jobs() {
     return DEFAULT_CHUNK;
 }
 
+void zkp::Consts::make(hipStream_t s) {
+    k.alloc(1);
+    ZK_LAUNCH(k_pair_consts, dim3(1), dim3(1), 0, s, k.p);
+    ZK_LAUNCH_OK("pairing constants");
+}
+
+namespace {
+
 // The largest calls that take the cooperative path (pairing_coop.hip), read at every call like the chunk.  The defaults are
 // the measured crossovers of profiles/verify_latency_timing.txt.
 constexpr uint64_t DEFAULT_VERIFY_COOP_MAX = 1024, DEFAULT_PAIRING_COOP_MAX = 256;
@@ -232,15 +243,6 @@ constexpr uint64_t COOP_MAX_PROOFS = 8192;            // lane way whatever the t
 uint64_t verify_coop_max() { return coop_threshold("ZKHIP_VERIFY_COOP_MAX", "proofs", DEFAULT_VERIFY_COOP_MAX); }
 uint64_t pairing_coop_max() { return coop_threshold("ZKHIP_PAIRING_COOP_MAX", "groups", DEFAULT_PAIRING_COOP_MAX); }
 thread_local int t_pairing_path = -1;
-
-struct Consts {
-    DevBuf<PairConsts> k;
-    void make(hipStream_t s) {
-        k.alloc(1);
-        ZK_LAUNCH(k_pair_consts, dim3(1), dim3(1), 0, s, k.p);
-        ZK_LAUNCH_OK("pairing constants");
-    }
-};
 
 // the three words of k_pair_check after the stream has drained
 struct CheckWords {
@@ -338,26 +340,6 @@ void pairing(uint8_t *out, const uint8_t *g1, const uint8_t *g2, uint64_t n_pair
 
 }   // namespace
 
-// The key on its device: IC, the line tables of gamma and delta, the Miller value of (alpha, beta), the constants.
-struct zk_vkey {
-    int device = 0;
-    uint32_t nPublic = 0;
-    std::mutex mu;                                    // calls on one key are serialised
-    Consts kc;
-    DevBuf<G1Affine> ic;
-    DevBuf<Line> tab;
-    DevBuf<Fq12> ml_ab;
-    // the cooperative path's own, kept between calls: a stream and buffers for `cap` proofs, grown when a call brings more
-    struct Coop {
-        std::unique_ptr<Stream> st;
-        DevBuf<uint8_t> dp, dv;
-        DevBuf<Fr> dpub;
-        DevBuf<Line> lines;
-        uint64_t cap = 0;
-    } coop;
-    zk_vkey_plan plan{};
-};
-
 namespace {
 
 bool all_zero(const void *p, size_t n) {
@@ -378,6 +360,8 @@ zk_vkey *vkey_create(const zk_vkey_view *v, int32_t device) {
     std::unique_ptr<zk_vkey> vk(new zk_vkey);
     vk->device = resolve_device(device);
     vk->nPublic = v->nPublic;
+    memcpy(vk->alpha_h, v->vk_alpha1, sizeof vk->alpha_h);
+    memcpy(vk->beta_h, v->vk_beta2, sizeof vk->beta_h);
     DeviceGuard g(vk->device);
     need_hbm("zk_vkey_create", n1 * sizeof(G1Affine) + 2 * MILLER_LINES * sizeof(Line) + 65536);
     Stream st;
@@ -421,11 +405,9 @@ zk_vkey *vkey_create(const zk_vkey_view *v, int32_t device) {
     return vk.release();
 }
 
-void vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict) {
-    if (!vk) throw std::invalid_argument("null argument");
-    if (!n) return;
-    if (!proofs || !verdict || (vk->nPublic && !publics)) throw std::invalid_argument("null argument");
-    std::lock_guard<std::mutex> lock(vk->mu);
+}   // namespace
+
+void zkp::vkey_verify_locked(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict) {
     const uint64_t coop_max = verify_coop_max();
     const uint64_t chunk = chunk_jobs(), cap = n < chunk ? n : chunk, pub_bytes = (uint64_t)vk->nPublic * 32;
     DeviceGuard g(vk->device);
@@ -483,6 +465,16 @@ void vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uin
         vk->plan.last_launches += 3;
         vk->plan.proofs_lanes += cnt;
     }
+}
+
+namespace {
+
+void vkey_verify(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, uint8_t *verdict) {
+    if (!vk) throw std::invalid_argument("null argument");
+    if (!n) return;
+    if (!proofs || !verdict || (vk->nPublic && !publics)) throw std::invalid_argument("null argument");
+    std::lock_guard<std::mutex> lock(vk->mu);
+    vkey_verify_locked(vk, proofs, publics, n, verdict);
 }
 
 }   // namespace

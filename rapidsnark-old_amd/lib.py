@@ -111,6 +111,11 @@ class zk_vkey_plan(C.Structure):
                 ("proofs_coop", C.c_uint64), ("proofs_lanes", C.c_uint64)]
 
 
+class zk_vkey_batch_report(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("group", C.c_uint32), ("groups", C.c_uint64), ("groups_failed", C.c_uint64),
+                ("proofs_rechecked", C.c_uint64), ("malformed", C.c_uint64), ("launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class zk_ptau_file_view(C.Structure):
     _fields_ = [("power", C.c_uint32), ("sec", C.c_void_p * 16), ("sec_bytes", C.c_uint64 * 16)]
 
@@ -198,12 +203,13 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare",
            "zk_g1_scale", "zk_g1_scale_plan", "zk_zkey_contribute_sizes", "zk_zkey_contribute",
            "zk_pairing", "zk_vkey_create", "zk_vkey_destroy", "zk_vkey_verify", "zk_vkey_info", "zk_pairing_last_path",
+           "zk_vkey_verify_batch",
            "zk_g2_in_subgroup", "zk_g1_power_msm", "zk_g2_power_msm", "zk_fr_power_dft", "zk_ptau_check_sizes", "zk_ptau_check",
            "zk_zkey_verify_sizes", "zk_zkey_verify",
            "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute"]
 ZK_SCALE_PLAN_MAX = 130
 ZK_VERIFY_OK, ZK_VERIFY_INVALID, ZK_VERIFY_MALFORMED = 0, 1, 2
-ZK_VERIFY_PATH_LANES, ZK_VERIFY_PATH_COOP = 0, 1
+ZK_VERIFY_PATH_LANES, ZK_VERIFY_PATH_COOP, ZK_VERIFY_PATH_BATCH = 0, 1, 2
 ZK_PTAU_OK, ZK_PTAU_INVALID, ZK_PTAU_MALFORMED = 0, 1, 2
 
 
@@ -310,6 +316,8 @@ def load_library():
         lib.zk_vkey_info.argtypes = [C.c_void_p, C.POINTER(zk_vkey_plan)]
         lib.zk_pairing_last_path.argtypes = []
         lib.zk_pairing_last_path.restype = C.c_int
+    if hasattr(lib, "zk_vkey_verify_batch"):
+        lib.zk_vkey_verify_batch.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p, u8p, C.POINTER(zk_vkey_batch_report)]
     if hasattr(lib, "zk_ptau_check"):
         lib.zk_g2_in_subgroup.argtypes = [u8p, u8p, C.c_uint64, C.c_int32]
         lib.zk_g1_power_msm.argtypes = [u8p, u8p, C.c_uint64, u8p, C.c_uint64, C.c_int32]

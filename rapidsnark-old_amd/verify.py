@@ -211,6 +211,36 @@ class VerificationKey:
         L.check(L.load_library().zk_vkey_verify(self._h, L._ptr(p) if n else None, L._ptr(s) if s.size else None, n, L._ptr(out) if n else None))
         return out
 
+    def verify_batch(self, proofs, publics=b"", scalars=None):
+        """zk_vkey_verify_batch: verify()'s arguments -> (verdicts, report).  Groups of ZKHIP_VERIFY_GROUP proofs are checked by
+        one random linear combination each and only the proofs of a failing group one by one: the same verdicts as verify()
+        except that an INVALID proof is taken for OK with probability at most 2^-128 per group.  report: dict of
+        zk_vkey_batch_report (group, groups, groups_failed, proofs_rechecked, malformed, launches).
+        scalars is for tests only: n x 16 bytes little-endian, one non-zero scalar per proof.  None, the only sound choice
+        outside a test, lets the library draw them from the system's random source."""
+        if not self._h:
+            raise L.ZkHipError("the verification key is closed")
+        p, s = L._buf(proofs), L._buf(publics)
+        if p.size % 256:
+            raise ValueError("proofs: a multiple of 256 bytes expected")
+        n = p.size // 256
+        if s.size != n * self.n_public * 32:
+            raise ValueError("publics: %d proofs x %d signals x 32 bytes expected, got %d bytes" % (n, self.n_public, s.size))
+        r = None
+        if scalars is not None:
+            r = L._buf(scalars)
+            if r.size != n * 16:
+                raise ValueError("scalars: %d proofs x 16 bytes expected, got %d bytes" % (n, r.size))
+        fn = getattr(L.load_library(), "zk_vkey_verify_batch", None)
+        if fn is None:
+            raise L.ZkHipError("zk_vkey_verify_batch is not in this build of libzkhip.so")
+        out = np.zeros(n, dtype=np.uint8)
+        rep = L.zk_vkey_batch_report()
+        rep.size = C.sizeof(L.zk_vkey_batch_report)
+        L.check(fn(self._h, L._ptr(p) if n else None, L._ptr(s) if s.size else None, n, L._ptr(r) if r is not None and n else None,
+                   L._ptr(out) if n else None, C.byref(rep)))
+        return out, {name: int(getattr(rep, name)) for name, _ in L.zk_vkey_batch_report._fields_ if name not in ("size", "reserved")}
+
     def info(self):
         """zk_vkey_info: which path the last verify() took (last_path: 0 a lane per proof, 1 a workgroup per proof), the
         threshold it used, its kernel launches, and the proofs sent down each path since the key was made."""
