@@ -550,6 +550,40 @@ typedef struct {
 int zk_vkey_verify_batch(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, const uint8_t *scalars16, uint8_t *verdict,
                          zk_vkey_batch_report *report /* may be NULL */);
 
+/* A key set: proofs under many keys in one call.  A set is a handle over existing zk_vkey objects of one device (n_keys >= 1;
+ * keys on two devices are an error that names both; a key may appear twice).  The keys are borrowed, not copied: the set
+ * keeps a device array with one record per key (the addresses of its IC, of its line tables and of its Miller value of
+ * (alpha, beta), and its nPublic), so a key must outlive every set that names it.  zk_vkey_set_verify gives proof i the
+ * verdict zk_vkey_verify gives it under key key_of[i] (the same checks, equation and codes; a proof under the wrong key of
+ * the same nPublic is INVALID, not an error), and the number of kernel launches of a call depends neither on n_keys nor
+ * on how the proofs are spread over the keys.  proofs: n x 256 bytes as for zk_vkey_verify; key_of: n indices below n_keys;
+ * publics: the signals of proof 0, then of proof 1, ...: proof i contributes nPublic(key_of[i]) x 32 bytes, a key without
+ * public signals nothing; publics_bytes must be that total (publics may be NULL when it is 0).  Errors of the call, found
+ * before any launch: a key_of entry out of range (the message names the first index), a wrong publics_bytes (expected and
+ * given), a null argument.  The return value tells only whether the call ran; n = 0 is a successful no-op.
+ * ZKHIP_VERIFY_COOP_MAX and ZKHIP_VERIFY_CHUNK are read at every call with zk_vkey_verify's meaning and error rules: up to
+ * the threshold a workgroup per proof in one launch (k_set_coop), above it a lane per proof in chunks (k_set_check /
+ * _miller / _final, three launches a chunk), the device memory held not growing with n.  On the lane path the host groups
+ * a chunk's proofs by key and pads every key's run to whole waves (at most 63 idle lanes per key and chunk), so a wave has
+ * one key; verdicts return to the caller's positions.  Calls on one set are serialised by the set's own mutex; the keys'
+ * device data never changes after zk_vkey_create, so no key's mutex is taken and every key's zk_vkey_plan is left as it
+ * was.  Not here: random combination across keys (zk_vkey_verify_batch stays single-key), more than one device.
+ * zk_vkey_set_info: set plan->size = sizeof first, as for zk_vkey_batch_report. */
+typedef struct zk_vkey_set zk_vkey_set;
+typedef struct {
+    uint32_t size;              /* sizeof, set by the caller */
+    uint32_t n_keys;
+    uint32_t last_path;         /* ZK_VERIFY_PATH_COOP or _LANES of the last zk_vkey_set_verify on this set */
+    uint32_t last_launches;     /* kernel launches of that call */
+    uint64_t last_waves_padded; /* waves of that call with idle lanes: key runs that did not end on a wave border; 0 on the cooperative path */
+    uint64_t proofs_coop, proofs_lanes;   /* totals since zk_vkey_set_create */
+} zk_vkey_set_plan;
+int zk_vkey_set_create(zk_vkey_set **out, zk_vkey *const *keys, uint32_t n_keys);
+void zk_vkey_set_destroy(zk_vkey_set *set);
+int zk_vkey_set_verify(zk_vkey_set *set, const uint8_t *proofs, const uint32_t *key_of, const uint8_t *publics, uint64_t publics_bytes, uint64_t n,
+                       uint8_t *verdict);
+int zk_vkey_set_info(zk_vkey_set *set, zk_vkey_set_plan *plan);
+
 /* ---- Powers of Tau: check (is the .ptau a sequence of powers of one tau, are its Lagrange sections its own) ---- */
 /* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the
  * counterpart is the arithmetic half of snarkjs `powersoftau verify`.  The contribution transcript (section 7) is not read.

@@ -29,23 +29,20 @@
 #include "ptcheck.hpp"
 #include "pairing.hpp"
 #include "paircheck.hpp"
+#include "verify_lanes.hpp"
 #include "pairing_coop.hpp"
 #include "pairing_internal.hpp"
 
 namespace {
 
 constexpr uint64_t DEFAULT_CHUNK = 1ull << 16;        // jobs per chunk
+// The largest calls that take the cooperative path (pairing_coop.hip), read at every call like the chunk.  The defaults are
+// the measured crossovers of profiles/verify_latency_timing.txt.
+constexpr uint64_t DEFAULT_VERIFY_COOP_MAX = 1024, DEFAULT_PAIRING_COOP_MAX = 256;
 
 static_assert(sizeof(G1Affine) == 64 && sizeof(G2Affine) == 128 && sizeof(Fq12) == 384 && sizeof(G2Proj) == 192 && sizeof(Line) == 192, "layout");
 
-// ---------------------------------------------------------------- device: checks
-__device__ __noinline__ bool in_subgroup(const G2Affine &Q) {   // [r] Q = infinity
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = FrParams::P[i];
-    return scalar_mul_affine(Q, r).is_inf();
-}
-
+// ---------------------------------------------------------------- device: checks (in_subgroup: verify_lanes.hpp)
 // err[0]: the lowest G1 index off the curve, err[1]: the lowest G2 index off the twist, err[2]: the lowest G2 index
 // outside the subgroup (NO_BAD_POINT: none).  The all-zero encoding (infinity) passes.
 __global__ __launch_bounds__(64) void k_pair_check(uint32_t *err, const G1Affine *__restrict__ g1, uint64_t n1, const G2Affine *__restrict__ g2,
@@ -137,24 +134,7 @@ __global__ __launch_bounds__(64) void k_verify_check(uint32_t *status, G1Affine 
                                                      uint64_t n, uint32_t nPublic, const G1Affine *__restrict__ ic, Fq b1, Fq2 b2) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint8_t *pr = proofs + i * 256;
-    const G1Affine A = load_pt(reinterpret_cast<const G1Affine *>(pr));
-    const G2Affine B = load_pt(reinterpret_cast<const G2Affine *>(pr + 64));
-    const G1Affine C = load_pt(reinterpret_cast<const G1Affine *>(pr + 192));
-    bool ok = !A.is_inf() && !B.is_inf() && !C.is_inf() && on_curve(A, b1) && on_curve(C, b1) && on_curve(B, b2);
-    const Fr *pub = publics + i * nPublic;
-    for (uint32_t j = 0; ok && j < nPublic; j++) ok = below_r(load_el(pub + j));
-    if (ok) ok = in_subgroup(B);
-    status[i] = ok ? ST_OK : ST_MALFORMED;
-    if (!ok) return;
-    G1XYZZ acc = G1XYZZ::from_affine(load_pt(ic));
-    for (uint32_t j = 0; j < nPublic; j++) {
-        const G1XYZZ t = scalar_mul_affine(load_pt(ic + 1 + j), load_el(pub + j));
-        add(acc, t);
-    }
-    const G1Affine X = g1_to_affine(acc);
-    store_el(&vkx[i].x, X.x);
-    store_el(&vkx[i].y, X.y);
+    verify_check_lane(status + i, vkx + i, proofs + i * 256, publics + i * nPublic, nPublic, ic, b1, b2);
 }
 
 // f_out[i] = miller(-A, B) miller(vk_x, gamma) miller(C, delta) miller(alpha, beta); tab: gamma's lines, then delta's
@@ -163,54 +143,13 @@ __global__ __launch_bounds__(64) void k_verify_miller(Fq12 *f_out, const uint32_
                                                       const PairConsts *k) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || status[i] != ST_OK) return;
-    const uint8_t *pr = proofs + i * 256;
-    G1Affine A = load_pt(reinterpret_cast<const G1Affine *>(pr));
-    A.y = Fq::neg(A.y);
-    const G2Affine B = load_pt(reinterpret_cast<const G2Affine *>(pr + 64));
-    const G1Affine C = load_pt(reinterpret_cast<const G1Affine *>(pr + 192));
-    const G1Affine X = load_pt(vkx + i);
-    const bool have_x = !X.is_inf();
-    const Line *tg = tab, *td = tab + MILLER_LINES;
-    G2Proj T{B.x, B.y, Fq2::one()};
-    G2Affine q1, q2;
-    frob_twist(q1, q2, B, *k);
-    Fq12 f;
-    f12_one(f);
-    Line l;
-    int at = 0;                                       // wave-uniform: the index into both tables
-    auto lines = [&]() {                              // the line just made at -A, and the tables' lines at vk_x and C
-        f12_mul_line_at(f, l, A);
-        if (have_x) f12_mul_line_at(f, tg[at], X);
-        f12_mul_line_at(f, td[at], C);
-        at++;
-    };
-    for (int s = 0; s < 64; s++) {
-        f12_sqr(f, f);
-        step_dbl(T, l, *k);
-        lines();
-        if (ate_bit(s)) {
-            step_add(T, l, B);
-            lines();
-        }
-    }
-    step_add(T, l, q1);
-    lines();
-    step_add(T, l, q2);
-    lines();
-    f12_mul(f, f, *ml_ab);
-    f_out[i] = f;
+    verify_miller_lane(f_out + i, proofs + i * 256, vkx + i, tab, ml_ab, k);
 }
 
 __global__ __launch_bounds__(64) void k_verify_final(uint8_t *verdict, const Fq12 *f, const uint32_t *__restrict__ status, uint64_t n, const PairConsts *k) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (status[i] != ST_OK) {
-        verdict[i] = ZK_VERIFY_MALFORMED;
-        return;
-    }
-    Fq12 r;
-    final_exp(r, f[i], *k);
-    verdict[i] = f12_is_one(r) ? ZK_VERIFY_OK : ZK_VERIFY_INVALID;
+    verify_final_lane(verdict + i, f + i, status[i], k);
 }
 
 }   // namespace
@@ -227,6 +166,8 @@ uint64_t zkp::chunk_jobs() {
     return DEFAULT_CHUNK;
 }
 
+uint64_t zkp::verify_coop_max() { return coop_threshold("ZKHIP_VERIFY_COOP_MAX", "proofs", DEFAULT_VERIFY_COOP_MAX); }
+
 void zkp::Consts::make(hipStream_t s) {
     k.alloc(1);
     ZK_LAUNCH(k_pair_consts, dim3(1), dim3(1), 0, s, k.p);
@@ -235,12 +176,8 @@ void zkp::Consts::make(hipStream_t s) {
 
 namespace {
 
-// The largest calls that take the cooperative path (pairing_coop.hip), read at every call like the chunk.  The defaults are
-// the measured crossovers of profiles/verify_latency_timing.txt.
-constexpr uint64_t DEFAULT_VERIFY_COOP_MAX = 1024, DEFAULT_PAIRING_COOP_MAX = 256;
-constexpr uint64_t COOP_MAX_PAIRS = 8192;             // 19 KiB of lines a pair or a proof: a call with more of them goes the
-constexpr uint64_t COOP_MAX_PROOFS = 8192;            // lane way whatever the threshold, in chunks and constant memory
-uint64_t verify_coop_max() { return coop_threshold("ZKHIP_VERIFY_COOP_MAX", "proofs", DEFAULT_VERIFY_COOP_MAX); }
+constexpr uint64_t COOP_MAX_PAIRS = 8192;             // 19 KiB of lines a pair or a proof (COOP_MAX_PROOFS): a call with more of
+                                                      // them goes the lane way whatever the threshold, in chunks and constant memory
 uint64_t pairing_coop_max() { return coop_threshold("ZKHIP_PAIRING_COOP_MAX", "groups", DEFAULT_PAIRING_COOP_MAX); }
 thread_local int t_pairing_path = -1;
 

@@ -1,6 +1,7 @@
 // What the translation units of the verification entry points share on the host: the key object, the constants' holder,
-// the chunk size and the per-proof pass that pairing.hip defines and pairing_batch.hip sends the proofs of failed groups
-// through.  No kernel is declared here: each unit keeps its own.
+// the chunk size, the cooperative threshold (pairing_set.hip reads both as zk_vkey_verify does) and the per-proof pass that
+// pairing.hip defines and pairing_batch.hip sends the proofs of failed groups through.  No kernel is declared here: each unit
+// keeps its own.
 #pragma once
 #include <memory>
 #include <mutex>
@@ -16,6 +17,8 @@ struct Consts {
 };
 
 uint64_t chunk_jobs();                                // ZKHIP_VERIFY_CHUNK, read at every call (pairing.hip)
+uint64_t verify_coop_max();                           // ZKHIP_VERIFY_COOP_MAX, read at every call (pairing.hip)
+constexpr uint64_t COOP_MAX_PROOFS = 8192;            // 19 KiB of lines a proof: a call with more of them goes the lane way whatever the threshold
 
 }   // namespace zkp
 

@@ -121,6 +121,7 @@ class VerificationKey:
             raise ValueError("verification key: alpha 64 bytes, beta, gamma, delta 128 bytes each, IC (nPublic + 1) x 64 bytes expected")
         self.alpha1, self.beta2, self.gamma2, self.delta2, self.ic = bytes(alpha1), bytes(beta2), bytes(gamma2), bytes(delta2), ic
         self.n_public = len(ic) // 64 - 1
+        self.device = int(device)                     # as given: -1 is the device that was current
         self._h = C.c_void_p()
         lib = L.load_library()
         if not hasattr(lib, "zk_vkey_create"):
@@ -254,6 +255,91 @@ class VerificationKey:
         if getattr(self, "_h", None):
             L.load_library().zk_vkey_destroy(self._h)
             self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VerificationKeySet:
+    """Proofs under many keys in one call (zk_vkey_set): a handle over VerificationKey objects of one device.
+    .verify(proofs, key_of, publics) gives proof i the verdict keys[key_of[i]].verify gives it, and the number of kernel
+    launches does not depend on the number of keys.  The set holds references to its keys: they live as long as it does
+    (closing one of them while the set is open is the caller's error).  A key may appear twice."""
+
+    def __init__(self, keys):
+        keys = list(keys)
+        if not keys:
+            raise ValueError("a key set needs at least one key")
+        for j, k in enumerate(keys):
+            if not isinstance(k, VerificationKey):
+                raise ValueError("key %d is not a VerificationKey" % j)
+            if not k._h:
+                raise ValueError("key %d is closed" % j)
+        # keys made for the current device (-1) are left to the library, which knows where they are and names both devices
+        named = sorted({k.device for k in keys if k.device >= 0})
+        if len(named) > 1:
+            raise ValueError("the keys of a set are on one device; these are on devices %s" % ", ".join(map(str, named)))
+        self.keys = keys
+        self.n_public = np.array([k.n_public for k in keys], dtype=np.int64)
+        self._h = C.c_void_p()
+        fn = getattr(L.load_library(), "zk_vkey_set_create", None)
+        if fn is None:
+            raise L.ZkHipError("zk_vkey_set_create is not in this build of libzkhip.so")
+        arr = (C.c_void_p * len(keys))(*[k._h.value for k in keys])
+        L.check(fn(C.byref(self._h), arr, len(keys)))
+
+    def verify(self, proofs, key_of, publics=b""):
+        """proofs: n x 256 bytes; key_of: n indices into the set's keys (any integer sequence or array); publics: the
+        signals of proof 0, then of proof 1, ...: proof i has keys[key_of[i]].n_public of them, 32 bytes each
+        -> numpy uint8 [n] of VERIFY_OK / VERIFY_INVALID / VERIFY_MALFORMED"""
+        if not self._h:
+            raise L.ZkHipError("the key set is closed")
+        p, s = L._buf(proofs), L._buf(publics)
+        if p.size % 256:
+            raise ValueError("proofs: a multiple of 256 bytes expected")
+        n = p.size // 256
+        ko = np.asarray(key_of)
+        if ko.ndim != 1 or ko.size != n:
+            raise ValueError("key_of: %d indices expected, one per proof, got %s" % (n, "x".join(map(str, ko.shape)) or "a scalar"))
+        if n and ko.dtype.kind not in "iu":
+            raise ValueError("key_of: integers expected, got %s" % ko.dtype)
+        ko = ko.astype(np.int64) if n else np.zeros(0, dtype=np.int64)
+        bad = np.flatnonzero((ko < 0) | (ko >= len(self.keys)))
+        if bad.size:
+            raise ValueError("key_of[%d] = %d: the set holds %d keys" % (bad[0], ko[bad[0]], len(self.keys)))
+        want = int(self.n_public[ko].sum()) * 32
+        if s.size != want:
+            raise ValueError("publics: %d bytes expected (%d signals of 32 bytes for these keys), got %d bytes" % (want, want // 32, s.size))
+        ko = np.ascontiguousarray(ko, dtype=np.uint32)
+        out = np.zeros(n, dtype=np.uint8)
+        L.check(L.load_library().zk_vkey_set_verify(self._h, L._ptr(p) if n else None, L._ptr(ko) if n else None, L._ptr(s) if s.size else None,
+                                                    s.size, n, L._ptr(out) if n else None))
+        return out
+
+    def info(self):
+        """zk_vkey_set_info: n_keys, the path of the last verify() (last_path: 0 a lane per proof, 1 a workgroup per proof),
+        its kernel launches, its waves with idle lanes, and the proofs sent down each path since the set was made."""
+        if not self._h:
+            raise L.ZkHipError("the key set is closed")
+        plan = L.zk_vkey_set_plan()
+        plan.size = C.sizeof(L.zk_vkey_set_plan)
+        L.check(L.load_library().zk_vkey_set_info(self._h, C.byref(plan)))
+        return {name: int(getattr(plan, name)) for name, _ in L.zk_vkey_set_plan._fields_ if name != "size"}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.load_library().zk_vkey_set_destroy(self._h)
+            self._h = C.c_void_p()
+        self.keys = []
 
     def __enter__(self):
         return self
