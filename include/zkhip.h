@@ -567,13 +567,13 @@ int zk_vkey_verify_batch(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publ
  * a chunk's proofs by key and pads every key's run to whole waves (at most 63 idle lanes per key and chunk), so a wave has
  * one key; verdicts return to the caller's positions.  Calls on one set are serialised by the set's own mutex; the keys'
  * device data never changes after zk_vkey_create, so no key's mutex is taken and every key's zk_vkey_plan is left as it
- * was.  Not here: random combination across keys (zk_vkey_verify_batch stays single-key), more than one device.
+ * was.  Not here: more than one device.
  * zk_vkey_set_info: set plan->size = sizeof first, as for zk_vkey_batch_report. */
 typedef struct zk_vkey_set zk_vkey_set;
 typedef struct {
     uint32_t size;              /* sizeof, set by the caller */
     uint32_t n_keys;
-    uint32_t last_path;         /* ZK_VERIFY_PATH_COOP or _LANES of the last zk_vkey_set_verify on this set */
+    uint32_t last_path;         /* ZK_VERIFY_PATH_COOP or _LANES of the last zk_vkey_set_verify on this set, _BATCH after zk_vkey_set_verify_batch */
     uint32_t last_launches;     /* kernel launches of that call */
     uint64_t last_waves_padded; /* waves of that call with idle lanes: key runs that did not end on a wave border; 0 on the cooperative path */
     uint64_t proofs_coop, proofs_lanes;   /* totals since zk_vkey_set_create */
@@ -583,6 +583,45 @@ void zk_vkey_set_destroy(zk_vkey_set *set);
 int zk_vkey_set_verify(zk_vkey_set *set, const uint8_t *proofs, const uint32_t *key_of, const uint8_t *publics, uint64_t publics_bytes, uint64_t n,
                        uint8_t *verdict);
 int zk_vkey_set_info(zk_vkey_set *set, zk_vkey_set_plan *plan);
+
+/* Batch verification across a key set: zk_vkey_verify_batch's random combination over proofs under many keys, every
+ * proof's own verdict kept.  Layouts, verdict codes, the errors found before any launch and the return convention are
+ * zk_vkey_set_verify's.  Inside a chunk of ZKHIP_VERIFY_CHUNK proofs the proofs are ordered by key (keys rising, a key's
+ * proofs in the caller's order); in that order consecutive proofs form groups.  A group closes when it holds
+ * ZKHIP_VERIFY_GROUP proofs (zk_vkey_verify_batch's switch and error rules), and also when the next proof would bring a key
+ * beyond the ZKHIP_VERIFY_GROUP_KEYS-th distinct key into it (decimal, 1 to 65536, read at every call, anything else is
+ * an error of the call; 1 otherwise, the measured default: groups of one key each, all keys still in one launch set;
+ * DESIGN.md section 25 has the sweep).  The proofs of one key inside one group are a segment; a group never straddles
+ * a chunk, a key's run may straddle groups and chunks.  Malformed proofs are found first, by zk_vkey_verify's criteria, get
+ * MALFORMED and take no part in any sum.  With a scalar r_i per proof, over the well-formed proofs of segment s (key k)
+ * R_s = sum r_i, S_sj = sum r_i pub_ij, X_s = R_s IC_0 + sum_j S_sj IC_(j+1) and Cs_s = sum r_i C_i, and the group passes iff
+ *     prod_i e(r_i A_i, B_i) prod_s [ e(-R_s alpha_k, beta_k) e(-X_s, gamma_k) e(-Cs_s, delta_k) ] = 1:
+ * one Miller loop and two 128-bit G1 multiplications per proof, three table walks per segment, one final exponentiation
+ * per group.  A passing group gives OK to its well-formed proofs.  The well-formed proofs of all failing groups of a chunk
+ * are verified one by one by zk_vkey_set_verify's own code in one pass, which gives each OK or INVALID.  So a valid proof
+ * always gets OK, and an INVALID one gets OK only if its group passes: with scalars the prover cannot foresee, a
+ * probability of at most 1 / (2^128 - 1) per group, whatever keys the group's proofs belong to.
+ * scalars16 is FOR TESTS ONLY, as for zk_vkey_verify_batch: n x 16 bytes little-endian, r_i of proof i; a zero scalar is
+ * an error of the call that names its index.  NULL: the library draws them with getrandom() per chunk, after the call has
+ * its inputs.  Scalars an adversary knows or can predict before fixing the proofs are unsound: wrong proofs whose errors
+ * cancel under those scalars, under one key or across two keys of one group, pass and all get OK.  Never pass constants,
+ * counters or a seeded generator.
+ * report (may be NULL; set report->size = sizeof first): groups and segments count those with at least one well-formed
+ * proof, the ones evaluated; launches every kernel launch of the call.  In zk_vkey_set_plan a batch call leaves last_path
+ * = ZK_VERIFY_PATH_BATCH, last_launches = report->launches and last_waves_padded = 0; rechecked proofs count in
+ * proofs_coop / proofs_lanes, the others in neither.  The set's first batch call makes alpha and the lines of beta of
+ * every key on the device in one launch (19 KiB a key), from bytes copied when the set was made: as for
+ * zk_vkey_set_verify, the set's mutex alone is taken and every key's zk_vkey_plan is left as it was. */
+typedef struct {
+    uint32_t size;                 /* sizeof, set by the caller */
+    uint32_t group, group_keys;    /* the two limits the call used */
+    uint32_t launches;
+    uint64_t groups, groups_failed, segments;   /* groups / segments with a well-formed proof */
+    uint64_t proofs_rechecked, malformed;
+} zk_vkey_set_batch_report;
+int zk_vkey_set_verify_batch(zk_vkey_set *set, const uint8_t *proofs, const uint32_t *key_of, const uint8_t *publics, uint64_t publics_bytes, uint64_t n,
+                             const uint8_t *scalars16 /* tests only; NULL: getrandom inside the call */,
+                             uint8_t *verdict, zk_vkey_set_batch_report *report /* may be NULL */);
 
 /* ---- Powers of Tau: check (is the .ptau a sequence of powers of one tau, are its Lagrange sections its own) ---- */
 /* Nothing in the reference corresponds to these entry points (it reads a finished .zkey, src/main_prover.cpp:57-72); the

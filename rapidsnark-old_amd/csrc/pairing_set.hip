@@ -24,21 +24,15 @@
 #include "hiputil.hpp"
 #include "verify_lanes.hpp"
 #include "pairing_coop_dev.hpp"
-#include "pairing_internal.hpp"
+#include "pairing_set_internal.hpp"
 
 namespace {
 
-struct KeyRec {                                       // a key as the kernels see it
-    const G1Affine *ic;
-    const Line *tab;                                  // gamma's lines, then delta's
-    const Fq12 *ml_ab;
-    uint32_t nPublic, reserved;
-};
 struct WaveRec {                                      // a wave of the lane path: `cnt` proofs of key `key` in its first lanes
     uint64_t pub_at;                                  // where the first lane's signals begin, in signals from the chunk's first
     uint32_t key, cnt;
 };
-static_assert(sizeof(KeyRec) == 32 && sizeof(WaveRec) == 16, "layout");
+static_assert(sizeof(WaveRec) == 16, "layout");
 
 // ---------------------------------------------------------------- a lane per proof, a wave per run of one key
 // Slot i = 64 blockIdx.x + threadIdx.x of the staged chunk.  The grid is the chunk's waves exactly; w and key are the same
@@ -83,25 +77,6 @@ __global__ __launch_bounds__(VERIFY_THREADS) void k_set_coop(uint8_t *verdict, c
 }   // namespace
 
 // ---------------------------------------------------------------- host
-struct zk_vkey_set {
-    int device = 0;
-    std::mutex mu;                                    // calls on one set are serialised; no key's mutex is taken
-    std::vector<uint32_t> nPublic;                    // per key
-    Consts kc;
-    DevBuf<KeyRec> recs;
-    // the cooperative path's own, kept between calls: a stream and buffers for `cap` proofs with `cap_pub` signals
-    struct Coop {
-        std::unique_ptr<Stream> st;
-        DevBuf<uint8_t> dp, dv;
-        DevBuf<Fr> dpub;
-        DevBuf<uint32_t> dkey;
-        DevBuf<uint64_t> dat;
-        DevBuf<Line> lines;
-        uint64_t cap = 0, cap_pub = 0;
-    } coop;
-    zk_vkey_set_plan plan{};
-};
-
 namespace {
 
 zk_vkey_set *set_create(zk_vkey *const *keys, uint32_t n_keys) {
@@ -120,6 +95,8 @@ zk_vkey_set *set_create(zk_vkey *const *keys, uint32_t n_keys) {
     for (uint32_t j = 0; j < n_keys; j++) {
         recs[j] = KeyRec{keys[j]->ic.p, keys[j]->tab.p, keys[j]->ml_ab.p, keys[j]->nPublic, 0};
         set->nPublic.push_back(keys[j]->nPublic);
+        set->alpha_h.insert(set->alpha_h.end(), keys[j]->alpha_h, keys[j]->alpha_h + 64);
+        set->beta_h.insert(set->beta_h.end(), keys[j]->beta_h, keys[j]->beta_h + 128);
     }
     DeviceGuard g(set->device);
     Stream st;
@@ -278,13 +255,18 @@ void set_verify(zk_vkey_set *set, const uint8_t *proofs, const uint32_t *key_of,
                                     " signals of 32 bytes), " + std::to_string(publics_bytes) + " given");
     if (total && !publics) throw std::invalid_argument("null argument");
     std::lock_guard<std::mutex> lock(set->mu);
-    const uint64_t coop_max = verify_coop_max(), chunk = chunk_jobs();
     DeviceGuard g(set->device);
-    if (n <= coop_max && n <= COOP_MAX_PROOFS) set_verify_coop(set, proofs, key_of, publics, at, n, verdict);
-    else set_verify_lanes(set, proofs, key_of, publics, at, n, verdict, chunk);
+    set_verify_locked(set, proofs, key_of, publics, at, n, verdict);
 }
 
 }   // namespace
+
+void zkp::set_verify_locked(zk_vkey_set *set, const uint8_t *proofs, const uint32_t *key_of, const uint8_t *publics, const std::vector<uint64_t> &at, uint64_t n,
+                            uint8_t *verdict) {
+    const uint64_t coop_max = verify_coop_max(), chunk = chunk_jobs();
+    if (n <= coop_max && n <= COOP_MAX_PROOFS) set_verify_coop(set, proofs, key_of, publics, at, n, verdict);
+    else set_verify_lanes(set, proofs, key_of, publics, at, n, verdict, chunk);
+}
 
 extern "C" {
 

@@ -121,6 +121,12 @@ class zk_vkey_set_plan(C.Structure):
                 ("last_waves_padded", C.c_uint64), ("proofs_coop", C.c_uint64), ("proofs_lanes", C.c_uint64)]
 
 
+class zk_vkey_set_batch_report(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("group", C.c_uint32), ("group_keys", C.c_uint32), ("launches", C.c_uint32),
+                ("groups", C.c_uint64), ("groups_failed", C.c_uint64), ("segments", C.c_uint64),
+                ("proofs_rechecked", C.c_uint64), ("malformed", C.c_uint64)]
+
+
 class zk_ptau_file_view(C.Structure):
     _fields_ = [("power", C.c_uint32), ("sec", C.c_void_p * 16), ("sec_bytes", C.c_uint64 * 16)]
 
@@ -208,7 +214,7 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_g1_lagrange", "zk_g2_lagrange", "zk_ptau_prepare_sizes", "zk_ptau_prepare",
            "zk_g1_scale", "zk_g1_scale_plan", "zk_zkey_contribute_sizes", "zk_zkey_contribute",
            "zk_pairing", "zk_vkey_create", "zk_vkey_destroy", "zk_vkey_verify", "zk_vkey_info", "zk_pairing_last_path",
-           "zk_vkey_verify_batch", "zk_vkey_set_create", "zk_vkey_set_destroy", "zk_vkey_set_verify", "zk_vkey_set_info",
+           "zk_vkey_verify_batch", "zk_vkey_set_create", "zk_vkey_set_destroy", "zk_vkey_set_verify", "zk_vkey_set_info", "zk_vkey_set_verify_batch",
            "zk_g2_in_subgroup", "zk_g1_power_msm", "zk_g2_power_msm", "zk_fr_power_dft", "zk_ptau_check_sizes", "zk_ptau_check",
            "zk_zkey_verify_sizes", "zk_zkey_verify",
            "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute"]
@@ -329,6 +335,9 @@ def load_library():
         lib.zk_vkey_set_destroy.restype = None
         lib.zk_vkey_set_verify.argtypes = [C.c_void_p, u8p, C.c_void_p, u8p, C.c_uint64, C.c_uint64, u8p]
         lib.zk_vkey_set_info.argtypes = [C.c_void_p, C.POINTER(zk_vkey_set_plan)]
+    if hasattr(lib, "zk_vkey_set_verify_batch"):
+        lib.zk_vkey_set_verify_batch.argtypes = [C.c_void_p, u8p, C.c_void_p, u8p, C.c_uint64, C.c_uint64, u8p, u8p,
+                                                 C.POINTER(zk_vkey_set_batch_report)]
     if hasattr(lib, "zk_ptau_check"):
         lib.zk_g2_in_subgroup.argtypes = [u8p, u8p, C.c_uint64, C.c_int32]
         lib.zk_g1_power_msm.argtypes = [u8p, u8p, C.c_uint64, u8p, C.c_uint64, C.c_int32]

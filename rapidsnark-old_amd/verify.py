@@ -297,12 +297,8 @@ class VerificationKeySet:
         arr = (C.c_void_p * len(keys))(*[k._h.value for k in keys])
         L.check(fn(C.byref(self._h), arr, len(keys)))
 
-    def verify(self, proofs, key_of, publics=b""):
-        """proofs: n x 256 bytes; key_of: n indices into the set's keys (any integer sequence or array); publics: the
-        signals of proof 0, then of proof 1, ...: proof i has keys[key_of[i]].n_public of them, 32 bytes each
-        -> numpy uint8 [n] of VERIFY_OK / VERIFY_INVALID / VERIFY_MALFORMED"""
-        if not self._h:
-            raise L.ZkHipError("the key set is closed")
+    def _checked(self, proofs, key_of, publics):
+        """verify()'s argument checks -> (proofs, key_of as uint32, publics, n); ValueError before any library call"""
         p, s = L._buf(proofs), L._buf(publics)
         if p.size % 256:
             raise ValueError("proofs: a multiple of 256 bytes expected")
@@ -319,11 +315,46 @@ class VerificationKeySet:
         want = int(self.n_public[ko].sum()) * 32
         if s.size != want:
             raise ValueError("publics: %d bytes expected (%d signals of 32 bytes for these keys), got %d bytes" % (want, want // 32, s.size))
-        ko = np.ascontiguousarray(ko, dtype=np.uint32)
+        return p, np.ascontiguousarray(ko, dtype=np.uint32), s, n
+
+    def verify(self, proofs, key_of, publics=b""):
+        """proofs: n x 256 bytes; key_of: n indices into the set's keys (any integer sequence or array); publics: the
+        signals of proof 0, then of proof 1, ...: proof i has keys[key_of[i]].n_public of them, 32 bytes each
+        -> numpy uint8 [n] of VERIFY_OK / VERIFY_INVALID / VERIFY_MALFORMED"""
+        if not self._h:
+            raise L.ZkHipError("the key set is closed")
+        p, ko, s, n = self._checked(proofs, key_of, publics)
         out = np.zeros(n, dtype=np.uint8)
         L.check(L.load_library().zk_vkey_set_verify(self._h, L._ptr(p) if n else None, L._ptr(ko) if n else None, L._ptr(s) if s.size else None,
                                                     s.size, n, L._ptr(out) if n else None))
         return out
+
+    def verify_batch(self, proofs, key_of, publics=b"", scalars=None):
+        """zk_vkey_set_verify_batch: verify()'s arguments -> (verdicts, report).  Inside a chunk the proofs are ordered by
+        key and cut into groups of at most ZKHIP_VERIFY_GROUP proofs under at most ZKHIP_VERIFY_GROUP_KEYS keys; a group is
+        checked by one random linear combination across its keys and only the proofs of a failing group one by one: the same
+        verdicts as verify() except that an INVALID proof is taken for OK with probability at most 2^-128 per group.
+        report: dict of zk_vkey_set_batch_report (group, group_keys, launches, groups, groups_failed, segments,
+        proofs_rechecked, malformed).
+        scalars is for tests only: n x 16 bytes little-endian, one non-zero scalar per proof.  None, the only sound choice
+        outside a test, lets the library draw them from the system's random source."""
+        if not self._h:
+            raise L.ZkHipError("the key set is closed")
+        p, ko, s, n = self._checked(proofs, key_of, publics)
+        r = None
+        if scalars is not None:
+            r = L._buf(scalars)
+            if r.size != n * 16:
+                raise ValueError("scalars: %d proofs x 16 bytes expected, got %d bytes" % (n, r.size))
+        fn = getattr(L.load_library(), "zk_vkey_set_verify_batch", None)
+        if fn is None:
+            raise L.ZkHipError("zk_vkey_set_verify_batch is not in this build of libzkhip.so")
+        out = np.zeros(n, dtype=np.uint8)
+        rep = L.zk_vkey_set_batch_report()
+        rep.size = C.sizeof(L.zk_vkey_set_batch_report)
+        L.check(fn(self._h, L._ptr(p) if n else None, L._ptr(ko) if n else None, L._ptr(s) if s.size else None, s.size, n,
+                   L._ptr(r) if r is not None and n else None, L._ptr(out) if n else None, C.byref(rep)))
+        return out, {name: int(getattr(rep, name)) for name, _ in L.zk_vkey_set_batch_report._fields_ if name != "size"}
 
     def info(self):
         """zk_vkey_set_info: n_keys, the path of the last verify() (last_path: 0 a lane per proof, 1 a workgroup per proof),
