@@ -794,6 +794,102 @@ int zk_zkey_verify_sizes(const zk_r1cs_view *r1cs, const zk_ptau_view *ptau, con
 int zk_zkey_verify(const zk_r1cs_view *r1cs, const zk_ptau_view *ptau, const zk_zkey_verify_view *zkey, const uint8_t *s32, int32_t device,
                    zk_zkey_verify_report *report);
 
+/* ---- KZG polynomial commitments over a .ptau ---------------------------------------------- */
+/* Nothing in the reference corresponds to these entry points (it proves Groth16 only); the counterpart is the commitment
+ * layer of snarkjs's PLONK and fflonk provers, which read the same .ptau: section 2 holds [tau^i] G1, section 3 holds
+ * [tau^i] G2 and section 12 holds [L_j(tau)] G1.
+ * Encodings.  Points are in the .ptau / .zkey encoding: affine Montgomery, x | y, 64 bytes in G1, all-zero = infinity.
+ * Scalars (coefficients, evaluations, points z, values y) are 32 bytes little-endian in STANDARD form and must be below r.
+ * Bases.  ZK_KZG_MONOMIAL: coeffs[i] is the coefficient of X^i and the bases are section 2's points.  ZK_KZG_LAGRANGE:
+ * coeffs[j] is the value at w^j, w the 2^lagrange_log_n-th root of unity of zk_fr_ntt, and the bases are level
+ * lagrange_log_n of section 12, the convention of zk_g1_lagrange: a Lagrange commitment of evaluations equals the monomial
+ * commitment of their zk_fr_ntt(.., inverse).
+ *
+ * The operator: q[0 .. n - 2] = the coefficients of (p(X) - p(z)) / (X - z) and y = p(z) for p = sum coeffs[i] X^i, in one
+ * pass on the device (q_(n-2) = c_(n-1), q_(i-1) = c_i + z q_i, y = c_0 + z q_0).  n = 0 is an error, "zk_fr_poly_divide: n
+ * is 0"; n = 1 writes y only (q may be NULL).  "zk_fr_poly_divide: coefficient 5 is not below r" and "zk_fr_poly_divide: z is
+ * not below r" are found before a device is touched.  ZKHIP_KZG_SEG=<coefficients a lane folds> (decimal, 1 to 4096, read at
+ * every call, 16 otherwise; anything else is an error of the call, "ZKHIP_KZG_SEG: a number of coefficients per lane from 1
+ * to 4096 expected") changes the shape of the scan and not one byte of the result.  device -1: the current one. */
+int zk_fr_poly_divide(uint8_t *q, uint8_t y[32], const uint8_t *coeffs, uint64_t n, const uint8_t z[32], int32_t device);
+
+/* The reference string on a device.  The view points into the caller's image of the file (a mapping will do); nothing of
+ * it is used after zk_kzg_create returns. */
+typedef struct zk_kzg zk_kzg;
+typedef struct zk_kzg_view {
+    uint32_t power;                         /* of the file's header */
+    const void *tau_g1;                     /* section 2 */
+    uint64_t tau_g1_bytes;
+    const void *tau_g2;                     /* section 3 */
+    uint64_t tau_g2_bytes;
+    const void *lagrange_g1;                /* section 12; NULL: the file is not prepared */
+    uint64_t lagrange_g1_bytes;
+} zk_kzg_view;
+#define ZK_KZG_MONOMIAL 0
+#define ZK_KZG_LAGRANGE 1
+#define ZK_KZG_NO_LAGRANGE 0xffffffffu      /* lagrange_log_n of an object without a Lagrange level */
+/* Keeps the first max_coeffs points of section 2 and, unless lagrange_log_n is ZK_KZG_NO_LAGRANGE, level lagrange_log_n
+ * of section 12 (2^lagrange_log_n points), both converted once to the form the multiplication kernels read; [tau] G2
+ * (point 1 of section 3) as the line table of its Miller loop, beside the G2 generator's; and the work buffers of one
+ * multiplication of max_coeffs points (a call with another n re-makes them for that n and keeps those).
+ * 1 <= max_coeffs <= 2^(power+1) - 1 and max_coeffs < 2^31; lagrange_log_n <= power (level power + 1 of a prepared file has
+ * its top power zeroed and is not offered).  Free HBM is checked before anything is allocated.  Errors, each naming the
+ * section and the lowest index:
+ *   "zk_kzg_create: max_coeffs 300 is outside 1 .. 127 (power 6)", "zk_kzg_create: Lagrange level 7 is above the file's power 6",
+ *   "zk_kzg_create: a Lagrange level needs a prepared file (ptau section 12 is absent)",
+ *   "zk_kzg_create: ptau section 2 is short: 640 bytes, 1088 needed" (sections 3 and 12 alike),
+ *   "zk_kzg_create: ptau section 2: point 0 is not the generator of G1", "... section 3: point 0 is not the generator of G2",
+ *   "zk_kzg_create: ptau section 2: point 5 has a coordinate that is not below q", "... is not on the curve", "... is the point
+ *   at infinity" (sections 2 and 3; infinity is legal in section 12), "zk_kzg_create: ptau section 3: point 1 is not in the
+ *   subgroup" (the endomorphism test of zk_g2_in_subgroup; ZKHIP_SUBGROUP_PLAIN honoured).
+ * NOT checked: that the points are the powers of ONE tau, and that the Lagrange level belongs to them.  zk_ptau_check
+ * (`ptaucheck`) answers for that; an object made from a file that fails it commits to nothing.  device -1: the current one.
+ * Calls on one object are serialised. */
+int zk_kzg_create(zk_kzg **out, const zk_kzg_view *view, uint64_t max_coeffs, uint32_t lagrange_log_n, int32_t device);
+void zk_kzg_destroy(zk_kzg *kzg);
+/* Set plan->size = sizeof(zk_kzg_plan) before the call (only `size` bytes are written). */
+typedef struct zk_kzg_plan {
+    uint32_t size;
+    uint32_t lagrange_log_n;      /* ZK_KZG_NO_LAGRANGE: none */
+    uint64_t max_coeffs;
+    uint64_t device_bytes;        /* HBM the object holds now */
+    uint32_t seg;                 /* ZKHIP_KZG_SEG in effect */
+    uint32_t last_launches;       /* kernel launches of the last commit, open, verify or verify_batch on the object */
+} zk_kzg_plan;
+int zk_kzg_info(zk_kzg *kzg, zk_kzg_plan *plan);
+/* out[k] = sum_i coeffs[k][i] B_i for m vectors of n scalars (m x n x 32 bytes), one after another: the sort, bucket and
+ * reduction kernels of zk_msm_g1 over the resident bases; only the scalars cross PCIe.  out: m x 64 bytes; an all-zero
+ * vector gives the all-zero encoding.  Monomial: 1 <= n <= max_coeffs ("zk_kzg_commit: n = 200 exceeds max_coeffs = 127");
+ * Lagrange: n = 2^lagrange_log_n exactly ("zk_kzg_commit: n = 32, the Lagrange level holds 64 points", "zk_kzg_commit: the
+ * object holds no Lagrange level").  "zk_kzg_commit: polynomial 2, coefficient 5 is not below r" is found before a device
+ * is touched; "zk_kzg_commit: n is 0", "zk_kzg_commit: basis 7 is unknown".  m = 0 is legal. */
+int zk_kzg_commit(zk_kzg *kzg, uint8_t *out, const uint8_t *coeffs, uint64_t n, uint64_t m, uint32_t basis);
+/* Opens m polynomials of n monomial coefficients, polynomial k at its own zs[k] (m x 32 bytes; a caller that opens several
+ * polynomials at one point repeats it): ys[k] = p_k(z_k) (32 bytes) and proofs[k] = the commitment of (p_k - y_k) / (X - z_k)
+ * (64 bytes; n = 1: infinity).  The quotient is made by zk_fr_poly_divide's kernels and goes into the multiplication's sort
+ * without leaving the device.  Commit and open are linear: an opening proof that folds several polynomials is the
+ * caller's linear combination of these.  Errors as zk_kzg_commit's, and "zk_kzg_open: z 3 is not below r". */
+int zk_kzg_open(zk_kzg *kzg, uint8_t *ys, uint8_t *proofs, const uint8_t *coeffs, uint64_t n, uint64_t m, const uint8_t *zs);
+/* verdict[i] (ZK_VERIFY_*) of opening i: e(C_i - [y_i] G + [z_i] pi_i, G2) = e(pi_i, [tau] G2).  MALFORMED: C_i or pi_i with
+ * a coordinate not below q or off the curve (infinity is legal: C = pi = infinity with y = 0 is the zero polynomial's
+ * opening), z_i or y_i not below r.  INVALID: well-formed and the equation does not hold.  commitments, proofs: m x 64
+ * bytes; zs, ys: m x 32 bytes.  Openings go through the device in chunks of ZKHIP_VERIFY_CHUNK (2^16 otherwise).  The
+ * return value tells only whether the call ran. */
+int zk_kzg_verify(zk_kzg *kzg, const uint8_t *commitments, const uint8_t *zs, const uint8_t *ys, const uint8_t *proofs, uint64_t m,
+                  uint8_t *verdict);
+/* ONE verdict byte for the batch, by random linear combination: with a 128-bit r_i != 0 per opening,
+ *     e(sum r_i C_i - [sum r_i y_i] G + sum (r_i z_i) pi_i, G2) = e(sum r_i pi_i, [tau] G2)
+ * (three multi-scalar multiplications, one fixed-base multiplication, one pair of Miller loops).  *verdict: MALFORMED if
+ * any opening is (zk_kzg_verify's criteria; nothing is summed then), else OK if the equation holds, else INVALID.  It does
+ * not say which opening failed: zk_kzg_verify does.  An all-valid batch always passes; a batch with an invalid opening
+ * passes for at most one of the 2^128 - 1 values of that opening's scalar: probability <= 1 / (2^128 - 1) with scalars the
+ * prover cannot foresee.  m = 0 gives OK.
+ * scalars16 is FOR TESTS ONLY: m x 16 bytes little-endian; "zk_kzg_verify_batch: scalar 3 is zero" is an error of the
+ * call.  NULL: the library draws them with getrandom() after the call has its inputs, redrawn while zero.  Scalars an
+ * adversary knows before fixing the openings are unsound: two wrong openings whose errors cancel under them pass. */
+int zk_kzg_verify_batch(zk_kzg *kzg, const uint8_t *commitments, const uint8_t *zs, const uint8_t *ys, const uint8_t *proofs, uint64_t m,
+                        const uint8_t *scalars16, uint8_t *verdict);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,5 +19,6 @@ from .r1cs import R1cs, R1csReport, write_r1cs                      # noqa: F401
 from .ptau import PtauFile, PtauReport, groth16_setup, prepare_phase2, ptau_check, ptau_check_sizes, write_trapdoor_ptau, ptau_new, ptau_contribute, ptau_contribute_sizes      # noqa: F401
 from .zkverify import ZkeyVerifyReport, zkey_verify, zkey_verify_sizes      # noqa: F401
 from .verify import VerificationKey, VerificationKeySet, pairing, pairing_last_path, groth16_verify, load_proof, load_public      # noqa: F401
+from .kzg import Kzg, fr_poly_divide                                  # noqa: F401
 from . import synth                                     # noqa: F401
 from .dist import gather_partials, ShardedChain                        # noqa: F401

@@ -163,6 +163,16 @@ class zk_zkey_verify_report(C.Structure):
                 ("coef_first_row", C.c_uint32), ("delta_is_generator", C.c_uint32)]
 
 
+class zk_kzg_view(C.Structure):
+    _fields_ = [("power", C.c_uint32), ("tau_g1", C.c_void_p), ("tau_g1_bytes", C.c_uint64), ("tau_g2", C.c_void_p), ("tau_g2_bytes", C.c_uint64),
+                ("lagrange_g1", C.c_void_p), ("lagrange_g1_bytes", C.c_uint64)]
+
+
+class zk_kzg_plan(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("lagrange_log_n", C.c_uint32), ("max_coeffs", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("seg", C.c_uint32), ("last_launches", C.c_uint32)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -217,7 +227,9 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_vkey_verify_batch", "zk_vkey_set_create", "zk_vkey_set_destroy", "zk_vkey_set_verify", "zk_vkey_set_info", "zk_vkey_set_verify_batch",
            "zk_g2_in_subgroup", "zk_g1_power_msm", "zk_g2_power_msm", "zk_fr_power_dft", "zk_ptau_check_sizes", "zk_ptau_check",
            "zk_zkey_verify_sizes", "zk_zkey_verify",
-           "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute"]
+           "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute",
+           "zk_fr_poly_divide", "zk_kzg_create", "zk_kzg_destroy", "zk_kzg_info", "zk_kzg_commit", "zk_kzg_open", "zk_kzg_verify", "zk_kzg_verify_batch"]
+ZK_KZG_MONOMIAL, ZK_KZG_LAGRANGE, ZK_KZG_NO_LAGRANGE = 0, 1, 0xffffffff
 ZK_SCALE_PLAN_MAX = 130
 ZK_VERIFY_OK, ZK_VERIFY_INVALID, ZK_VERIFY_MALFORMED = 0, 1, 2
 ZK_VERIFY_PATH_LANES, ZK_VERIFY_PATH_COOP, ZK_VERIFY_PATH_BATCH = 0, 1, 2
@@ -358,6 +370,16 @@ def load_library():
         lib.zk_glv_split.argtypes = [u8p, u8p, u8p]
         lib.zk_ptau_contribute_sizes.argtypes = [C.POINTER(zk_ptau_file_view), C.POINTER(zk_ptau_contrib_sizes)]
         lib.zk_ptau_contribute.argtypes = [C.POINTER(zk_ptau_file_view), u8p, u8p, u8p, C.c_int32, C.POINTER(zk_ptau_contrib_out)]
+    if hasattr(lib, "zk_kzg_create"):
+        lib.zk_fr_poly_divide.argtypes = [u8p, u8p, u8p, C.c_uint64, u8p, C.c_int32]
+        lib.zk_kzg_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(zk_kzg_view), C.c_uint64, C.c_uint32, C.c_int32]
+        lib.zk_kzg_destroy.argtypes = [C.c_void_p]
+        lib.zk_kzg_destroy.restype = None
+        lib.zk_kzg_info.argtypes = [C.c_void_p, C.POINTER(zk_kzg_plan)]
+        lib.zk_kzg_commit.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, C.c_uint64, C.c_uint32]
+        lib.zk_kzg_open.argtypes = [C.c_void_p, u8p, u8p, u8p, C.c_uint64, C.c_uint64, u8p]
+        lib.zk_kzg_verify.argtypes = [C.c_void_p, u8p, u8p, u8p, u8p, C.c_uint64, u8p]
+        lib.zk_kzg_verify_batch.argtypes = [C.c_void_p, u8p, u8p, u8p, u8p, C.c_uint64, u8p, u8p]
     _LIB = lib
     return lib
 

@@ -144,6 +144,18 @@ class PtauFile:
                 v.sec_bytes[sid] = s.size
         return v
 
+    def kzg_view(self):
+        """-> zk_kzg_view (sections 2, 3 and, when the file is prepared, 12 as pointers into this object's memory).  A missing
+        section stays NULL: the library names it."""
+        v = L.zk_kzg_view()
+        v.power = self.power
+        for sid, name in ((2, "tau_g1"), (3, "tau_g2"), (12, "lagrange_g1")):
+            if sid in self.sections:
+                s = self.section(sid)
+                setattr(v, name, s.ctypes.data if s.size else None)
+                setattr(v, name + "_bytes", s.size)
+        return v
+
     def close(self):
         self.raw = None
         if self._map is not None:
