@@ -890,6 +890,49 @@ int zk_kzg_verify(zk_kzg *kzg, const uint8_t *commitments, const uint8_t *zs, co
 int zk_kzg_verify_batch(zk_kzg *kzg, const uint8_t *commitments, const uint8_t *zs, const uint8_t *ys, const uint8_t *proofs, uint64_t m,
                         const uint8_t *scalars16, uint8_t *verdict);
 
+/* ---- Grand products and batch inversion over Fr -------------------------------------------- */
+/* Running products of scalars on the device: round 2 of a PLONK prover (the accumulator Z of the permutation argument) and
+ * the batched inversion its later rounds and every lookup argument need.  Nothing in the reference corresponds to them.
+ * Encodings are the KZG section's: scalars are 32 bytes little-endian in STANDARD form and must be below r, which is
+ * checked before a device is touched; an error names the array and the lowest index.  Pointers are the host's; the vectors
+ * are staged through the device.  device -1: the current one.  n < 2^31.
+ * The formula.  With T = prod den[j], 1 / (den[0] .. den[i-1]) = (den[i] .. den[n-1]) / T, so every entry is a prefix scan,
+ * a suffix scan and ONE inversion for the whole vector, and no element is inverted on its own:
+ *     z[i] = (num[0] .. num[i-1]) (den[i] .. den[n-1]) / T,      1 / a[i] = (a[0] .. a[i-1]) (a[i+1] .. a[n-1]) / T.
+ * ZKHIP_SCAN_SEG=<elements a lane folds> (decimal, 1 to 4096, read at every call, 8 otherwise; anything else is an error of
+ * the call, "ZKHIP_SCAN_SEG: a number of elements per lane from 1 to 4096 expected") changes the shape of the scan and not
+ * one byte of any result. */
+
+/* out[i] = in[i]^-1; a zero gives zero; *zeros (may be NULL) = how many.  out == in is legal.  n = 0 is legal.
+ * "zk_fr_batch_inverse: value 5 is not below r", "zk_fr_batch_inverse: n is not below 2^31". */
+int zk_fr_batch_inverse(uint8_t *out, const uint8_t *in, uint64_t n, uint64_t *zeros, int32_t device);
+
+#define ZK_SCAN_EXCLUSIVE 1u
+/* inclusive: out[i] = in[0] ... in[i];  exclusive: out[0] = 1, out[i] = in[0] ... in[i-1].  Zeros are ordinary values:
+ * everything from the first zero on (after it, when exclusive) is zero.  out == in is legal.  n = 0 is legal.
+ * "zk_fr_prefix_product: value 5 is not below r", "zk_fr_prefix_product: flags 2 is unknown". */
+int zk_fr_prefix_product(uint8_t *out, const uint8_t *in, uint64_t n, uint32_t flags, int32_t device);
+
+/* z[0] = 1, z[i] = prod_(j<i) num[j]/den[j] (n values); last = prod_(j<n) num[j]/den[j].  A zero denominator is an
+ * error of the call naming the lowest index ("zk_fr_grand_product: denominator 5 is zero"); a zero numerator is legal.
+ * "zk_fr_grand_product: numerator 5 is not below r", "zk_fr_grand_product: denominator 5 is not below r".  n = 0 writes
+ * last = 1 only.  The zero is found from T = 0 by a pass of its own: a call without one pays nothing for the check. */
+int zk_fr_grand_product(uint8_t *z, uint8_t last[32], const uint8_t *num, const uint8_t *den, uint64_t n, int32_t device);
+
+/* The permutation argument's accumulator over cols wire columns of n = 2^log_n rows:
+ *   num_i = prod_j (wires[j][i] + beta * shifts[j] * w^i + gamma),  den_i = prod_j (wires[j][i] + beta * sigmas[j][i] + gamma),
+ * w the 2^log_n-th root of zk_fr_ntt; z and last as in zk_fr_grand_product.  wires, sigmas: cols x n x 32 bytes, column
+ * after column; sigmas[j][i] is the VALUE sigma_j(w^i) = shifts[j'] * w^i' of the cell that (j, i) maps to; shifts: cols x 32.
+ * 1 <= cols <= 8, log_n <= 28.  last == 1 iff the copy constraints hold, up to the soundness of (beta, gamma); the call does
+ * not judge it.  This is snarkjs's round-2 convention: cols = 3, shifts (1, k1, k2), Z[0] = 1.  The factors are built inside
+ * the scan: no num or den vector exists on the device.  Errors: "zk_plonk_permutation_product: cols 9 is outside 1 .. 8",
+ * "zk_plonk_permutation_product: log_n 29 is above 28", "zk_plonk_permutation_product: wires: column 1, row 5 is not below r"
+ * (sigmas alike), "zk_plonk_permutation_product: shift 2 is not below r", "zk_plonk_permutation_product: beta is not below r"
+ * (gamma alike), "zk_plonk_permutation_product: row 5 has a zero denominator" (the lowest such row).
+ * NOT checked: that shifts name distinct cosets, that sigmas is a permutation. */
+int zk_plonk_permutation_product(uint8_t *z, uint8_t last[32], const uint8_t *wires, const uint8_t *sigmas, uint32_t cols,
+                                 uint32_t log_n, const uint8_t *shifts, const uint8_t beta[32], const uint8_t gamma[32], int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,5 +20,6 @@ from .ptau import PtauFile, PtauReport, groth16_setup, prepare_phase2, ptau_chec
 from .zkverify import ZkeyVerifyReport, zkey_verify, zkey_verify_sizes      # noqa: F401
 from .verify import VerificationKey, VerificationKeySet, pairing, pairing_last_path, groth16_verify, load_proof, load_public      # noqa: F401
 from .kzg import Kzg, fr_poly_divide                                  # noqa: F401
+from .frscan import fr_batch_inverse, fr_prefix_product, fr_grand_product, plonk_permutation_product      # noqa: F401
 from . import synth                                     # noqa: F401
 from .dist import gather_partials, ShardedChain                        # noqa: F401

@@ -228,7 +228,9 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_g2_in_subgroup", "zk_g1_power_msm", "zk_g2_power_msm", "zk_fr_power_dft", "zk_ptau_check_sizes", "zk_ptau_check",
            "zk_zkey_verify_sizes", "zk_zkey_verify",
            "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute",
-           "zk_fr_poly_divide", "zk_kzg_create", "zk_kzg_destroy", "zk_kzg_info", "zk_kzg_commit", "zk_kzg_open", "zk_kzg_verify", "zk_kzg_verify_batch"]
+           "zk_fr_poly_divide", "zk_kzg_create", "zk_kzg_destroy", "zk_kzg_info", "zk_kzg_commit", "zk_kzg_open", "zk_kzg_verify", "zk_kzg_verify_batch",
+           "zk_fr_batch_inverse", "zk_fr_prefix_product", "zk_fr_grand_product", "zk_plonk_permutation_product"]
+ZK_SCAN_EXCLUSIVE = 1
 ZK_KZG_MONOMIAL, ZK_KZG_LAGRANGE, ZK_KZG_NO_LAGRANGE = 0, 1, 0xffffffff
 ZK_SCALE_PLAN_MAX = 130
 ZK_VERIFY_OK, ZK_VERIFY_INVALID, ZK_VERIFY_MALFORMED = 0, 1, 2
@@ -380,6 +382,11 @@ def load_library():
         lib.zk_kzg_open.argtypes = [C.c_void_p, u8p, u8p, u8p, C.c_uint64, C.c_uint64, u8p]
         lib.zk_kzg_verify.argtypes = [C.c_void_p, u8p, u8p, u8p, u8p, C.c_uint64, u8p]
         lib.zk_kzg_verify_batch.argtypes = [C.c_void_p, u8p, u8p, u8p, u8p, C.c_uint64, u8p, u8p]
+    if hasattr(lib, "zk_fr_batch_inverse"):
+        lib.zk_fr_batch_inverse.argtypes = [u8p, u8p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int32]
+        lib.zk_fr_prefix_product.argtypes = [u8p, u8p, C.c_uint64, C.c_uint32, C.c_int32]
+        lib.zk_fr_grand_product.argtypes = [u8p, u8p, u8p, u8p, C.c_uint64, C.c_int32]
+        lib.zk_plonk_permutation_product.argtypes = [u8p, u8p, u8p, u8p, C.c_uint32, C.c_uint32, u8p, u8p, u8p, C.c_int32]
     _LIB = lib
     return lib
 
