@@ -6,6 +6,9 @@ The operators take x * 2^256 bytes and convert with ONE Montgomery product by 2^
 kernels hold is bytes * 2^5 mod p.  A word that must become T inside the kernel is therefore T * 32^-1 mod p.  That product
 leaves (bytes * K_IN + M p) / 2^261 with 0 <= bytes, K_IN < p and M within 2^235 of [0, 2^261): a representative of T in
 (-p / 2^20, p + p / 160).  For p - p / 160 > T > p / 160 the representative is T itself, limb for limb (internal_limbs()).
+
+G1 points (extreme_g1) are in the group whatever their coordinates; G2 points with a chosen coordinate (extreme_g2, half_zero_g2)
+are on the twist but outside its order-r subgroup: see the section comment there for what may receive them.
 """
 import numpy as np
 
@@ -207,6 +210,231 @@ def mixed_scalars(n, seed=40):
 
 def scalars_bytes(ks):
     return np.frombuffer(b"".join(int(k).to_bytes(32, "little") for k in ks), dtype=np.uint8)
+
+
+# ----------------------------------------------------------------------------------------------------------------- G2 points
+# The twist y^2 = x^3 + b' over Fq2 has about q^2 points and r divides that count once: the cofactor is about q, and a point
+# built from a chosen coordinate lies OUTSIDE the order-r subgroup (tests/test_extreme_operands_host.py checks [r]P != inf).
+# The group law still holds for such points, but k P depends on k itself and not on k mod r: only operators that take the
+# scalar as a plain integer may receive them, and only with scalars below r (g2_scalars_below_r).
+def f2_pow(a, e):
+    out = bn.F2_ONE
+    for bit in bin(e)[2:]:
+        out = bn.f2_mul(out, out)
+        if bit == "1":
+            out = bn.f2_mul(out, a)
+    return out
+
+
+def _fq_sqrt(a):
+    s = pow(a, (Q + 1) // 4, Q)                          # q = 3 mod 4
+    return s if s * s % Q == a % Q else None
+
+
+def f2_sqrt(a):
+    """A square root of a in Fq2 = Fq[u] / (u^2 + 1), or None for a non-square (the complex method: with n = sqrt(a0^2 + a1^2)
+    a root is x0 + x1 u, x0^2 = (a0 + n) / 2 or (a0 - n) / 2, x1 = a1 / (2 x0))."""
+    a0, a1 = a[0] % Q, a[1] % Q
+    if a1 == 0:
+        s = _fq_sqrt(a0)
+        if s is not None:
+            return (s, 0)
+        return (0, _fq_sqrt(Q - a0))                     # -1 is a non-square: exactly one of a0, -a0 has a root
+    n = _fq_sqrt((a0 * a0 + a1 * a1) % Q)
+    if n is None:                                        # the norm of a square is a square
+        return None
+    half = (Q + 1) // 2
+    x0 = _fq_sqrt((a0 + n) * half % Q)
+    if x0 is None:
+        x0 = _fq_sqrt((a0 - n) * half % Q)
+    if x0 is None or x0 == 0:
+        return None
+    x = (x0, a1 * pow(2 * x0, -1, Q) % Q)
+    return x if bn.f2_mul(x, x) == (a0, a1) else None
+
+
+_F2_ORDER = Q * Q - 1
+_CBRT = {}
+
+
+def _cbrt_constants():
+    """q^2 - 1 = 3^s m with 3 not dividing m, a generator z of the 3-Sylow subgroup of Fq2*, and the Bezout pair of 3^s and m."""
+    if not _CBRT:
+        s, m = 0, _F2_ORDER
+        while m % 3 == 0:
+            s, m = s + 1, m // 3
+        assert s == 2                                    # v3(q^2 - 1) = 2
+        g = next((i, 1) for i in range(1, 100) if f2_pow((i, 1), _F2_ORDER // 3) != bn.F2_ONE)      # a non-cube
+        z = f2_pow(g, m)                                 # order exactly 3^s
+        assert f2_pow(z, 3 ** (s - 1)) != bn.F2_ONE and f2_pow(z, 3 ** s) == bn.F2_ONE
+        a = pow(3 ** s, -1, m)                           # a 3^s + b m = 1
+        b = (1 - a * 3 ** s) // m
+        _CBRT.update(s=s, m=m, z=z, a=a, b=b % 3 ** s, third=pow(3, -1, m))
+    return _CBRT
+
+
+def f2_cbrt(c):
+    """A cube root of c in Fq2, or None for a non-cube: Tonelli-Shanks for exponent 3.  c = (c^(3^s))^a (c^m)^b splits c into a
+    part of order prime to 3, whose cube root is a power of it, and a part in the 3-Sylow subgroup <z>, whose logarithm to the
+    base z is found one base-3 digit at a time; c is a cube iff that logarithm is a multiple of 3."""
+    c = (c[0] % Q, c[1] % Q)
+    if c == bn.F2_ZERO:
+        return c
+    if f2_pow(c, _F2_ORDER // 3) != bn.F2_ONE:
+        return None
+    k = _cbrt_constants()
+    s, m, z = k["s"], k["m"], k["z"]
+    t = f2_pow(c, m)                                     # in <z>: t = z^e
+    e, zinv = 0, f2_pow(z, 3 ** s - 1)
+    w = f2_pow(z, 3 ** (s - 1))                          # order 3: the digit is read off against its powers
+    for d in range(s):                                   # digit d of e
+        probe = f2_pow(bn.f2_mul(t, f2_pow(zinv, e)), 3 ** (s - 1 - d))
+        digit = next(j for j in range(3) if f2_pow(w, j) == probe)
+        e += digit * 3 ** d
+    assert f2_pow(z, e) == t and e % 3 == 0
+    x = bn.f2_mul(f2_pow(f2_pow(c, 3 ** s), k["a"] * k["third"] % m), f2_pow(z, e // 3 * k["b"] % 3 ** s))
+    assert f2_pow(x, 3) == c
+    return x
+
+
+def _twist_rhs(x):
+    return bn.f2_add(bn.f2_mul(bn.f2_mul(x, x), x), bn.G2_B)
+
+
+def _twist_points_at(x):
+    """Both points of the twist over x, or () where x^3 + b' is no square (or zero)."""
+    y = f2_sqrt(_twist_rhs(x))
+    if y is None or y == bn.F2_ZERO:
+        return ()
+    pts = ((x, y), (x, bn.f2_neg(y)))
+    assert all(bn.G2.is_on_curve(P) for P in pts)
+    return pts
+
+
+def g2_internal_x(P):
+    """(Ta, Tb): what the kernels hold for the two components of P's x after converting its bytes."""
+    b = bn.g2_to_bytes(P)
+    return tuple(internal_value(int.from_bytes(b[32 * i:32 * i + 32], "little"), Q) for i in range(2))
+
+
+# every pairing of the three G1 target kinds for (re x, im x); the two that come last get the smaller share of an uneven count
+G2_KINDS = (("full_limbs", "full_limbs"), ("full_limbs", "below_q"), ("full_limbs", "above_zero"), ("below_q", "full_limbs"),
+            ("above_zero", "full_limbs"), ("below_q", "above_zero"), ("above_zero", "below_q"), ("below_q", "below_q"),
+            ("above_zero", "above_zero"))
+
+
+def extreme_g2(count=32):
+    """[(kind, (Ta, Tb), P)] with x = (Ta, Tb) * 2^-261: for each of the nine kinds (kind_a + "/" + kind_b) the first target pairs
+    — the i-th target of kind_a beside the (i + 1)-th of kind_b, so the components differ within a kind — for which x^3 + b' is
+    a square, each with both roots.  count / 2 target pairs are dealt round the kinds: 32 gives two pairs to the first seven
+    kinds and one to the last two.  The points are on the twist and NOT in the order-r subgroup (see the section comment)."""
+    assert count % 2 == 0 and count // 2 >= len(G2_KINDS)
+    share = [(count // 2 - i + len(G2_KINDS) - 1) // len(G2_KINDS) for i in range(len(G2_KINDS))]
+    inv261 = pow(1 << 261, -1, Q)
+    out = []
+    for (ka, kb), want in zip(G2_KINDS, share):
+        gens = dict(_g1_targets())
+        ga, gb = gens[ka], dict(_g1_targets())[kb]
+        next(gb)
+        found = tried = 0
+        while found < want:
+            ta, tb = next(ga), next(gb)
+            tried += 1
+            assert 0 < ta < Q and 0 < tb < Q and tried <= 10
+            x = (ta * inv261 % Q, tb * inv261 % Q)
+            for P in _twist_points_at(x):
+                assert g2_internal_x(P) == (ta, tb)
+                out.append((ka + "/" + kb, (ta, tb), P))
+            found += bool(_twist_points_at(x))
+    assert len(out) == count
+    return out
+
+
+def extreme_g2_points(count=32):
+    """The points of extreme_g2 in the affine Montgomery bytes the ABI takes, 128 each."""
+    return [bn.g2_to_bytes(P) for _, _, P in extreme_g2(count)]
+
+
+def _fq_beta():
+    """A primitive cube root of unity in Fq."""
+    for g in range(2, 50):
+        beta = pow(g, (Q - 1) // 3, Q)
+        if beta != 1:
+            assert beta * beta % Q * beta % Q == 1
+            return beta
+
+
+def half_zero_g2():
+    """(pairs, points), all found by scanning small integers.
+    pairs: [(shape, P1, P2)], two points of the twist whose difference of x (what a mixed addition onto a fresh affine
+    accumulator forms as P = U2 - x) or of y (R = S2 - y) is zero in exactly the stated way:
+      "a"  equal re(x), different im(x);  "b"  equal im(x), different re(x)  — P has exactly one zero component;
+      "c"  (x, y) and (beta x, y), beta a primitive cube root of unity in Fq (x^3 and with it b' unchanged): R = 0 with P != 0,
+           both components of P non-zero; "c-" the same with -y on the second point: R = -2y.
+    points: [(shape, P)], points with a zero component of their own:
+      "d_re" y = (t, 0), "d_im" y = (0, t) (x a cube root of y^2 - b'): with -P they give P = 0 and R = -2y half zero;
+      "e_re" x = (t, 0), "e_im" x = (0, t)."""
+    pairs, points = [], []
+    # (a), (b): the first two fixed components with two partners each
+    for shape, make in (("a", lambda fix, var: (fix, var)), ("b", lambda fix, var: (var, fix))):
+        got = 0
+        for fix in range(1, 50):
+            on = [_twist_points_at(make(fix, var)) for var in range(1, 12)]
+            on = [p[0] for p in on if p]
+            if len(on) >= 2:
+                pairs += [(shape, on[0], on[1]), (shape, on[0], bn.G2.neg(on[1]))]
+                got += 1
+            if got == 2:
+                break
+        assert got == 2
+    beta = _fq_beta()
+    got = 0
+    for s in range(1, 50):
+        for P in _twist_points_at((s, s + 1))[:1]:
+            Pb = (bn.f2_scalar(P[0], beta), P[1])
+            assert bn.G2.is_on_curve(Pb) and Pb[0] != P[0]
+            pairs += [("c", P, Pb), ("c-", P, bn.G2.neg(Pb))]
+            got += 1
+        if got == 2:
+            break
+    assert got == 2
+    # (d): y with one zero component; (e): x with one zero component
+    for shape, make in (("d_re", lambda t: (t, 0)), ("d_im", lambda t: (0, t))):
+        got = 0
+        for t in range(1, 50):
+            y = make(t)
+            x = f2_cbrt(bn.f2_sub(bn.f2_mul(y, y), bn.G2_B))
+            if x is not None:
+                assert bn.G2.is_on_curve((x, y))
+                points.append((shape, (x, y)))
+                got += 1
+            if got == 2:
+                break
+        assert got == 2
+    for shape, make in (("e_re", lambda t: (t, 0)), ("e_im", lambda t: (0, t))):
+        got = 0
+        for t in range(1, 50):
+            for P in _twist_points_at(make(t))[:1]:
+                points.append((shape, P))
+                got += 1
+            if got == 2:
+                break
+        assert got == 2
+    return pairs, points
+
+
+def g2_scalars_below_r(n, seed=41):
+    """0, 1, 2, r - 1, r - 2 and random values, ALL below r, up to n.  The extreme G2 points lie outside the order-r subgroup:
+    for them k P and (k mod r) P differ, and zk_msm_g2 reduces a scalar at or above r by subtracting r while the references
+    take its raw digits — the two agree on such points only for k < r."""
+    import random
+    rng = random.Random(seed)
+    ks = [0, 1, 2, R - 1, R - 2]
+    while len(ks) < n:
+        ks.append(rng.randrange(R))
+    ks = ks[:n]
+    assert all(0 <= k < R for k in ks)                   # never at or above r: see the docstring
+    return ks
 
 
 # ----------------------------------------------------------------------------------------------- Montgomery-product operands

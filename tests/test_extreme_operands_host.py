@@ -1,6 +1,7 @@
 """The extreme-operand families of tests/extreme_inputs.py are what they claim to be, and the two references the GPU tests
 trust (oracle/bn254.py in Python integers, oracle/c_oracle.py in C) agree on all of them.  No GPU: a disagreement here is a
-finding about an oracle, to be settled before tests/test_gpu_extreme_operands.py means anything."""
+finding about an oracle, to be settled before tests/test_gpu_extreme_operands.py and tests/test_gpu_extreme_operands_g2.py mean
+anything."""
 import numpy as np
 import pytest
 
@@ -117,6 +118,138 @@ def test_c_restatement_and_python_oracle_agree_on_the_extreme_msm():
     for _, _, P in ext:
         for k in (1, 2, R - 1):
             assert co.g1_mul(bn.g1_to_bytes(P), k) == bn.g1_to_bytes(bn.G1.mul(P, k))
+
+
+def test_f2_sqrt_and_f2_cbrt():
+    import random
+    rng = random.Random(2)
+    roots = cubes = 0
+    for i in range(40):
+        a = (rng.randrange(Q), rng.randrange(Q) if i % 4 else 0)
+        for x in ((a[0], a[1]), bn.f2_mul(a, a), xi.f2_pow(a, 3)):
+            s, c = xi.f2_sqrt(x), xi.f2_cbrt(x)
+            assert s is None or bn.f2_mul(s, s) == x
+            assert c is None or xi.f2_pow(c, 3) == x
+            roots += s is not None
+            cubes += c is not None
+        assert xi.f2_sqrt(bn.f2_mul(a, a)) in (a, bn.f2_neg(a))
+        assert xi.f2_cbrt(xi.f2_pow(a, 3)) is not None
+    assert 40 < roots < 120 and 40 < cubes < 120          # squares and cubes are found, non-squares and non-cubes refused
+    assert xi.f2_sqrt((Q - 4, 0)) in ((0, 2), (0, Q - 2))   # -4 = (2u)^2
+    # an element is a square iff its (q^2 - 1) / 2-th power is 1: None exactly for the others
+    for i in range(1, 12):
+        assert (xi.f2_sqrt((i, 1)) is None) == (xi.f2_pow((i, 1), (Q * Q - 1) // 2) != bn.F2_ONE)
+
+
+def test_extreme_g2_points_are_on_the_twist_with_the_intended_x():
+    pts = xi.extreme_g2(32)
+    assert len(pts) == 32 and len({P for _, _, P in pts}) == 32
+    kinds = [k for k, _, _ in pts]
+    assert set(kinds) == {a + "/" + b for a in ("full_limbs", "below_q", "above_zero") for b in ("full_limbs", "below_q", "above_zero")}
+    assert all(kinds.count(k) in (2, 4) for k in kinds)
+    for i, (kind, t, P) in enumerate(pts):
+        assert bn.G2.is_on_curve(P) and P[1] != bn.F2_ZERO
+        b = bn.g2_to_bytes(P)
+        words = [int.from_bytes(b[32 * j:32 * j + 32], "little") for j in range(2)]
+        assert tuple(w * 32 % Q for w in words) == t == xi.g2_internal_x(P)
+        for comp_kind, tc, w in zip(kind.split("/"), t, words):
+            if comp_kind == "full_limbs":
+                assert xi.limbs29(tc)[:8] == [(1 << 29) - 1] * 8 and 3171406 - 64 < xi.limbs29(tc)[8] < 3171406
+                assert xi.internal_limbs(w, Q) == xi.limbs29(tc)
+            elif comp_kind == "below_q":
+                assert 0 < Q - tc < 64
+            else:
+                assert 0 < tc < 64
+        if i % 2:
+            assert P == bn.G2.neg(pts[i - 1][2])
+    assert xi.extreme_g2_points(32) == [bn.g2_to_bytes(P) for _, _, P in pts]
+
+
+def test_extreme_g2_points_are_outside_the_order_r_subgroup():
+    """Why the G2 families go only to operators that take the scalar as a plain integer, with scalars below r."""
+    ext = xi.extreme_g2(32)
+    pairs, points = xi.half_zero_g2()
+    for P in (ext[0][2], ext[18][2], pairs[0][1], points[0][1]):
+        assert bn.G2.mul(P, R) is not None
+    assert bn.G2.mul(bn.G2.gen, R) is None
+    ks = xi.g2_scalars_below_r(300)
+    assert ks[:5] == [0, 1, 2, R - 1, R - 2] and len(ks) == 300 and max(ks) < R and len(set(ks)) == 300
+    assert xi.g2_scalars_below_r(3) == [0, 1, 2]
+
+
+def test_half_zero_g2_shapes_are_what_they_claim():
+    pairs, points = xi.half_zero_g2()
+    assert sorted({s for s, _, _ in pairs}) == ["a", "b", "c", "c-"] and len(pairs) == 12
+    assert sorted({s for s, _ in points}) == ["d_im", "d_re", "e_im", "e_re"] and len(points) == 8
+    beta = xi._fq_beta()
+    assert beta != 1 and pow(beta, 3, Q) == 1
+    for shape, P1, P2 in pairs:
+        assert bn.G2.is_on_curve(P1) and bn.G2.is_on_curve(P2) and P1 != P2
+        dx, dy = bn.f2_sub(P2[0], P1[0]), bn.f2_sub(P2[1], P1[1])
+        # the kernels hold x * 2^261: a component is zero there exactly when it is zero here
+        ix = bn.f2_sub(xi.g2_internal_x(P2), xi.g2_internal_x(P1))
+        assert [v == 0 for v in ix] == [v == 0 for v in dx]
+        if shape == "a":
+            assert dx[0] == 0 and dx[1] != 0
+        elif shape == "b":
+            assert dx[0] != 0 and dx[1] == 0
+        else:
+            assert P2[0] == bn.f2_scalar(P1[0], beta) and dx[0] != 0 and dx[1] != 0
+            assert dy == bn.F2_ZERO if shape == "c" else dy == bn.f2_neg(bn.f2_scalar(P1[1], 2))
+        if shape in ("a", "b"):
+            assert dy[0] != 0 and dy[1] != 0
+    for shape, P in points:
+        assert bn.G2.is_on_curve(P)
+        (xa, xb), (ya, yb) = P
+        zero = {"d_re": yb, "d_im": ya, "e_re": xb, "e_im": xa}[shape]
+        rest = [v for v in (xa, xb, ya, yb)]
+        assert zero == 0 and rest.count(0) == 1
+        if shape.startswith("d"):                            # P and -P: P = 0 and R = -2y with exactly one zero component
+            r = bn.f2_sub(bn.G2.neg(P)[1], P[1])
+            assert (r[0] == 0) != (r[1] == 0)
+
+
+def _g2_host_set():
+    """16 points: two of each mixed kind, the half-zero pairs of every shape and a point of each zero-component shape."""
+    ext = xi.extreme_g2(32)
+    pairs, points = xi.half_zero_g2()
+    pts = [ext[i][2] for i in (0, 5, 8, 13, 16, 22, 28, 31)]
+    pts += [pairs[0][1], pairs[0][2], pairs[4][2], pairs[8][2], pairs[9][2]] + [points[i][1] for i in (0, 2, 5)]
+    assert len(pts) == 16
+    return pts
+
+
+def test_c_restatement_and_python_oracle_agree_on_the_extreme_g2_msm():
+    """The C restatement is the reference of tests/test_gpu_extreme_operands_g2.py; the Python integers settle it here (16
+    points: a G2 multiplication in Python takes about half a second)."""
+    pts = _g2_host_set()
+    ks = xi.g2_scalars_below_r(16)
+    want = None
+    for P, k in zip(pts, ks):
+        want = bn.G2.add(want, bn.G2.mul(P, k))
+    bases = b"".join(bn.g2_to_bytes(P) for P in pts)
+    assert co.msm_g2(bases, xi.scalars_bytes(ks)) == bn.g2_to_bytes(want)
+    # all scalars one: the plain sum
+    want = None
+    for P in pts:
+        want = bn.G2.add(want, P)
+    assert co.msm_g2(bases, xi.scalars_bytes([1] * 16)) == bn.g2_to_bytes(want)
+    for P, k in zip(pts[:6], (1, 2, R - 1, R - 2, ks[5], ks[6])):
+        assert co.g2_mul(bn.g2_to_bytes(P), k) == bn.g2_to_bytes(bn.G2.mul(P, k))
+
+
+def test_c_restatement_adds_the_half_zero_pairs_like_the_python_oracle():
+    """Two and three points under one common scalar: what the tiny device MSMs compare with."""
+    pairs, points = xi.half_zero_g2()
+    cases = [(P1, P2) for _, P1, P2 in pairs] + [(P2, P1) for _, P1, P2 in pairs]
+    cases += [(P, bn.G2.neg(P)) for _, P in points] + [(P, P) for _, P in points]
+    one = xi.scalars_bytes([1, 1])
+    for P1, P2 in cases:
+        got = co.msm_g2(bn.g2_to_bytes(P1) + bn.g2_to_bytes(P2), one)
+        assert got == bn.g2_to_bytes(bn.G2.add(P1, P2))
+    P, P2 = points[0][1], pairs[0][1]
+    got = co.msm_g2(b"".join(bn.g2_to_bytes(X) for X in (P, bn.G2.neg(P), P2)), xi.scalars_bytes([1, 1, 1]))
+    assert got == bn.g2_to_bytes(P2)
 
 
 @pytest.mark.parametrize("field,p", [("fr", R), ("fq", Q)])

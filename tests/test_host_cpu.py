@@ -260,10 +260,16 @@ def test_column_bounds_of_the_29_bit_limb_products():
 def test_no_product_column_leaves_int64_for_the_job_shapes_in_use(tmp_path):
     """Companion of the analytic bound above: tools/field29_bounds_test.cpp builds field29.hpp / curve29.hpp for the host with every
     multiply-accumulate evaluated in 128 bits (-DZK_CHECK_COLUMNS) and runs each job shape the kernels use (a*b, a*wide, a^2,
-    a*b + c*d, the four-product job, chains of G1 / G2 mixed additions) over extreme and random operands of the callers' limb ranges."""
+    a*b + c*d, the four-product job, chains of G1 / G2 mixed additions) over extreme and random operands of the callers' limb ranges.
+    G2 runs through both bound-tracked additions of curve29.hpp: the Fq2r one and a host restatement of the lane-pair one (device-only:
+    DPP exchanges), over random chains, X components on full limbs / q - 32 / 1 / 2 / 0 meeting themselves and their negatives, and
+    the half-zero shapes of tests/extreme_inputs.py; the program exits 1 if the two ever differ in value.  Each block prints its peak."""
     import subprocess
     exe = str(tmp_path / "field29_bounds_test")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-DZK_CHECK_COLUMNS", "-I", os.path.join(ROOT, "rapidsnark-old_amd", "csrc"),
                            os.path.join(ROOT, "tools", "field29_bounds_test.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "OK: no column left int64" in out.stdout, out.stdout + out.stderr
+    for block in ("G2 random chain", "G2 extreme X, self and negative", "G2 extreme X, running sum", "G2 half-zero shapes"):
+        line = [ln for ln in out.stdout.splitlines() if ln.startswith(block)]
+        assert len(line) == 1 and "(lane pair), overflows 0" in line[0], out.stdout

@@ -7,12 +7,21 @@
 //   plus chains of G1 and G2 mixed additions (curve29.hpp) over random operands, which exercise sub_nc / neg_lazy / dbl_lazy as used;
 //   plus the butterfly schedules of nttpair.hip (lazy DIT adds, DIF settle) over the extreme-operand families of
 //   tests/extreme_inputs.py — the element whose limbs are all 2^29 - 1 in every register, r - 1, masks, strides — with the
-//   all-sums element of a constant vector checked for its VALUE (2^11 v after a tile), and G1 additions with X on full limbs.
-// Prints the peak |column| as a multiple of 2^58 and exits 1 on any overflow or wrong all-sums value.
+//   all-sums element of a constant vector checked for its VALUE (2^11 v after a tile), and G1 additions with X on full limbs;
+//   plus G2 chains through BOTH bound-tracked mixed additions of curve29.hpp: madd(XYZZ<Fq2r>&, ...) as it is, and the lane-pair
+//   madd(XYZZ<Fq2s>&, ...) — device-only, it is written with DPP builtins — in a restatement below that keeps the two lanes side
+//   by side and follows the kernel statement for statement (the carries of R and D, the operand signs of JMulAdd4, the run3
+//   with zz' and zzz' in place).  The chains: random operands; X components T_MAX, q - 1 as held internally (q - 32), 1, 2
+//   and 0 in every pairing, a point meeting itself and its negative; those points on a running sum; and the half-zero shapes
+//   of tests/extreme_inputs.py (half_zero_g2: P or R zero in exactly one component, y or x with a zero component).  After
+//   every addition the lane-pair accumulator must equal the Fq2r one, component by component in canonical form.
+// Prints the peak |column| of every block as a multiple of 2^58 and exits 1 on any overflow, wrong all-sums value, lane-pair
+// result that differs from the Fq2r one, or P, -P that does not end at infinity.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <vector>
 #include "curve29.hpp"
 
 using namespace zk;
@@ -164,6 +173,11 @@ static long family_windows(const char *name, const Fr29 &v, int pattern, int rou
     return wrong;
 }
 
+static Fq29 &tmax_fq() {                              // the T_MAX element of Fq as families() converted it
+    static Fq29 v = Fq29::zero();
+    return v;
+}
+
 static int families() {
     // the word whose internal value is T_MAX, through the conversion the operators run: limbs 0..7 must come out full
     // T_MAX * 32^-1 mod r and mod q, T_MAX = 3171406 * 2^232 - 1 (tests/extreme_inputs.py: T_MAX_WORD_FR, T_MAX_WORD_FQ)
@@ -177,6 +191,7 @@ static int families() {
     }
     const Fr29 tr = Fr29::from_mont256(wr);
     const Fq29 tq = Fq29::from_mont256(wq);
+    tmax_fq() = tq;
     for (int i = 0; i < 9; i++) {
         const int32_t want = i < 8 ? (1 << 29) - 1 : 3171405;
         if (tr.l[i] != want || tq.l[i] != want) {
@@ -211,6 +226,284 @@ static int families() {
     return 0;
 }
 
+// ---- The lane-pair G2 mixed addition of curve29.hpp (madd(XYZZ<Fq2s>&, ...)) restated for the host.  The device version holds
+// the real component of an Fq2 value in an even lane and the imaginary one in its odd neighbour and exchanges operands with
+// DPP moves; here a "register" is the pair of values the two lanes hold (Reg), the exchanges are plain copies, and every
+// statement runs for lane 0 (even) and lane 1 (odd) in turn.  Everything else is the kernel's, statement for statement: sub_nc
+// for P and sub for R, sqr_operands, prepare, and the run3 of JMulAdd2, JMulAdd2 and JMulAdd4 with zz' and zzz' in place.
+struct Reg {
+    Fq29 l[2];
+};
+struct Fq2h {
+    Reg v;
+    typedef Fq29 B;
+    static Reg other(const Reg &a) { return Reg{{a.l[1], a.l[0]}}; }          // quad_perm [1,0,3,2]
+    static Reg from_even(const Reg &a) { return Reg{{a.l[0], a.l[0]}}; }      // quad_perm [0,0,2,2]
+    static Reg from_odd(const Reg &a) { return Reg{{a.l[1], a.l[1]}}; }       // quad_perm [1,1,3,3]
+    template <class Fn>
+    static Reg lanes(Fn f) { return Reg{{f(0), f(1)}}; }                      // f(lane): what the lane computes; odd() == (lane == 1)
+    static bool both(bool even, bool odd) { return even && odd; }             // the AND over the pair
+    static Fq2h zero() { return Fq2h{Reg{{B::zero(), B::zero()}}}; }
+    static Fq2h one() { return Fq2h{Reg{{B::one(), B::zero()}}}; }            // sel(odd(), zero, one)
+    bool is_zero() const { return both(v.l[0].is_zero(), v.l[1].is_zero()); }
+    bool is_zero_raw() const { return both(v.l[0].is_zero_raw(), v.l[1].is_zero_raw()); }
+    static Fq2h add(const Fq2h &x, const Fq2h &y) { return Fq2h{lanes([&](int k) { return B::add(x.v.l[k], y.v.l[k]); })}; }
+    static Fq2h sub(const Fq2h &x, const Fq2h &y) { return Fq2h{lanes([&](int k) { return B::sub(x.v.l[k], y.v.l[k]); })}; }
+    static Fq2h dbl(const Fq2h &x) { return Fq2h{lanes([&](int k) { return B::dbl(x.v.l[k]); })}; }
+    struct Pre {
+        Reg a0, a1s;
+    };
+    static Pre prepare(const Fq2h &x) {
+        const Reg a1 = from_odd(x.v);
+        return Pre{from_even(x.v), lanes([&](int k) { return k ? a1.l[k] : B::neg_lazy(a1.l[k]); })};      // sel(odd(), a1, -a1)
+    }
+    static Fq2h mul(const Fq2h &x, const Fq2h &y) {
+        const Pre p = prepare(x);
+        const Reg yo = other(y.v);
+        return Fq2h{lanes([&](int k) { return B::mul_add2(p.a0.l[k], y.v.l[k], p.a1s.l[k], yo.l[k]); })};
+    }
+    static void sqr_operands(Reg &u, Reg &w, const Fq2h &x) {
+        const Reg a0 = from_even(x.v), xo = other(x.v);
+        const Reg t = lanes([&](int k) { return k ? B::zero() : xo.l[k]; });  // xo & keep, keep = odd() ? 0 : -1
+        u = lanes([&](int k) { return B::add_nc(a0.l[k], xo.l[k]); });
+        w = lanes([&](int k) { return B::sub(x.v.l[k], t.l[k]); });
+    }
+    static Fq2h sqr(const Fq2h &x) {
+        Reg u, w;
+        sqr_operands(u, w, x);
+        return Fq2h{lanes([&](int k) { return B::mul(u.l[k], w.l[k]); })};
+    }
+    static void mul2(Fq2h &r0, const Pre &x0, const Fq2h &y0, Fq2h &r1, const Pre &x1, const Fq2h &y1) {
+        const Reg yo0 = other(y0.v), yo1 = other(y1.v);
+        for (int k = 0; k < 2; k++)
+            B::run2(r0.v.l[k], B::JMulAdd2{x0.a0.l[k], y0.v.l[k], x0.a1s.l[k], yo0.l[k]}, r1.v.l[k], B::JMulAdd2{x1.a0.l[k], y1.v.l[k], x1.a1s.l[k], yo1.l[k]});
+    }
+    static void mul2(Fq2h &r0, const Fq2h &x0, const Fq2h &y0, Fq2h &r1, const Fq2h &x1, const Fq2h &y1) {
+        mul2(r0, prepare(x0), y0, r1, prepare(x1), y1);
+    }
+    static void sqr2(Fq2h &r0, const Fq2h &x0, Fq2h &r1, const Fq2h &x1) {
+        Reg u0, w0, u1, w1;
+        sqr_operands(u0, w0, x0);
+        sqr_operands(u1, w1, x1);
+        for (int k = 0; k < 2; k++) B::mul2(r0.v.l[k], u0.l[k], w0.l[k], r1.v.l[k], u1.l[k], w1.l[k]);
+    }
+};
+
+static void madd(XYZZ<Fq2h> &acc, const Affine<Fq2h> &p) {
+    typedef Fq29 B;
+    typedef Fq2h F;
+    if (p.is_inf()) return;
+    if (acc.is_inf()) {
+        acc = XYZZ<F>{p.x, F{F::lanes([&](int k) { return B::carry(p.y.v.l[k]); })}, F::one(), F::one()};
+        return;
+    }
+    F U2, S2;
+    F::mul2(U2, p.x, acc.zz, S2, p.y, acc.zzz);
+    F P{F::lanes([&](int k) { return B::sub_nc(U2.v.l[k], acc.x.v.l[k]); })};
+    F R{F::lanes([&](int k) { return B::sub(S2.v.l[k], acc.y.v.l[k]); })};
+    if (P.is_zero()) {
+        if (R.is_zero()) acc = dbl_affine(Affine<F>{p.x, F{F::lanes([&](int k) { return B::carry(p.y.v.l[k]); })}});
+        else acc = XYZZ<F>::inf();
+        return;
+    }
+    F PP, R2;
+    F::sqr2(PP, P, R2, R);
+    const F::Pre pp = F::prepare(PP);
+    F PPP, Q;
+    F::mul2(PPP, pp, P, Q, pp, acc.x);
+    const F::Pre ppp = F::prepare(PPP);
+    for (int k = 0; k < 2; k++) {
+        for (int i = 0; i < 9; i++) acc.x.v.l[k].l[i] = R2.v.l[k].l[i] - PPP.v.l[k].l[i] - (Q.v.l[k].l[i] << 1);
+        acc.x.v.l[k] = B::carry(acc.x.v.l[k]);                                 // X3
+    }
+    const Reg D = F::lanes([&](int k) { return B::sub(Q.v.l[k], acc.x.v.l[k]); }), Do = F::other(D);
+    const Reg ny = F::lanes([&](int k) { return B::neg_lazy(acc.y.v.l[k]); }), nyo = F::other(ny);
+    const F::Pre rp = F::prepare(R);
+    const Reg zzo = F::other(acc.zz.v), zzzo = F::other(acc.zzz.v);
+    Reg Y3;
+    for (int k = 0; k < 2; k++)
+        B::run3(acc.zz.v.l[k], B::JMulAdd2{pp.a0.l[k], acc.zz.v.l[k], pp.a1s.l[k], zzo.l[k]},                     // zz', zzz' in place
+                acc.zzz.v.l[k], B::JMulAdd2{ppp.a0.l[k], acc.zzz.v.l[k], ppp.a1s.l[k], zzzo.l[k]},
+                Y3.l[k], B::JMulAdd4{rp.a0.l[k], D.l[k], rp.a1s.l[k], Do.l[k], ppp.a0.l[k], ny.l[k], ppp.a1s.l[k], nyo.l[k]});
+    acc.y = F{Y3};
+}
+
+static Fq2h lane_form(const Fq2r &x) { return Fq2h{Reg{{x.a, x.b}}}; }
+
+// A chain: points added in turn, the accumulator reset to infinity in front of a step where `fresh` is set.
+struct Step {
+    Affine<Fq2r> p;
+    bool fresh;
+};
+typedef std::vector<Step> Chain;
+
+// the accumulator after a step: infinity or eight canonical components
+struct Snap {
+    bool inf;
+    Fq29 c[8];
+};
+static Snap snap(const XYZZ<Fq2r> &a) {
+    Snap s{a.is_inf(), {}};
+    const Fq29 *src[8] = {&a.x.a, &a.x.b, &a.y.a, &a.y.b, &a.zz.a, &a.zz.b, &a.zzz.a, &a.zzz.b};
+    for (int i = 0; i < 8; i++) s.c[i] = Fq29::canonical(*src[i]);
+    return s;
+}
+static Snap snap(const XYZZ<Fq2h> &a) {
+    Snap s{a.is_inf(), {}};
+    const Fq29 *src[8] = {&a.x.v.l[0], &a.x.v.l[1], &a.y.v.l[0], &a.y.v.l[1], &a.zz.v.l[0], &a.zz.v.l[1], &a.zzz.v.l[0], &a.zzz.v.l[1]};
+    for (int i = 0; i < 8; i++) s.c[i] = Fq29::canonical(*src[i]);
+    return s;
+}
+static bool same(const Snap &a, const Snap &b) {
+    if (a.inf != b.inf) return false;
+    if (a.inf) return true;
+    for (int i = 0; i < 8; i++)
+        for (int k = 0; k < 9; k++)
+            if (a.c[i].l[k] != b.c[i].l[k]) return false;
+    return true;
+}
+
+// Runs the chain through the Fq2r madd, then through the lane-pair restatement, and compares the accumulator after every step.
+// want_inf: indices of steps after which the accumulator must be infinity (a point met its negative).  -> 0, or 1 after FAIL
+static int run_chain(const char *name, const Chain &ch, const std::vector<size_t> &want_inf) {
+    const long before = zk_column_overflows();
+    std::vector<Snap> ref;
+    ref.reserve(ch.size());
+    zk_column_peak() = 0;
+    XYZZ<Fq2r> acc = XYZZ<Fq2r>::inf();
+    long infs = 0;
+    for (const Step &s : ch) {
+        if (s.fresh) acc = XYZZ<Fq2r>::inf();
+        madd(acc, s.p);
+        ref.push_back(snap(acc));
+        infs += acc.is_inf();
+    }
+    const double peak_r = (double)zk_column_peak() / 288230376151711744.0;
+    for (size_t i : want_inf)
+        if (!ref[i].inf) {
+            printf("FAIL: %s: step %zu of the Fq2r chain did not end at infinity\n", name, i);
+            return 1;
+        }
+    zk_column_peak() = 0;
+    XYZZ<Fq2h> acch = XYZZ<Fq2h>::inf();
+    for (size_t i = 0; i < ch.size(); i++) {
+        if (ch[i].fresh) acch = XYZZ<Fq2h>::inf();
+        madd(acch, Affine<Fq2h>{lane_form(ch[i].p.x), lane_form(ch[i].p.y)});
+        if (!same(snap(acch), ref[i])) {
+            printf("FAIL: %s: the lane-pair addition differs from the Fq2r one at step %zu\n", name, i);
+            return 1;
+        }
+    }
+    printf("G2 %-28s: %6zu additions (%ld to infinity), peak |column| = %.3f * 2^58 (Fq2r), %.3f * 2^58 (lane pair), overflows %ld\n", name,
+           ch.size(), infs, peak_r, (double)zk_column_peak() / 288230376151711744.0, zk_column_overflows() - before);
+    return 0;
+}
+
+static Fq29 small_fq(int32_t v) {
+    Fq29 r = Fq29::zero();
+    r.l[0] = v;
+    return r;
+}
+
+static Affine<Fq2r> with_neg_y(Affine<Fq2r> p) {
+    negate_y(p);
+    return p;
+}
+
+static int g2_chains(const Fq29 &tq) {
+    Fq29 qm = Fq29::zero();                          // q - 1 as the kernels hold it: (q - 1) * 2^5 = q - 32
+    for (int i = 0; i < 9; i++) qm.l[i] = Fq29Params::P[i];
+    qm.l[0] -= 32;
+    int bad = 0;
+    // random operands: the chain of main(), now through both additions
+    Chain rnd;
+    for (int i = 0; i < 10000; i++) {
+        Affine<Fq2r> p{Fq2r{random_canonical<Fq29>(), random_canonical<Fq29>()}, Fq2r{random_canonical<Fq29>(), random_canonical<Fq29>()}};
+        if (i & 1) negate_y(p);
+        rnd.push_back(Step{p, false});
+    }
+    bad |= run_chain("random chain", rnd, {});
+    // extreme X: every pairing of T_MAX, q - 32, 1, 2 and 0 for the two components, Y random or extreme as well
+    const Fq29 comp[5] = {tq, qm, small_fq(1), small_fq(2), Fq29::zero()};
+    std::vector<Affine<Fq2r>> ext;
+    for (int a = 0; a < 5; a++)
+        for (int b = 0; b < 5; b++) {
+            if (a == 4 && b == 4) continue;
+            ext.push_back(Affine<Fq2r>{Fq2r{comp[a], comp[b]}, Fq2r{random_canonical<Fq29>(), random_canonical<Fq29>()}});
+            ext.push_back(Affine<Fq2r>{Fq2r{comp[a], comp[b]}, Fq2r{comp[b == 4 ? 0 : b], comp[a == 4 ? 1 : a]}});
+        }
+    // a point meets itself (the doubling branch), then its negative twice: 2P - P is a general addition whose result is P
+    // again with zz != 1, and P - P ends at infinity from there
+    Chain self;
+    std::vector<size_t> ends;
+    for (size_t i = 0; i < ext.size(); i++)
+        for (int neg_first = 0; neg_first < 2; neg_first++) {
+            const Affine<Fq2r> p = neg_first ? with_neg_y(ext[i]) : ext[i], m = neg_first ? ext[i] : with_neg_y(ext[i]);
+            self.push_back(Step{p, true});
+            self.push_back(Step{p, false});
+            self.push_back(Step{m, false});
+            self.push_back(Step{m, false});
+            ends.push_back(self.size() - 1);
+            self.push_back(Step{p, true});           // and the plain pair P, -P on a fresh accumulator
+            self.push_back(Step{m, false});
+            ends.push_back(self.size() - 1);
+        }
+    bad |= run_chain("extreme X, self and negative", self, ends);
+    // general additions: a running accumulator takes the extreme points in turn, random ones between them
+    Chain gen;
+    for (int round = 0; round < 40; round++)
+        for (size_t i = 0; i < ext.size(); i++) {
+            Affine<Fq2r> p = ext[(i * 7 + round) % ext.size()];
+            if ((i + round) & 1) negate_y(p);
+            gen.push_back(Step{p, false});
+            if (i % 3 == 2) gen.push_back(Step{Affine<Fq2r>{Fq2r{random_canonical<Fq29>(), random_canonical<Fq29>()}, Fq2r{random_canonical<Fq29>(), random_canonical<Fq29>()}}, false});
+        }
+    bad |= run_chain("extreme X, running sum", gen, {});
+    // the half-zero shapes of tests/extreme_inputs.py (half_zero_g2), a fresh affine accumulator meeting the second point:
+    //   (a) / (b) P = U2 - x zero in one component only;  (c) R = 0 with P != 0, and R zero in one component only;
+    //   (d) y with a zero component: P, -P gives P = 0 with R = -2y half zero (infinity, not the doubling), P, P the doubling;
+    //   (e) x with a zero component.  Each pair in both orders.
+    Chain half;
+    std::vector<size_t> hends;
+    const Fq29 vals[4] = {tq, qm, small_fq(3), random_canonical<Fq29>()};
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            if (i == j) continue;
+            const Fq29 s = vals[i], t1 = vals[j], t2 = vals[(j + 1) % 4 == i ? (j + 2) % 4 : (j + 1) % 4];
+            const Fq2r y1{random_canonical<Fq29>(), vals[(i + j) % 4]}, y2{vals[(i + 2 * j) % 4], random_canonical<Fq29>()};
+            const Fq2r y3{y1.a, y2.b}, y4{y2.a, y1.b};
+            const Affine<Fq2r> pairs[][2] = {
+                {{Fq2r{s, t1}, y1}, {Fq2r{s, t2}, y2}},              // (a)
+                {{Fq2r{t1, s}, y1}, {Fq2r{t2, s}, y2}},              // (b)
+                {{Fq2r{s, t1}, y1}, {Fq2r{t1, t2}, y1}},             // (c) R = 0
+                {{Fq2r{s, t1}, y1}, {Fq2r{t1, t2}, y3}},             // R = (0, *)
+                {{Fq2r{s, t1}, y1}, {Fq2r{t1, t2}, y4}},             // R = (*, 0)
+                {{Fq2r{s, t1}, y1}, {Fq2r{s, t2}, y3}},              // P = (0, *) and R = (0, *)
+                {{Fq2r{s, t1}, y1}, {Fq2r{s, t2}, y4}},              // P = (0, *) and R = (*, 0)
+            };
+            for (const auto &pr : pairs)
+                for (int order = 0; order < 2; order++) {
+                    half.push_back(Step{pr[order], true});
+                    half.push_back(Step{pr[1 - order], false});
+                    half.push_back(Step{with_neg_y(pr[order]), false});     // and a general addition on top of the result
+                }
+            const Affine<Fq2r> zc[4] = {{Fq2r{s, t1}, Fq2r{t2, Fq29::zero()}}, {Fq2r{s, t1}, Fq2r{Fq29::zero(), t2}},     // (d)
+                                        {Fq2r{s, Fq29::zero()}, y1}, {Fq2r{Fq29::zero(), s}, y2}};                         // (e)
+            for (const auto &p : zc) {
+                half.push_back(Step{p, true});
+                half.push_back(Step{with_neg_y(p), false});
+                hends.push_back(half.size() - 1);
+                half.push_back(Step{with_neg_y(p), true});
+                half.push_back(Step{with_neg_y(p), false});               // the doubling branch with lazily negated y
+                half.push_back(Step{p, false});
+                half.push_back(Step{p, false});
+                hends.push_back(half.size() - 1);
+            }
+        }
+    bad |= run_chain("half-zero shapes", half, hends);
+    return bad;
+}
+
 int main() {
     if (families()) return 1;
     zk_column_peak() = 0;
@@ -235,6 +528,7 @@ int main() {
     printf("G1 / G2 mixed-addition chains: peak |column| = %.3f * 2^58, overflows %ld\n", (double)zk_column_peak() / 288230376151711744.0,
            zk_column_overflows());
     (void)fq_over;
+    if (g2_chains(tmax_fq())) return 1;
     if (zk_column_overflows()) {
         printf("FAIL: %ld column overflows\n", zk_column_overflows());
         return 1;
