@@ -16,136 +16,38 @@
 //   k_batch_reduce   a wave per 64 values: the product of the f_i and the sum of the r_i C_i, by a fixed tree in LDS; run
 //                    again on its own output until one value a group is left (groups above 64 proofs)
 //   k_batch_tail     a workgroup per group: X and R alpha with mul_glv, the three table-driven pairs under one squaring
-//                    chain, the product with the group's f and the final exponentiation, on the sliced Fq12 operations of
-//                    pairing_coop.hpp (the same lane map as pairing_coop.hip's, whose kernels are left as they are)
+//                    chain, the product with the group's f and the final exponentiation, on pairing_coop_dev.hpp's LDS
+//                    block and sliced Fq12 operations
 // No atomics on points or field elements: every sum has a fixed shape, so the bytes do not depend on scheduling.
-#include <errno.h>
-#include <sys/random.h>
-
-#include "hiputil.hpp"
-#include "devmem.hpp"
-#include "ptcheck.hpp"
-#include "pairing.hpp"
-#include "paircheck.hpp"
-#include "ptengine.hpp"
-#include "mulglv.hpp"
-#include "pairing_coop.hpp"
+//
+// What this unit has in common with pairing_set_batch.hip is written once: what a lane does in the check, scale and Miller
+// kernels, the wave that sums X and the tail's points in verify_batch_dev.hpp; the scalars, the group switch and the
+// report's size in verify_batch_host.hpp.  The kernels here only find the lane's proof.
+#include "verify_batch_dev.hpp"
 #include "pairing_internal.hpp"
 
 namespace {
 
-constexpr uint64_t DEFAULT_GROUP = 1024;              // profiles/verify_batch_timing.txt
-constexpr uint32_t TAIL_THREADS = 192;
-
-struct Scalar16 {
-    uint32_t v[4];
-};
-static_assert(sizeof(Scalar16) == 16, "layout");
-
-// the large pieces as functions of their own (as pairing_coop.hip has them)
-__device__ __noinline__ bool nl_subgroup(const G2Affine &Q, const PairConsts *k) {
-    const zkp::PsiConsts pk{k->gamma1[1], k->gamma1[2]};
-    return zkp::g2_in_subgroup(Q, pk);
-}
-__device__ __noinline__ bool nl_on_curve(const G1Affine &P, const Fq &b) { return on_curve(P, b); }
-__device__ __noinline__ bool nl_on_curve(const G2Affine &Q, const Fq2 &b) { return on_curve(Q, b); }
-__device__ __noinline__ void nl_add(G1XYZZ &a, const G1XYZZ &b) { add(a, b); }
-__device__ __noinline__ void nl_madd(G1XYZZ &a, const G1Affine &b) { madd(a, b); }
-__device__ __noinline__ void nl_dbl(G1XYZZ &a) { a = dbl(a); }
-__device__ __noinline__ void nl_mul_glv(G1XYZZ &r, const G1Affine &P, const Fr &k, const Fq &beta) { r = mul_glv(P, k, beta); }
-__device__ __noinline__ void nl_to_affine(G1Affine &r, const G1XYZZ &p) { r = g1_to_affine(p); }
-
-__device__ __forceinline__ Fr scalar_of(const Scalar16 *p) {
-    const uint4 w = *reinterpret_cast<const uint4 *>(p);
-    Fr r = Fr::zero();
-    r.v[0] = w.x; r.v[1] = w.y; r.v[2] = w.z; r.v[3] = w.w;
-    return r;
-}
-
-// ---------------------------------------------------------------- a lane per proof
-// status[i]: k_verify_check's criteria (without vk_x), the subgroup by psi
+// ---------------------------------------------------------------- a lane per proof: verify_batch_dev.hpp's bodies, lane i has proof i
 __global__ __launch_bounds__(64) void k_batch_check(uint32_t *status, const uint8_t *__restrict__ proofs, const Fr *__restrict__ publics, uint64_t n,
                                                     uint32_t nPublic, const PairConsts *__restrict__ k, Fq b1, Fq2 b2) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint8_t *pr = proofs + i * 256;
-    const G1Affine A = load_pt(reinterpret_cast<const G1Affine *>(pr));
-    const G2Affine B = load_pt(reinterpret_cast<const G2Affine *>(pr + 64));
-    const G1Affine C = load_pt(reinterpret_cast<const G1Affine *>(pr + 192));
-    bool ok = !A.is_inf() && !B.is_inf() && !C.is_inf() && nl_on_curve(A, b1) && nl_on_curve(C, b1) && nl_on_curve(B, b2);
-    const Fr *pub = publics + i * nPublic;
-    for (uint32_t j = 0; ok && j < nPublic; j++) ok = below_r(load_el(pub + j));
-    if (ok) ok = nl_subgroup(B, k);
-    status[i] = ok ? ST_OK : ST_MALFORMED;
+    batch_check_lane(status + i, proofs + i * 256, publics + i * nPublic, nPublic, k, b1, b2);
 }
 
-// ra[i] = r_i A_i (affine), rc[i] = r_i C_i; a malformed proof: rc[i] = infinity, ra[i] is not written.  The scalar is not
-// zero and below 2^128 < r, and A has order r: r_i A_i is never infinity.
 __global__ __launch_bounds__(64) void k_batch_scale(G1Affine *ra, G1XYZZ *rc, const uint32_t *__restrict__ status, const uint8_t *__restrict__ proofs,
                                                     const Scalar16 *__restrict__ scalars, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (status[i] != ST_OK) {
-        store_pt(rc + i, G1XYZZ::inf());
-        return;
-    }
-    const uint8_t *pr = proofs + i * 256;
-    const G1Affine A = load_pt(reinterpret_cast<const G1Affine *>(pr));
-    const G1Affine C = load_pt(reinterpret_cast<const G1Affine *>(pr + 192));
-    const uint4 w = *reinterpret_cast<const uint4 *>(scalars + i);
-    uint32_t k0 = w.x, k1 = w.y, k2 = w.z, k3 = w.w;
-    G1XYZZ a = G1XYZZ::inf(), c = G1XYZZ::inf();
-#pragma unroll 1
-    for (int b = 0; b < 128; b++) {                   // from the top bit; doubling infinity keeps it
-        nl_dbl(a);
-        nl_dbl(c);
-        if (k3 >> 31) {
-            nl_madd(a, A);
-            nl_madd(c, C);
-        }
-        k3 = (k3 << 1) | (k2 >> 31);
-        k2 = (k2 << 1) | (k1 >> 31);
-        k1 = (k1 << 1) | (k0 >> 31);
-        k0 <<= 1;
-    }
-    G1Affine P;
-    nl_to_affine(P, a);
-    store_el(&ra[i].x, P.x);
-    store_el(&ra[i].y, P.y);
-    store_pt(rc + i, c);
+    batch_scale_lane(ra + i, rc + i, status[i], proofs + i * 256, scalars + i);
 }
 
-// f[i]: the Miller value of (r_i A_i, B_i); 1 for a malformed proof, so that the products below need no status
 __global__ __launch_bounds__(64) void k_batch_miller(Fq12 *f_out, const uint32_t *__restrict__ status, const uint8_t *__restrict__ proofs,
                                                      const G1Affine *__restrict__ ra, uint64_t n, const PairConsts *k) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fq12 f;
-    f12_one(f);
-    if (status[i] != ST_OK) {
-        f_out[i] = f;
-        return;
-    }
-    const G2Affine B = load_pt(reinterpret_cast<const G2Affine *>(proofs + i * 256 + 64));
-    const G1Affine P = load_pt(ra + i);
-    G2Proj T{B.x, B.y, Fq2::one()};
-    G2Affine q1, q2;
-    frob_twist(q1, q2, B, *k);
-    Line l;
-    for (int s = 0; s < 64; s++) {
-        f12_sqr(f, f);
-        step_dbl(T, l, *k);
-        f12_mul_line_at(f, l, P);
-        if (ate_bit(s)) {
-            step_add(T, l, B);
-            f12_mul_line_at(f, l, P);
-        }
-    }
-    step_add(T, l, q1);
-    f12_mul_line_at(f, l, P);
-    step_add(T, l, q2);
-    f12_mul_line_at(f, l, P);
-    f_out[i] = f;
+    batch_miller_lane(f_out + i, status[i], proofs + i * 256, ra + i, k);
 }
 
 // ---------------------------------------------------------------- the sums in Fr
@@ -227,156 +129,7 @@ __global__ __launch_bounds__(64) void k_batch_reduce(Fq12 *fout, G1XYZZ *cout, c
 }
 
 // ---------------------------------------------------------------- the tail: a workgroup per group
-// the Fq12 values wave 0 keeps in LDS: the running value, then final_exp's variables under their names there; E_G: the
-// group's product of Miller values
-enum { E_IN, E_F, E_T0, E_T1, E_FX, E_FX2, E_FX3, E_Y0, E_Y2, E_Y3, E_Y4, E_Y6, E_G, E_COUNT };
-
-struct alignas(16) TailLds {
-    Fq2 prod[36];                                     // a_i b_j of the product under way
-    Fq2 e[E_COUNT][6];                                // [value][power of w]
-    G1XYZZ part[64];                                  // X's partial sums
-    G1Affine pt[3];                                   // -R alpha, -X, -Cs
-    uint32_t have[3];
-};
-static_assert(sizeof(TailLds) < 16384, "LDS of a tail workgroup");
-__shared__ TailLds L;
-
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// sliced Fq12, wave 0 only (threadIdx.x < 64): pairing_coop.hpp's lane map
-__device__ __noinline__ void c_mul(int r, int a, int b) {
-    const int lane = threadIdx.x;
-    if (lane < COOP_LANES_FULL) {
-        int i, j;
-        coop_pair_full(lane, i, j);
-        L.prod[lane] = Fq2::mul(L.e[a][i], L.e[b][j]);
-    }
-    wsync();
-    if (lane < 6) L.e[r][lane] = coop_sum(lane, L.prod, COOP_FULL);
-    wsync();
-}
-// f <- f (s P.y + t P.x w + c w^3); P in LDS
-__device__ __noinline__ void c_line(int f, const Line *l, const G1Affine *P) {
-    const int lane = threadIdx.x;
-    if (lane < COOP_LANES_LINE) {
-        int i, j;
-        coop_pair_line(lane, i, j);
-        const Fq2 coef = load_el(j == 0 ? &l->s : j == 1 ? &l->t : &l->c);
-        const Fq scal = j == 0 ? P->y : j == 1 ? P->x : Fq::one();   // times one: the same reduced element
-        Fq2 b;
-        f2_mul_fq(b, coef, scal);
-        L.prod[6 * i + j] = Fq2::mul(L.e[f][i], b);
-    }
-    wsync();
-    if (lane < 6) L.e[f][lane] = coop_sum(lane, L.prod, COOP_LINE);
-    wsync();
-}
-__device__ __noinline__ void c_frob(int r, int a, const PairConsts *k) {
-    const int lane = threadIdx.x;
-    if (lane < 6) {
-        Fq2 x = f2_conj(L.e[a][lane]);
-        if (lane) x = Fq2::mul(x, k->gamma1[lane - 1]);
-        L.e[r][lane] = x;
-    }
-    wsync();
-}
-__device__ __noinline__ void c_frob2(int r, int a, const PairConsts *k) {
-    const int lane = threadIdx.x;
-    if (lane < 6) {
-        Fq2 x = L.e[a][lane];
-        if (lane) f2_mul_fq(x, x, k->gamma2[lane - 1]);
-        L.e[r][lane] = x;
-    }
-    wsync();
-}
-__device__ __forceinline__ void c_conj(int r, int a) {
-    const int lane = threadIdx.x;
-    if (lane < 6) {
-        const Fq2 x = L.e[a][lane];
-        L.e[r][lane] = (lane & 1) ? Fq2::neg(x) : x;
-    }
-    wsync();
-}
-__device__ __forceinline__ void c_copy(int r, int a) {
-    const int lane = threadIdx.x;
-    if (lane < 6) L.e[r][lane] = L.e[a][lane];
-    wsync();
-}
-__device__ __forceinline__ void c_one(int r) {
-    const int lane = threadIdx.x;
-    if (lane < 6) L.e[r][lane] = lane ? Fq2::zero() : Fq2::one();
-    wsync();
-}
-__device__ __noinline__ void c_inv(int r, int a) {
-    if (threadIdx.x == 0) {
-        Fq12 x, y;
-        Fq2 *xs = reinterpret_cast<Fq2 *>(&x), *ys = reinterpret_cast<Fq2 *>(&y);
-        for (int k = 0; k < 6; k++) xs[coop_slot(k)] = L.e[a][k];
-        f12_inv(y, x);
-        for (int k = 0; k < 6; k++) L.e[r][k] = ys[coop_slot(k)];
-    }
-    wsync();
-}
-__device__ __noinline__ void c_pow_x(int r, int a) {  // r != a
-    c_copy(r, a);
-    for (int i = 61; i >= 0; i--) {
-        c_mul(r, r, r);
-        if ((BN_X >> i) & 1) c_mul(r, r, a);
-    }
-}
-// E_F <- final_exp(E_IN): pairing.hpp's chain, line for line
-__device__ __noinline__ void c_final_exp(const PairConsts *k) {
-    c_inv(E_T0, E_IN);
-    c_conj(E_T1, E_IN);
-    c_mul(E_T0, E_T1, E_T0);
-    c_frob2(E_T1, E_T0, k);
-    c_mul(E_F, E_T1, E_T0);
-    c_pow_x(E_FX, E_F);
-    c_pow_x(E_FX2, E_FX);
-    c_pow_x(E_FX3, E_FX2);
-    c_frob(E_T0, E_F, k);
-    c_frob2(E_T1, E_F, k);
-    c_mul(E_Y0, E_T0, E_T1);
-    c_frob(E_T0, E_T1, k);
-    c_mul(E_Y0, E_Y0, E_T0);
-    c_frob2(E_Y2, E_FX2, k);
-    c_frob(E_T0, E_FX, k);
-    c_conj(E_Y3, E_T0);
-    c_frob(E_T0, E_FX2, k);
-    c_mul(E_T0, E_T0, E_FX);
-    c_conj(E_Y4, E_T0);
-    c_frob(E_T0, E_FX3, k);
-    c_mul(E_T0, E_T0, E_FX3);
-    c_conj(E_Y6, E_T0);
-    c_conj(E_FX2, E_FX2);                             // y5
-    c_conj(E_FX, E_F);                                // y1
-    c_mul(E_T0, E_Y6, E_Y6);
-    c_mul(E_T0, E_T0, E_Y4);
-    c_mul(E_T0, E_T0, E_FX2);
-    c_mul(E_T1, E_Y3, E_FX2);
-    c_mul(E_T1, E_T1, E_T0);
-    c_mul(E_T0, E_T0, E_Y2);
-    c_mul(E_T1, E_T1, E_T1);
-    c_mul(E_T1, E_T1, E_T0);
-    c_mul(E_T1, E_T1, E_T1);
-    c_mul(E_T0, E_T1, E_FX);
-    c_mul(E_T1, E_T1, E_Y0);
-    c_mul(E_T0, E_T0, E_T0);
-    c_mul(E_F, E_T0, E_T1);
-}
-
-// -p into L.pt[slot], L.have[slot] = p is not infinity
-__device__ __forceinline__ void put_neg(int slot, const G1XYZZ &p) {
-    G1Affine P;
-    nl_to_affine(P, p);
-    L.have[slot] = P.is_inf() ? 0u : 1u;
-    P.y = Fq::neg(P.y);
-    L.pt[slot] = P;
-}
+__shared__ TailPts<1> T;                             // -R alpha, -X, -Cs
 
 // pass[g] = 1 when group g's equation holds, 0 when it fails; a group without a well-formed proof is left alone.
 // F, Cs: the group's product and sum at index g stride; S, wf: k_batch_fr's; tab: gamma's lines, then delta's
@@ -394,40 +147,26 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_batch_tail(uint8_t *pass, cons
         if (lane == 0) {
             G1XYZZ t;
             nl_mul_glv(t, load_pt(alpha), load_el(Sg + nPublic), beta);
-            put_neg(0, t);
+            put_neg(&T.pt[0][0], &T.have[0][0], t);
         }
     } else if (wave == 1) {
-        if (lane == 0) put_neg(2, load_pt(Cs + g * stride));
+        if (lane == 0) put_neg(&T.pt[0][2], &T.have[0][2], load_pt(Cs + g * stride));
     } else {
-        G1XYZZ acc = G1XYZZ::inf();                   // term j: S_j IC_(j+1); term nPublic: R IC_0
-        for (uint32_t j = lane; j <= nPublic; j += 64) {
-            G1XYZZ t;
-            nl_mul_glv(t, load_pt(ic + (j == nPublic ? 0 : 1 + j)), load_el(Sg + j), beta);
-            nl_add(acc, t);
-        }
-        L.part[lane] = acc;
-        for (uint32_t s = 32; s; s >>= 1) {
-            wsync();
-            if (lane < s) {
-                G1XYZZ a = L.part[lane];
-                const G1XYZZ b = L.part[lane + s];
-                nl_add(a, b);
-                L.part[lane] = a;
-            }
-        }
-        if (lane == 0) put_neg(1, L.part[0]);
+        x_wave(lane, ic, Sg, nPublic, beta);
+        if (lane == 0) put_neg(&T.pt[0][1], &T.have[0][1], L.part[0]);
     }
     __syncthreads();
     if (wave) return;                                 // no barrier below
-    if (lane < 6) L.e[E_G][lane] = load_el(reinterpret_cast<const Fq2 *>(F + g * stride) + coop_slot(lane));
+    // E_T0: the group's product of Miller values, until the final exponentiation takes the slot
+    if (lane < 6) L.e[E_T0][lane] = load_el(reinterpret_cast<const Fq2 *>(F + g * stride) + coop_slot(lane));
     c_one(E_IN);
-    const bool have_x = L.have[1] != 0, have_c = L.have[2] != 0;
+    const bool have_x = T.have[0][1] != 0, have_c = T.have[0][2] != 0;
     const Line *tg = tab, *td = tab + MILLER_LINES;
     int at = 0;
     auto lines3 = [&]() {
-        c_line(E_IN, tab_beta + at, &L.pt[0]);
-        if (have_x) c_line(E_IN, tg + at, &L.pt[1]);
-        if (have_c) c_line(E_IN, td + at, &L.pt[2]);
+        c_line(E_IN, tab_beta + at, &T.pt[0][0]);
+        if (have_x) c_line(E_IN, tg + at, &T.pt[0][1]);
+        if (have_c) c_line(E_IN, td + at, &T.pt[0][2]);
         at++;
     };
     for (int s = 0; s < 64; s++) {
@@ -437,13 +176,9 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_batch_tail(uint8_t *pass, cons
     }
     lines3();
     lines3();
-    c_mul(E_IN, E_IN, E_G);
+    c_mul(E_IN, E_IN, E_T0);
     c_final_exp(k);
-    if (lane == 0) {
-        bool one = L.e[E_F][0] == Fq2::one();
-        for (int c = 1; c < 6; c++) one = one && L.e[E_F][c].is_zero();
-        pass[g] = one ? 1 : 0;
-    }
+    if (lane == 0) pass[g] = c_is_one(E_F) ? 1 : 0;
 }
 
 __global__ void k_batch_beta_lines(Line *tab, const G2Affine *Q, const PairConsts *k) {
@@ -451,37 +186,6 @@ __global__ void k_batch_beta_lines(Line *tab, const G2Affine *Q, const PairConst
 }
 
 // ---------------------------------------------------------------- host
-uint64_t group_size() {
-    const char *e = getenv("ZKHIP_VERIFY_GROUP");
-    if (!e || !*e) return DEFAULT_GROUP;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (*end || *e < '0' || *e > '9' || v < 1 || v > (1ull << 24)) throw std::invalid_argument("ZKHIP_VERIFY_GROUP: a number of proofs from 1 to 2^24 expected");
-    return v;
-}
-
-bool is_zero16(const uint8_t *p) {
-    uint8_t o = 0;
-    for (int i = 0; i < 16; i++) o |= p[i];
-    return o == 0;
-}
-
-void draw_scalars(uint8_t *out, uint64_t n) {
-    for (size_t got = 0, want = (size_t)n * 16; got < want;) {
-        const ssize_t k = getrandom(out + got, want - got, 0);
-        if (k < 0) {
-            if (errno == EINTR) continue;
-            throw std::runtime_error("zk_vkey_verify_batch: the random source failed");
-        }
-        got += (size_t)k;
-    }
-    for (uint64_t i = 0; i < n; i++)
-        while (is_zero16(out + i * 16)) {
-            const ssize_t k = getrandom(out + i * 16, 16, 0);
-            if (k < 0 && errno != EINTR) throw std::runtime_error("zk_vkey_verify_batch: the random source failed");
-        }
-}
-
 // alpha on the device and beta's lines, once per key
 void batch_prepare(zk_vkey *vk, hipStream_t s) {
     if (vk->batch.ready) return;
@@ -500,7 +204,7 @@ void batch_prepare(zk_vkey *vk, hipStream_t s) {
 void verify_batch(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, uint64_t n, const uint8_t *scalars16, uint8_t *verdict,
                   zk_vkey_batch_report *report) {
     if (!vk) throw std::invalid_argument("null argument");
-    const uint32_t rep_size = report ? (report->size && report->size < sizeof *report ? report->size : (uint32_t)sizeof *report) : 0;
+    const uint32_t rep_size = report_size(report);
     zk_vkey_batch_report rep;
     memset(&rep, 0, sizeof rep);
     const uint64_t group = group_size(), chunk = chunk_jobs();
@@ -514,9 +218,7 @@ void verify_batch(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, ui
         return;
     }
     if (!proofs || !verdict || (vk->nPublic && !publics)) throw std::invalid_argument("null argument");
-    if (scalars16)
-        for (uint64_t i = 0; i < n; i++)
-            if (is_zero16(scalars16 + i * 16)) throw std::invalid_argument("zk_vkey_verify_batch: scalar " + std::to_string(i) + " is zero");
+    refuse_zero_scalars(scalars16, n, "zk_vkey_verify_batch");
     std::lock_guard<std::mutex> lock(vk->mu);
     const uint64_t cap = n < chunk ? n : chunk, pub_bytes = (uint64_t)vk->nPublic * 32, terms = (uint64_t)vk->nPublic + 1;
     const uint64_t cap_groups = (cap + group - 1) / group;
@@ -566,7 +268,7 @@ void verify_batch(zk_vkey *vk, const uint8_t *proofs, const uint8_t *publics, ui
         const uint8_t *sc = scalars16 ? scalars16 + off * 16 : nullptr;
         if (!sc) {                                    // drawn now: the proofs of this call are fixed
             drawn.resize(cnt * 16);
-            draw_scalars(drawn.data(), cnt);
+            draw_scalars(drawn.data(), cnt, "zk_vkey_verify_batch");
             sc = drawn.data();
         }
         HIP_TRY(hipMemcpyAsync(dp.p, proofs + off * 256, cnt * 256, hipMemcpyHostToDevice, s));

@@ -9,11 +9,10 @@
 // j in {0, 1, 3} only: 18 lanes.  The sums are exact in Fq2 and every element is kept reduced, so the result has the same
 // bytes as the Karatsuba forms of pairing.hpp.
 #pragma once
-#include <stdlib.h>
-#include <stdexcept>
 #include <string>
 
 #include "pairing.hpp"
+#include "verify_batch_host.hpp"
 
 namespace zk {
 
@@ -46,12 +45,7 @@ ZK_HD Fq2 coop_sum(int k, const Fq2 *prod, uint32_t jmask) {
 
 // ZKHIP_VERIFY_COOP_MAX / ZKHIP_PAIRING_COOP_MAX: the largest number of jobs a call sends down the cooperative path; 0: never
 inline uint64_t coop_threshold(const char *name, const char *jobs, uint64_t dflt) {
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (*end || *e < '0' || *e > '9' || v > (1ull << 24)) throw std::invalid_argument(std::string(name) + ": a number of " + jobs + " from 0 to 2^24 expected");
-    return v;
+    return env_number(name, dflt, 0, 1ull << 24, ("a number of " + std::string(jobs) + " from 0 to 2^24").c_str());
 }
 
 #if defined(__HIPCC__)

@@ -1,7 +1,8 @@
 // The device side of the cooperative (latency) path that its translation units share: the workgroup's LDS block, the
 // sliced Fq12 operations of wave 0, and the body of a workgroup that verifies one proof.  pairing_coop.hip's kernels take
-// the key from their launch arguments, pairing_set.hip's from a record in device memory; both run this code.  Everything
-// here has internal linkage: each unit that includes it gets its own LDS block and its own copies of the functions.
+// the key from their launch arguments, pairing_set.hip's from a record in device memory; both run this code.  The tails of
+// the two batch units (verify_batch_dev.hpp) run on the same LDS block and sliced operations.  Everything here has
+// internal linkage: each unit that includes it gets its own LDS block and its own copies of the functions.
 // The lane map is pairing_coop.hpp's; DESIGN.md section 22 has the division of work and the synchronisation.
 #pragma once
 #include "hiputil.hpp"
@@ -158,6 +159,12 @@ __device__ __noinline__ void c_final_exp(const PairConsts *k) {
     c_mul(E_T0, E_T0, E_T0);
     c_mul(E_F, E_T0, E_T1);
 }
+// is value e one; for the one lane that gives the verdict
+__device__ __forceinline__ bool c_is_one(int e) {
+    bool one = L.e[e][0] == Fq2::one();
+    for (int c = 1; c < 6; c++) one = one && L.e[e][c].is_zero();
+    return one;
+}
 
 // the large pieces as functions of their own: inlined, each kernel would carry several copies of the curve arithmetic
 __device__ __noinline__ bool nl_subgroup(const G2Affine &Q, const PairConsts *k) {
@@ -274,11 +281,7 @@ __device__ __forceinline__ void verify_coop_proof(uint8_t *verdict, const uint8_
     lines3();
     c_mul(E_IN, E_IN, E_T0);
     c_final_exp(k);
-    if (lane == 0) {
-        bool one = L.e[E_F][0] == Fq2::one();
-        for (int c = 1; c < 6; c++) one = one && L.e[E_F][c].is_zero();
-        *verdict = one ? ZK_VERIFY_OK : ZK_VERIFY_INVALID;
-    }
+    if (lane == 0) *verdict = c_is_one(E_F) ? ZK_VERIFY_OK : ZK_VERIFY_INVALID;
 }
 
 }   // namespace

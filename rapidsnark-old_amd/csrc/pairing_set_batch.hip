@@ -13,8 +13,8 @@
 // Kernels, in launch order per chunk:
 //   k_setb_check    a lane per proof over per-wave records (a wave's proofs have one key): k_batch_check's criteria,
 //                   nPublic from the key record
-//   k_setb_scale    a lane per proof: pairing_batch.hip's k_batch_scale, a second copy (that unit is left byte for byte)
-//   k_setb_miller   a lane per proof: pairing_batch.hip's k_batch_miller, a second copy
+//   k_setb_scale    a lane per proof: r_i A_i (made affine) and r_i C_i, as k_batch_scale
+//   k_setb_miller   a lane per proof: the Miller value of (r_i A_i, B_i), as k_batch_miller
 //   k_setb_fr       a wave per (segment, j), j up to the segment's own nPublic: S_sj and R_s by a fixed tree in LDS
 //   k_setb_reduce   a wave per 64 values: the product of the f_i per group and the sum of the r_i C_i per segment, by a
 //                   fixed tree in LDS; run again on its own output while a group has more than one value left
@@ -25,29 +25,20 @@
 // Only the groups and segments with a well-formed proof reach k_setb_fr, k_setb_reduce and k_setb_tail: the host has the
 // status words before it makes their records.  No atomics on points or field elements: every tree's shape is fixed by the
 // indices, so verdicts and intermediate bytes do not depend on scheduling.
-#include <errno.h>
-#include <sys/random.h>
-
-#include <algorithm>
-
-#include "hiputil.hpp"
-#include "pairing_coop_dev.hpp"
+//
+// What this unit has in common with pairing_batch.hip is written once: what a lane does in the check, scale and Miller
+// kernels, the wave that sums X_s and the tail's points in verify_batch_dev.hpp; the scalars, the group switches, the
+// report's size and the chunk's layout (ChunkPlan) in verify_batch_host.hpp.  The kernels here find the lane's proof, and
+// the fr, reduce and tail kernels keep their own structure: ragged records where pairing_batch.hip has a stride.
+#include "verify_batch_dev.hpp"
 #include "pairing_set_internal.hpp"
 
 namespace {
 
-constexpr uint64_t DEFAULT_GROUP = 1024;              // pairing_batch.hip's
 constexpr uint64_t DEFAULT_GROUP_KEYS = 1;            // profiles/verify_set_batch_timing.txt
 constexpr uint64_t MAX_GROUP_KEYS = 65536;
-constexpr uint32_t TAIL_THREADS = 192, TAIL_SEGS = 16;
+constexpr uint32_t TAIL_SEGS = 16;
 
-struct Scalar16 {
-    uint32_t v[4];
-};
-struct BWave {                                        // a wave of the check: `cnt` proofs of key `key` from slot `slot0` on
-    uint64_t pub_at;                                  // where the first lane's signals begin, in signals from the chunk's first
-    uint32_t key, slot0, cnt, reserved;
-};
 struct SegRec {                                       // a segment with a well-formed proof
     uint64_t pub_at;                                  // where the signals of slot `lo` begin
     uint32_t lo, hi;                                  // its slots
@@ -61,17 +52,7 @@ struct GroupRec {                                     // a group with a well-for
 struct Range {                                        // a level of the reduction: `len` values from in_lo become ceil(len / 64) from out_lo
     uint32_t in_lo, len, out_lo;
 };
-static_assert(sizeof(Scalar16) == 16 && sizeof(BWave) == 24 && sizeof(SegRec) == 32 && sizeof(GroupRec) == 16 && sizeof(Range) == 12, "layout");
-
-__device__ __noinline__ void nl_madd(G1XYZZ &a, const G1Affine &b) { madd(a, b); }
-__device__ __noinline__ void nl_dbl(G1XYZZ &a) { a = dbl(a); }
-
-__device__ __forceinline__ Fr scalar_of(const Scalar16 *p) {
-    const uint4 w = *reinterpret_cast<const uint4 *>(p);
-    Fr r = Fr::zero();
-    r.v[0] = w.x; r.v[1] = w.y; r.v[2] = w.z; r.v[3] = w.w;
-    return r;
-}
+static_assert(sizeof(SegRec) == 32 && sizeof(GroupRec) == 16 && sizeof(Range) == 12, "layout");
 
 // the last r below n with key(r) <= b; key(0) <= b.  The same in every lane.
 template <class Key>
@@ -85,8 +66,8 @@ __device__ __forceinline__ uint32_t find_range(uint32_t n, uint32_t b, Key key) 
     return lo;
 }
 
-// ---------------------------------------------------------------- a lane per proof
-// status[slot]: k_batch_check's criteria.  The grid is the chunk's waves exactly; w is the same in every lane.
+// ---------------------------------------------------------------- a lane per proof: verify_batch_dev.hpp's bodies
+// The check's grid is the chunk's waves exactly; w is the same in every lane.  The other two: lane i has slot i.
 __global__ __launch_bounds__(64) void k_setb_check(uint32_t *status, const uint8_t *__restrict__ proofs, const Fr *__restrict__ publics,
                                                    const BWave *__restrict__ waves, const KeyRec *__restrict__ keys, const PairConsts *__restrict__ k, Fq b1,
                                                    Fq2 b2) {
@@ -94,84 +75,21 @@ __global__ __launch_bounds__(64) void k_setb_check(uint32_t *status, const uint8
     if (threadIdx.x >= w.cnt) return;
     const uint32_t nPublic = keys[w.key].nPublic;
     const uint64_t i = (uint64_t)w.slot0 + threadIdx.x;
-    const uint8_t *pr = proofs + i * 256;
-    const G1Affine A = load_pt(reinterpret_cast<const G1Affine *>(pr));
-    const G2Affine B = load_pt(reinterpret_cast<const G2Affine *>(pr + 64));
-    const G1Affine C = load_pt(reinterpret_cast<const G1Affine *>(pr + 192));
-    bool ok = !A.is_inf() && !B.is_inf() && !C.is_inf() && nl_on_curve(A, b1) && nl_on_curve(C, b1) && nl_on_curve(B, b2);
-    const Fr *pub = publics + w.pub_at + (uint64_t)threadIdx.x * nPublic;
-    for (uint32_t j = 0; ok && j < nPublic; j++) ok = below_r(load_el(pub + j));
-    if (ok) ok = nl_subgroup(B, k);
-    status[i] = ok ? ST_OK : ST_MALFORMED;
+    batch_check_lane(status + i, proofs + i * 256, publics + w.pub_at + (uint64_t)threadIdx.x * nPublic, nPublic, k, b1, b2);
 }
 
-// ra[i] = r_i A_i (affine), rc[i] = r_i C_i; a malformed proof: rc[i] = infinity, ra[i] is not written.  The scalar is not
-// zero and below 2^128 < r, and A has order r: r_i A_i is never infinity.
 __global__ __launch_bounds__(64) void k_setb_scale(G1Affine *ra, G1XYZZ *rc, const uint32_t *__restrict__ status, const uint8_t *__restrict__ proofs,
                                                    const Scalar16 *__restrict__ scalars, uint64_t n) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (status[i] != ST_OK) {
-        store_pt(rc + i, G1XYZZ::inf());
-        return;
-    }
-    const uint8_t *pr = proofs + i * 256;
-    const G1Affine A = load_pt(reinterpret_cast<const G1Affine *>(pr));
-    const G1Affine C = load_pt(reinterpret_cast<const G1Affine *>(pr + 192));
-    const uint4 w = *reinterpret_cast<const uint4 *>(scalars + i);
-    uint32_t k0 = w.x, k1 = w.y, k2 = w.z, k3 = w.w;
-    G1XYZZ a = G1XYZZ::inf(), c = G1XYZZ::inf();
-#pragma unroll 1
-    for (int b = 0; b < 128; b++) {                   // from the top bit; doubling infinity keeps it
-        nl_dbl(a);
-        nl_dbl(c);
-        if (k3 >> 31) {
-            nl_madd(a, A);
-            nl_madd(c, C);
-        }
-        k3 = (k3 << 1) | (k2 >> 31);
-        k2 = (k2 << 1) | (k1 >> 31);
-        k1 = (k1 << 1) | (k0 >> 31);
-        k0 <<= 1;
-    }
-    G1Affine P;
-    nl_to_affine(P, a);
-    store_el(&ra[i].x, P.x);
-    store_el(&ra[i].y, P.y);
-    store_pt(rc + i, c);
+    batch_scale_lane(ra + i, rc + i, status[i], proofs + i * 256, scalars + i);
 }
 
-// f[i]: the Miller value of (r_i A_i, B_i); 1 for a malformed proof, so that the products below need no status
 __global__ __launch_bounds__(64) void k_setb_miller(Fq12 *f_out, const uint32_t *__restrict__ status, const uint8_t *__restrict__ proofs,
                                                     const G1Affine *__restrict__ ra, uint64_t n, const PairConsts *k) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fq12 f;
-    f12_one(f);
-    if (status[i] != ST_OK) {
-        f_out[i] = f;
-        return;
-    }
-    const G2Affine B = load_pt(reinterpret_cast<const G2Affine *>(proofs + i * 256 + 64));
-    const G1Affine P = load_pt(ra + i);
-    G2Proj T{B.x, B.y, Fq2::one()};
-    G2Affine q1, q2;
-    frob_twist(q1, q2, B, *k);
-    Line l;
-    for (int s = 0; s < 64; s++) {
-        f12_sqr(f, f);
-        step_dbl(T, l, *k);
-        f12_mul_line_at(f, l, P);
-        if (ate_bit(s)) {
-            step_add(T, l, B);
-            f12_mul_line_at(f, l, P);
-        }
-    }
-    step_add(T, l, q1);
-    f12_mul_line_at(f, l, P);
-    step_add(T, l, q2);
-    f12_mul_line_at(f, l, P);
-    f_out[i] = f;
+    batch_miller_lane(f_out + i, status[i], proofs + i * 256, ra + i, k);
 }
 
 // ---------------------------------------------------------------- the sums in Fr, ragged
@@ -247,20 +165,7 @@ __global__ __launch_bounds__(64) void k_setb_reduce(Fq12 *fout, G1XYZZ *cout, co
 }
 
 // ---------------------------------------------------------------- the tail: a workgroup per group
-struct alignas(16) TailPts {
-    G1Affine pt[TAIL_SEGS][3];                        // per segment of the pass: -R alpha, -X, -Cs
-    uint32_t have[TAIL_SEGS][3];
-};
-__shared__ TailPts T;
-
-// -p into T.pt[q][slot], T.have[q][slot] = p is not infinity
-__device__ __forceinline__ void put_neg(uint32_t q, int slot, const G1XYZZ &p) {
-    G1Affine P;
-    nl_to_affine(P, p);
-    T.have[q][slot] = P.is_inf() ? 0u : 1u;
-    P.y = Fq::neg(P.y);
-    T.pt[q][slot] = P;
-}
+__shared__ TailPts<TAIL_SEGS> T;                     // per segment of the pass: -R alpha, -X, -Cs
 
 // pass[g] = 1 when group g's equation holds, 0 when it fails.  F, Cs: the reduction's outputs (f_at, c_at); S: k_setb_fr's;
 // alpha[key], tab_beta[key][MILLER_LINES]: the set's; keys[key].tab: gamma's lines, then delta's.
@@ -283,32 +188,17 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_setb_tail(uint8_t *pass, const
                 const SegRec sg = segs[s0 + lane];
                 G1XYZZ t;
                 nl_mul_glv(t, load_pt(alpha + sg.key), load_el(S + sg.s_at + keys[sg.key].nPublic), beta);
-                put_neg(lane, 0, t);
+                put_neg(&T.pt[lane][0], &T.have[lane][0], t);
             }
         } else if (wave == 1) {
-            if (lane < np) put_neg(lane, 2, load_pt(Cs + segs[s0 + lane].c_at));
+            if (lane < np) put_neg(&T.pt[lane][2], &T.have[lane][2], load_pt(Cs + segs[s0 + lane].c_at));
         } else {
             for (uint32_t q = 0; q < np; q++) {
                 const SegRec sg = segs[s0 + q];
                 const KeyRec key = keys[sg.key];
-                G1XYZZ acc = G1XYZZ::inf();           // term j: S_j IC_(j+1); term nPublic: R IC_0
-                for (uint32_t j = lane; j <= key.nPublic; j += 64) {
-                    G1XYZZ t;
-                    nl_mul_glv(t, load_pt(key.ic + (j == key.nPublic ? 0 : 1 + j)), load_el(S + sg.s_at + j), beta);
-                    nl_add(acc, t);
-                }
                 wsync();                              // the tree before has been read
-                L.part[lane] = acc;
-                for (uint32_t s = 32; s; s >>= 1) {
-                    wsync();
-                    if (lane < s) {
-                        G1XYZZ a = L.part[lane];
-                        const G1XYZZ b = L.part[lane + s];
-                        nl_add(a, b);
-                        L.part[lane] = a;
-                    }
-                }
-                if (lane == 0) put_neg(q, 1, L.part[0]);
+                x_wave(lane, key.ic, S + sg.s_at, key.nPublic, beta);
+                if (lane == 0) put_neg(&T.pt[q][1], &T.have[q][1], L.part[0]);
             }
         }
         __syncthreads();
@@ -339,11 +229,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_setb_tail(uint8_t *pass, const
     if (wave) return;                                 // no barrier below
     c_copy(E_IN, E_T0);
     c_final_exp(k);
-    if (lane == 0) {
-        bool one = L.e[E_F][0] == Fq2::one();
-        for (int c = 1; c < 6; c++) one = one && L.e[E_F][c].is_zero();
-        pass[blockIdx.x] = one ? 1 : 0;
-    }
+    if (lane == 0) pass[blockIdx.x] = c_is_one(E_F) ? 1 : 0;
 }
 
 // tab[key][MILLER_LINES]: the lines of beta_key, a lane per key
@@ -354,37 +240,6 @@ __global__ __launch_bounds__(64) void k_setb_ab(Line *tab, const G2Affine *__res
 }
 
 // ---------------------------------------------------------------- host
-uint64_t env_number(const char *name, uint64_t dflt, uint64_t max, const char *what) {
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (*end || *e < '0' || *e > '9' || v < 1 || v > max) throw std::invalid_argument(std::string(name) + ": " + what + " expected");
-    return v;
-}
-
-bool is_zero16(const uint8_t *p) {
-    uint8_t o = 0;
-    for (int i = 0; i < 16; i++) o |= p[i];
-    return o == 0;
-}
-
-void draw_scalars(uint8_t *out, uint64_t n) {
-    for (size_t got = 0, want = (size_t)n * 16; got < want;) {
-        const ssize_t k = getrandom(out + got, want - got, 0);
-        if (k < 0) {
-            if (errno == EINTR) continue;
-            throw std::runtime_error("zk_vkey_set_verify_batch: the random source failed");
-        }
-        got += (size_t)k;
-    }
-    for (uint64_t i = 0; i < n; i++)
-        while (is_zero16(out + i * 16)) {
-            const ssize_t k = getrandom(out + i * 16, 16, 0);
-            if (k < 0 && errno != EINTR) throw std::runtime_error("zk_vkey_set_verify_batch: the random source failed");
-        }
-}
-
 // alpha_k on the device and beta_k's lines for every key, once per set, one launch
 void batch_prepare(zk_vkey_set *set, hipStream_t s) {
     const uint32_t n_keys = (uint32_t)set->nPublic.size();
@@ -400,70 +255,16 @@ void batch_prepare(zk_vkey_set *set, hipStream_t s) {
     set->batch.ready = true;
 }
 
-// The layout of one chunk: the proofs of caller positions off .. off + cnt - 1 in slots ordered by key (keys rising, a
-// key's proofs in the caller's order), the waves of the check, and the groups and segments by position.
-struct Seg {
-    uint32_t lo, hi, key;
-    uint64_t pub_at;                                  // where the signals of slot `lo` begin
-};
-struct ChunkPlan {
-    std::vector<uint64_t> count, slot0, pub0;         // per key: its proofs in the chunk, its first slot, its first signal
-    std::vector<uint32_t> present;                    // the keys with proofs in the chunk
-    std::vector<BWave> waves;
-    std::vector<Seg> segs;
-    std::vector<uint32_t> group_seg0;                 // per group its first segment; one more entry closes the last
-    uint64_t npub = 0;
-    explicit ChunkPlan(size_t n_keys) : count(n_keys, 0), slot0(n_keys), pub0(n_keys) {}
-    void plan(const uint32_t *key_of, uint64_t cnt, const std::vector<uint32_t> &nPublic, uint64_t group, uint64_t group_keys) {
-        for (uint32_t k : present) count[k] = 0;
-        present.clear();
-        waves.clear();
-        segs.clear();
-        group_seg0.clear();
-        npub = 0;
-        for (uint64_t i = 0; i < cnt; i++)
-            if (count[key_of[i]]++ == 0) present.push_back(key_of[i]);
-        std::sort(present.begin(), present.end());
-        uint64_t slot = 0, in_group = 0, keys_in_group = 0;
-        for (uint32_t k : present) {
-            slot0[k] = slot;
-            pub0[k] = npub;
-            const uint64_t end = slot + count[k];
-            for (uint64_t done = 0; done < count[k]; done += 64) {
-                const uint32_t live = (uint32_t)(count[k] - done < 64 ? count[k] - done : 64);
-                waves.push_back(BWave{npub + done * nPublic[k], k, (uint32_t)(slot + done), live, 0});
-            }
-            bool fresh = true;                        // k is not yet in the open group
-            while (slot < end) {
-                if (in_group == 0 || (fresh && keys_in_group == group_keys)) {   // a new group opens
-                    group_seg0.push_back((uint32_t)segs.size());
-                    in_group = keys_in_group = 0;
-                    fresh = true;
-                }
-                const uint64_t take = std::min(end - slot, group - in_group);
-                segs.push_back(Seg{(uint32_t)slot, (uint32_t)(slot + take), k, npub + (slot - slot0[k]) * nPublic[k]});
-                keys_in_group += fresh;
-                fresh = false;
-                in_group += take;
-                slot += take;
-                if (in_group == group) in_group = 0;  // full: the next proof opens a group
-            }
-            npub += count[k] * nPublic[k];
-        }
-        group_seg0.push_back((uint32_t)segs.size());
-    }
-};
-
 uint64_t ceil64(uint64_t v) { return (v + 63) / 64; }
 
 void set_verify_batch(zk_vkey_set *set, const uint8_t *proofs, const uint32_t *key_of, const uint8_t *publics, uint64_t publics_bytes, uint64_t n,
                       const uint8_t *scalars16, uint8_t *verdict, zk_vkey_set_batch_report *report) {
     if (!set) throw std::invalid_argument("null argument");
-    const uint32_t rep_size = report ? (report->size && report->size < sizeof *report ? report->size : (uint32_t)sizeof *report) : 0;
+    const uint32_t rep_size = report_size(report);
     zk_vkey_set_batch_report rep;
     memset(&rep, 0, sizeof rep);
-    const uint64_t group = env_number("ZKHIP_VERIFY_GROUP", DEFAULT_GROUP, 1ull << 24, "a number of proofs from 1 to 2^24");
-    const uint64_t group_keys = env_number("ZKHIP_VERIFY_GROUP_KEYS", DEFAULT_GROUP_KEYS, MAX_GROUP_KEYS, "a number of keys from 1 to 65536");
+    const uint64_t group = group_size();
+    const uint64_t group_keys = env_number("ZKHIP_VERIFY_GROUP_KEYS", DEFAULT_GROUP_KEYS, 1, MAX_GROUP_KEYS, "a number of keys from 1 to 65536");
     const uint64_t chunk = chunk_jobs();
     rep.size = rep_size;
     rep.group = (uint32_t)group;
@@ -491,9 +292,7 @@ void set_verify_batch(zk_vkey_set *set, const uint8_t *proofs, const uint32_t *k
         throw std::invalid_argument("zk_vkey_set_verify_batch: publics_bytes: " + std::to_string(total * 32) + " expected (" + std::to_string(total) +
                                     " signals of 32 bytes), " + std::to_string(publics_bytes) + " given");
     if (total && !publics) throw std::invalid_argument("null argument");
-    if (scalars16)
-        for (uint64_t i = 0; i < n; i++)
-            if (is_zero16(scalars16 + i * 16)) throw std::invalid_argument("zk_vkey_set_verify_batch: scalar " + std::to_string(i) + " is zero");
+    refuse_zero_scalars(scalars16, n, "zk_vkey_set_verify_batch");
     std::lock_guard<std::mutex> lock(set->mu);
     DeviceGuard dg(set->device);
     const uint64_t cap = n < chunk ? n : chunk;
@@ -574,7 +373,7 @@ void set_verify_batch(zk_vkey_set *set, const uint8_t *proofs, const uint32_t *k
         const uint8_t *sc = scalars16 ? scalars16 + off * 16 : nullptr;
         if (!sc) {                                    // drawn now: the proofs of this call are fixed
             drawn.resize(cnt * 16);
-            draw_scalars(drawn.data(), cnt);
+            draw_scalars(drawn.data(), cnt, "zk_vkey_set_verify_batch");
             sc = drawn.data();
         }
         for (uint32_t k : lay.present) filled[k] = 0;

@@ -1,6 +1,6 @@
 """zk_vkey_set_verify_batch without a device: the header declares the entry and its report, the ctypes struct has the C
-layout (a C program prints sizeof and the offsets), the export is bound, and VerificationKeySet.verify_batch refuses bad
-arguments before any library call."""
+layout (a C program prints sizeof and the offsets), the export is bound, VerificationKeySet.verify_batch refuses bad
+arguments before any library call, and the host code the two batch entries share passes its own program's checks."""
 import ctypes
 import os
 import re
@@ -41,6 +41,18 @@ def test_ctypes_report_has_the_c_layout(tmp_path):
     assert [name for name, _ in L.zk_vkey_set_batch_report._fields_] == FIELDS
     assert got == [ctypes.sizeof(L.zk_vkey_set_batch_report)] + [getattr(L.zk_vkey_set_batch_report, f).offset for f in FIELDS] + [40, 48]
     assert got[0] == 56
+
+
+def test_shared_host_code_under_the_sanitizers(tmp_path):
+    """csrc/verify_batch_host.hpp alone, in a program of its own (tools/verify_batch_host_test.cpp): the strict reading of the
+    group switches, 4096 drawn scalars (none zero, no two equal), the refusal of a zero scalar, the report's size, and
+    ChunkPlan against a restatement of the grouping rule on the key_of layouts of the device tests."""
+    exe = str(tmp_path / "verify_batch_host_test")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "rapidsnark-old_amd", "csrc"), os.path.join(ROOT, "tools", "verify_batch_host_test.cpp"), "-o", exe])
+    env = {k: v for k, v in os.environ.items() if not k.startswith("ZKHIP_")}
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert out.returncode == 0 and "OK: env_number, scalars, report size and ChunkPlan" in out.stdout, out.stdout + out.stderr
 
 
 def test_the_export_is_bound():
