@@ -1,6 +1,6 @@
-// Device-side moves of field elements and points between HBM and registers, and the per-lane double-and-add over
-// them: the one definition every kernel file uses (msm_*.hip, ntt.hip, nttpair.hip, fieldops.hip, synth.hip, r1cs.hip,
-// setup.hip, ptau_prepare.hip).  The plain 8 x 32-bit forms of field.hpp / curve.hpp only: msm_lanes.hpp's Reg<>-converting
+// Device-side moves of field elements and points between HBM and registers (and, for the scans over Fr, between the lanes
+// of a wave), and the per-lane double-and-add over them: the one definition every kernel file uses (msm_*.hip, ntt.hip,
+// nttpair.hip, fieldops.hip, synth.hip, r1cs.hip, setup.hip, ptau_prepare.hip, kzg.hip, frscan.hip).  The plain 8 x 32-bit forms of field.hpp / curve.hpp only: msm_lanes.hpp's Reg<>-converting
 // load_affine / load_xyzz / store_xyzz*, its load_row_el and the twiddle loaders of ntt.hip / nttpair.hip stay with
 // their kernels.
 #pragma once
@@ -30,6 +30,35 @@ __device__ __forceinline__ Fq2 load_el(const Fq2 *p) { return Fq2{load_el(&p->a)
 __device__ __forceinline__ void store_el(Fq2 *p, const Fq2 &r) {
     store_el(&p->a, r.a);
     store_el(&p->b, r.b);
+}
+
+// ---- what the tiers of a scan over Fr share (kzg.hip: division by X - z; frscan.hip: running products)
+// a's value in the lane d places up / down the wave (the lane's own where there is none)
+__device__ __forceinline__ Fr shfl_down_fr(const Fr &a, uint32_t d) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = __shfl_down(a.v[i], d, 64);
+    return r;
+}
+__device__ __forceinline__ Fr shfl_up_fr(const Fr &a, uint32_t d) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = __shfl_up(a.v[i], d, 64);
+    return r;
+}
+// A wave-uniform element (a weight, a sum another workgroup left) loaded into VECTOR registers and kept there: the scalar
+// file is what the products' carry chains and constants fill, and uniform operands held in it spilled
+__device__ __forceinline__ Fr load_uniform(const Fr *p) {
+    Fr r = load_el(p);
+#pragma unroll
+    for (int i = 0; i < 8; i++) __asm__ volatile("" : "+v"(r.v[i]));
+    return r;
+}
+// elements [lo, lo + cnt) of n are this lane's, seg a lane; first_lane: the workgroup's first lane in the grid
+__device__ __forceinline__ uint32_t lane_span(uint64_t &lo, uint64_t first_lane, uint64_t n, uint32_t seg) {
+    lo = (first_lane + threadIdx.x) * seg;
+    if (lo >= n) return 0;
+    return n - lo < seg ? (uint32_t)(n - lo) : seg;
 }
 
 // whole points, coordinate by coordinate (no conversion: the table's form is the registers' form)

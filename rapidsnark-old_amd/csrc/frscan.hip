@@ -8,7 +8,8 @@
 //     1 / a_i = (exclusive prefix product of a)_i * (exclusive suffix product of a)_i / T:
 // a prefix scan, a suffix scan and ONE inversion for the whole vector.
 //
-// Tiers, section 26's, with the operator P_i = a_i P_(i-1) (no weights: a product has none):
+// Tiers (the lane's span, the shuffles and the uniform loads are devmem.hpp's), with the operator P_i = a_i P_(i-1) (no
+// weights: a product has none):
 //   lane       `seg` consecutive elements by a chain of products (ZKHIP_SCAN_SEG, read at every call)
 //   wave       64 lanes: a prefix scan of the lanes' products by six __shfl_up steps, a suffix scan by six __shfl_down steps
 //   workgroup  4 waves: their totals meet in LDS
@@ -24,7 +25,7 @@
 // of m such factors from a Montgomery seed carries R^-m, which depends on the lane map only, and the host hands the kernels
 // the two powers of R that cancel it (ScanConsts::lift, ::tail).  A lane short of seg elements pads its chain with products
 // by 1, so that every lane carries the same power.  Everything a tier above the lane touches is Montgomery.
-// Field arithmetic: field.hpp's 8 x 32-bit Fr, as kzg.hip.
+// Field arithmetic: field.hpp's 8 x 32-bit Fr.
 #include "hiputil.hpp"
 #include "devmem.hpp"
 #include "ptengine.hpp"
@@ -35,8 +36,6 @@ constexpr uint32_t SC_WG = 256, SC_WAVES = SC_WG / 64;
 constexpr uint32_t DEFAULT_SEG = 8, MAX_SEG = 4096;   // the default: the best of profiles/frscan_timing.txt's sweep at 2^20
 constexpr uint32_t MAX_COLS = 8, MAX_LOG_N = 28, POW_TAB = 32;
 constexpr int OP_PREFIX = 0, OP_INVERSE = 1, OP_GRAND = 2, OP_PLONK = 3;
-// w_(2^28), standard form (ntt.hip)
-const uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
 
 static_assert(sizeof(Fr) == 32, "layout");
 
@@ -64,28 +63,6 @@ struct ScanArgs {
     Fr *before, *behind;                              // per workgroup: what lies before it (num) / behind it (den)
 };
 
-__device__ __forceinline__ Fr shfl_down_fr(const Fr &a, uint32_t d) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = __shfl_down(a.v[i], d, 64);
-    return r;
-}
-__device__ __forceinline__ Fr shfl_up_fr(const Fr &a, uint32_t d) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = __shfl_up(a.v[i], d, 64);
-    return r;
-}
-
-// A wave-uniform element loaded into VECTOR registers and kept there (kzg.hip's: uniform operands held in the scalar file
-// spilled)
-__device__ __forceinline__ Fr load_uniform(const Fr *p) {
-    Fr r = load_el(p);
-#pragma unroll
-    for (int i = 0; i < 8; i++) __asm__ volatile("" : "+v"(r.v[i]));
-    return r;
-}
-
 __device__ __forceinline__ Fr raw_one() {             // 1 in standard form: a product by it divides by R
     Fr r = Fr::zero();
     r.v[0] = 1;
@@ -109,13 +86,6 @@ __device__ __forceinline__ Fr wave_suffix(Fr v, uint32_t lane) {
         if (lane + (1u << k) < 64) v = Fr::mul(v, t);
     }
     return v;
-}
-
-// elements [lo, lo + cnt) of n are this lane's
-__device__ __forceinline__ uint32_t lane_span(uint64_t &lo, uint64_t first_lane, uint64_t n, uint32_t seg) {
-    lo = (first_lane + threadIdx.x) * seg;
-    if (lo >= n) return 0;
-    return n - lo < seg ? (uint32_t)(n - lo) : seg;
 }
 
 // A lane's walk over its elements: num(p, i) multiplies p by the forward factors of element i (called with rising i),
@@ -375,22 +345,7 @@ __global__ __launch_bounds__(SC_WG) void k_scan_zero_den(uint64_t *low, ScanArgs
 }
 
 // ---------------------------------------------------------------- host
-uint32_t seg_in_effect() {
-    const char *e = getenv("ZKHIP_SCAN_SEG");
-    if (!e || !*e) return DEFAULT_SEG;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (*end || v < 1 || v > MAX_SEG) throw std::invalid_argument("ZKHIP_SCAN_SEG: a number of elements per lane from 1 to 4096 expected");
-    return (uint32_t)v;
-}
-
-Fr root_of_unity(uint32_t log_n) {                    // the 2^log_n-th root zk_fr_ntt uses
-    Fr w;
-    for (int i = 0; i < 8; i++) w.v[i] = ROOT_2_28_STD[i];
-    w = Fr::to_mont(w);
-    for (uint32_t i = log_n; i < MAX_LOG_N; i++) w = Fr::sqr(w);
-    return w;
-}
+uint32_t seg_in_effect() { return (uint32_t)env_number("ZKHIP_SCAN_SEG", DEFAULT_SEG, 1, MAX_SEG, "a number of elements per lane from 1 to 4096", ENV_LAX); }
 
 // the residue R^k mod r
 Fr r_power(uint64_t k) {
@@ -400,13 +355,6 @@ Fr r_power(uint64_t k) {
         return one;
     }
     return fr_pow(Fr::r2(), k - 1);                   // Montgomery arithmetic on the value R: (R)^(k-1), times R
-}
-
-// the lowest index of n scalars (32 bytes LE) that is not below r, n when there is none
-uint64_t first_not_below_r(const uint8_t *sc, uint64_t n) {
-    for (uint64_t i = 0; i < n; i++)
-        if (!below(sc + i * 32, FrParams::P)) return i;
-    return n;
 }
 
 // what lies between the launches; grown, never shrunk

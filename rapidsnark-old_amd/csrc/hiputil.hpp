@@ -1,6 +1,7 @@
 // Host-side helpers of libzkhip's entry points that know nothing of the prover object: RAII around HIP memory, streams
-// and the current device, the exception -> status-code boundary of the C-ABI, and the admission check against the free
-// HBM.  Every translation unit with entry points includes it (the prover's through prover_internal.hpp).
+// and the current device, the exception -> status-code boundary of the C-ABI, the admission check against the free HBM,
+// the upload of a .ptau's Lagrange level and the host's root of unity.  Every translation unit with entry points includes
+// it (the prover's through prover_internal.hpp), and with it hostutil.hpp, the helpers that need no HIP.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -13,6 +14,7 @@
 #include "../../include/zkhip.h"
 #include "common.hpp"
 #include "hipcheck.hpp"
+#include "hostutil.hpp"
 #include "kernels.hpp"
 
 using namespace zk;
@@ -98,6 +100,14 @@ struct StreamUploader {
         }
     }
 };
+
+// d <- level p (2^p points of pt_bytes each, from point 2^p - 1 on) of a Lagrange section of a prepared .ptau
+inline void upload_level(DevBuf<uint8_t> &d, const void *section, uint32_t p, uint64_t pt_bytes, hipStream_t s) {
+    const uint64_t count = 1ull << p;
+    d.alloc(count * pt_bytes);
+    StreamUploader up(s);
+    up.copy(d.p, static_cast<const uint8_t *>(section) + (count - 1) * pt_bytes, count * pt_bytes);
+}
 
 // a non-blocking stream of an entry point's own, drained and destroyed when the call leaves
 struct Stream {
@@ -216,6 +226,17 @@ inline uint32_t ilog2_exact(uint64_t n) {
     while ((1ull << l) < n) l++;
     if ((1ull << l) != n) throw std::invalid_argument("domainSize is not a power of two");
     return l;
+}
+
+// w_(2^28), standard form (ntt.hip and nttpair.hip keep the device's copies), and the 2^log_n-th root zk_fr_ntt uses
+// (log_n <= 28, Montgomery): the host's, for ptau_prepare.hip, ptau_check.hip and frscan.hip
+constexpr uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
+inline Fr root_of_unity(uint32_t log_n) {
+    Fr w;
+    for (int i = 0; i < 8; i++) w.v[i] = ROOT_2_28_STD[i];
+    w = Fr::to_mont(w);
+    for (uint32_t i = log_n; i < 28; i++) w = Fr::sqr(w);
+    return w;
 }
 
 inline uint32_t nblocks(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }

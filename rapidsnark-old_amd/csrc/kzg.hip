@@ -36,6 +36,7 @@
 #include "mulglv.hpp"
 #include "ptengine.hpp"
 #include "pairing_internal.hpp"
+#include "verify_batch_host.hpp"
 
 namespace {
 
@@ -52,22 +53,6 @@ struct DivPows {
     Fr lane[6];                                       // z^(seg 2^k): between lanes 2^k apart
     Fr wave;                                          // z^(64 seg): between waves
 };
-
-__device__ __forceinline__ Fr shfl_down_fr(const Fr &a, uint32_t d) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.v[i] = __shfl_down(a.v[i], d, 64);
-    return r;
-}
-
-// A wave-uniform element (a weight, a sum another workgroup left) loaded into VECTOR registers and kept there: the scalar
-// file is what the products' carry chains and constants fill, and uniform operands held in it spilled
-__device__ __forceinline__ Fr load_uniform(const Fr *p) {
-    Fr r = load_el(p);
-#pragma unroll
-    for (int i = 0; i < 8; i++) __asm__ volatile("" : "+v"(r.v[i]));
-    return r;
-}
 
 // sum_(k < cnt) c[k] z^k
 __device__ __forceinline__ Fr horner(const Fr *__restrict__ c, uint32_t cnt, const Fr &z) {
@@ -95,13 +80,6 @@ __device__ __forceinline__ Fr behind_wave(Fr behind, uint32_t w, const DivPows *
 #pragma unroll 1
     for (uint32_t j = DIV_WAVES - 1; j > w; j--) behind = Fr::add(sum_of(j), Fr::mul(pw, behind));
     return behind;
-}
-
-// elements [lo, lo + cnt) of n are this lane's
-__device__ __forceinline__ uint32_t lane_span(uint64_t &lo, uint64_t first_lane, uint64_t n, uint32_t seg) {
-    lo = (first_lane + threadIdx.x) * seg;
-    if (lo >= n) return 0;
-    return n - lo < seg ? (uint32_t)(n - lo) : seg;
 }
 
 // wsum[4 g + w]: the sum of wave w of workgroup g (weights from the wave's first element), gsum[g]: the workgroup's
@@ -231,14 +209,7 @@ __global__ __launch_bounds__(64) void k_kzg_pair(uint8_t *verdict, const uint32_
 }
 
 // ---------------------------------------------------------------- host: division
-uint32_t seg_in_effect() {
-    const char *e = getenv("ZKHIP_KZG_SEG");
-    if (!e || !*e) return DEFAULT_SEG;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (*end || v < 1 || v > MAX_SEG) throw std::invalid_argument("ZKHIP_KZG_SEG: a number of coefficients per lane from 1 to 4096 expected");
-    return (uint32_t)v;
-}
+uint32_t seg_in_effect() { return (uint32_t)env_number("ZKHIP_KZG_SEG", DEFAULT_SEG, 1, MAX_SEG, "a number of coefficients per lane from 1 to 4096", ENV_LAX); }
 
 DivPows make_pows(const Fr &base, uint64_t seg) {
     DivPows p;
@@ -281,13 +252,6 @@ void launch_divide(Fr *q, Fr *y, const Fr *c, uint64_t n, const Fr &z, uint32_t 
     ZK_LAUNCH(k_div_carry, dim3(1), dim3(DIV_WG), 0, s, w.behind.p, w.gsum.p, groups, cseg, w.pows.p + 1);
     ZK_LAUNCH(k_div_apply, dim3((uint32_t)groups), dim3(DIV_WG), 0, s, q, y, c, w.wsum.p, w.behind.p, n, seg, w.pows.p);
     ZK_LAUNCH_OK("division by X - z");
-}
-
-// the lowest index of n scalars (32 bytes LE) that is not below r, n when there is none
-uint64_t first_not_below_r(const uint8_t *sc, uint64_t n) {
-    for (uint64_t i = 0; i < n; i++)
-        if (!below(sc + i * 32, FrParams::P)) return i;
-    return n;
 }
 
 void fr_poly_divide(uint8_t *q, uint8_t *y, const uint8_t *coeffs, uint64_t n, const uint8_t *z, int32_t device) {
@@ -364,31 +328,16 @@ struct LaunchCount {
     ~LaunchCount() { k->last_launches = (uint32_t)(g_kernel_launches.load(std::memory_order_relaxed) - at); }
 };
 
-void classify_or_throw(uint32_t sec, uint64_t first, const uint32_t err[4]) {
-    static const uint32_t order[4] = {0, 1, 3, 2};    // k_ptau_classify's words 0, 1, 3, then the subgroup kernel's
-    static const char *const text[4] = {"has a coordinate that is not below q", "is not on the curve", "is not in the subgroup", "is the point at infinity"};
-    uint32_t lowest = NONE, kind = 0;
-    for (uint32_t w : order)
-        if (err[w] < lowest) lowest = err[w], kind = w;
-    if (lowest != NONE)
-        throw std::invalid_argument("zk_kzg_create: ptau section " + std::to_string(sec) + ": point " + std::to_string(first + lowest) + " " + text[kind]);
-}
-
+// ptengine.hpp's pass over n points of section `sec` from its point `first` on; psi (section 3): the subgroup test too.
+// There the two points go through both kernels before the words are read: point 0 is the generator (compared before), so
+// point 1 is the only one either kernel can name, and the pick's order (hostutil.hpp) says which kind comes first.
 template <class F>
-void classify(uint32_t sec, const Affine<F> *pts, uint64_t n, uint32_t inf_bad, uint32_t *d_err, const PsiConsts *psi, hipStream_t s) {
-    uint32_t err[4];
-    HIP_TRY(hipMemsetAsync(d_err, 0xFF, 16, s));
-    ZK_LAUNCH(k_ptau_classify<F>, dim3(nblocks(n, 256)), dim3(256), 0, s, d_err, pts, n, curve_b<F>(), inf_bad);
-    ZK_LAUNCH_OK("point check");
-    HIP_TRY(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    classify_or_throw(sec, 0, err);
-    if constexpr (sizeof(F) == sizeof(Fq2)) {         // on the twist: now the subgroup, point 0 is the generator itself
-        launch_subgroup(nullptr, d_err + 2, pts, n, *psi, plain_subgroup(), s);
-        HIP_TRY(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        classify_or_throw(sec, 0, err);
-    }
+void classify(uint32_t sec, uint64_t first, const Affine<F> *pts, uint64_t n, bool inf_bad, uint32_t *d_err, const PsiConsts *psi, hipStream_t s) {
+    uint32_t h[4];
+    enqueue_classify<F>(h, d_err, pts, n, inf_bad, psi, plain_subgroup(), s);
+    const BadPoint b = classified(h, s);
+    if (b.kind)
+        throw std::invalid_argument("zk_kzg_create: ptau section " + std::to_string(sec) + ": point " + std::to_string(first + b.index) + " " + KIND_TEXT[b.kind]);
 }
 
 zk_kzg *kzg_create(const zk_kzg_view *v, uint64_t max_coeffs, uint32_t lagrange_log_n, int32_t device) {
@@ -440,20 +389,14 @@ zk_kzg *kzg_create(const zk_kzg_view *v, uint64_t max_coeffs, uint32_t lagrange_
     const PsiConsts psi = psi_consts();
     k->tau.alloc(max_coeffs);
     up.copy(k->tau.p, v->tau_g1, max_coeffs * sizeof(G1Affine));
-    classify<Fq>(2, k->tau.p, max_coeffs, 1, derr.p, nullptr, s);
+    classify<Fq>(2, 0, k->tau.p, max_coeffs, true, derr.p, nullptr, s);
     if (want_lag) {
         k->lag.alloc(lag_n);
         up.copy(k->lag.p, (const uint8_t *)v->lagrange_g1 + (lag_n - 1) * sizeof(G1Affine), lag_n * sizeof(G1Affine));
-        uint32_t err[4];
-        HIP_TRY(hipMemsetAsync(derr.p, 0xFF, 16, s));
-        ZK_LAUNCH(k_ptau_classify<Fq>, dim3(nblocks(lag_n, 256)), dim3(256), 0, s, derr.p, k->lag.p, lag_n, curve_b<Fq>(), 0u);
-        ZK_LAUNCH_OK("point check");
-        HIP_TRY(hipMemcpyAsync(err, derr.p, 16, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        classify_or_throw(12, lag_n - 1, err);       // the index within the section
+        classify<Fq>(12, lag_n - 1, k->lag.p, lag_n, false, derr.p, nullptr, s);       // the index within the section
     }
     HIP_TRY(hipMemcpyAsync(d2.p, v->tau_g2, 2 * sizeof(G2Affine), hipMemcpyHostToDevice, s));
-    classify<Fq2>(3, d2.p, 2, 1, derr.p, &psi, s);
+    classify<Fq2>(3, 0, d2.p, 2, true, derr.p, &psi, s);
     // every point is what the file may hold: now the forms the kernels read
     launch_fq_to_internal(reinterpret_cast<Fq *>(k->tau.p), max_coeffs * 2, s);
     if (want_lag) launch_fq_to_internal(reinterpret_cast<Fq *>(k->lag.p), lag_n * 2, s);
@@ -582,25 +525,6 @@ void kzg_verify(zk_kzg *k, const uint8_t *commitments, const uint8_t *zs, const 
     }
 }
 
-void draw_scalars16(std::vector<uint8_t> &r, uint64_t m) {
-    r.resize(m * 16);
-    auto fill = [](uint8_t *p, size_t len) {
-        size_t got = 0;
-        while (got < len) {
-            const ssize_t n = getrandom(p + got, len - got, 0);
-            if (n < 0) {
-                if (errno == EINTR) continue;
-                throw std::runtime_error("zk_kzg_verify_batch: the random source failed");
-            }
-            got += (size_t)n;
-        }
-    };
-    fill(r.data(), r.size());
-    static const uint8_t zero[16] = {0};
-    for (uint64_t i = 0; i < m; i++)
-        while (memcmp(r.data() + i * 16, zero, 16) == 0) fill(r.data() + i * 16, 16);
-}
-
 void kzg_verify_batch(zk_kzg *k, const uint8_t *commitments, const uint8_t *zs, const uint8_t *ys, const uint8_t *proofs, uint64_t m,
                       const uint8_t *scalars16, uint8_t *verdict) {
     if (!k || !verdict) throw std::invalid_argument("null argument");
@@ -611,12 +535,10 @@ void kzg_verify_batch(zk_kzg *k, const uint8_t *commitments, const uint8_t *zs, 
     if (!commitments || !zs || !ys || !proofs) throw std::invalid_argument("null argument");
     if (m >= (1ull << 31)) throw std::invalid_argument("zk_kzg_verify_batch: m is not below 2^31");
     std::vector<uint8_t> drawn;
-    if (scalars16) {
-        static const uint8_t zero[16] = {0};
-        for (uint64_t i = 0; i < m; i++)
-            if (memcmp(scalars16 + i * 16, zero, 16) == 0) throw std::invalid_argument("zk_kzg_verify_batch: scalar " + std::to_string(i) + " is zero");
-    } else {
-        draw_scalars16(drawn, m);
+    refuse_zero_scalars(scalars16, m, "zk_kzg_verify_batch");
+    if (!scalars16) {
+        drawn.resize(m * 16);
+        draw_scalars(drawn.data(), m, "zk_kzg_verify_batch");
         scalars16 = drawn.data();
     }
     std::lock_guard<std::mutex> lock(k->mu);

@@ -32,11 +32,12 @@
 // Scalars come from the host (zk_g*_mul_vec: 32 bytes a point) or are made by the lane (zk_g*_power_scale and the
 // contribution: c base^(first_exp + i) from ptengine.hpp's table of squarings, so tau's powers never exist in host
 // memory and no scalar crosses PCIe).  Points go through the device in chunks (ZKHIP_PTAU_CONTRIB_CHUNK points, 2^20
-// otherwise) on two buffer sets, as in scale.hip: upload, checks, multiplication, synth.hip's batched normalisation and
-// download of chunk c + 1 run on the other stream while chunk c is copied out.
+// otherwise) on chunklanes.hpp's two buffer sets, which scale.hip uses too: upload, checks, multiplication, synth.hip's
+// batched normalisation and download of chunk c + 1 run on the other stream while chunk c is copied out.
 //
 // Fields: curve.hpp's 8 x 32-bit Montgomery forms (R = 2^256), the .ptau's own bytes, as ptau_prepare.hip and scale.hip.
 #include "ptengine.hpp"
+#include "chunklanes.hpp"
 #include "mulglv.hpp"
 
 namespace {
@@ -59,20 +60,7 @@ __global__ __launch_bounds__(64) void k_mul_vec(XYZZ<F> *__restrict__ out, const
 }
 
 // ---------------------------------------------------------------- host
-uint64_t chunk_points() {
-    const char *e = getenv("ZKHIP_PTAU_CONTRIB_CHUNK");
-    if (e && *e) {
-        char *end = nullptr;
-        const unsigned long long v = strtoull(e, &end, 10);
-        if (*end || v < 1 || v > (1ull << 28)) throw std::invalid_argument("ZKHIP_PTAU_CONTRIB_CHUNK: a number of points from 1 to 2^28 expected");
-        return v;
-    }
-    return DEFAULT_CHUNK;
-}
-bool plain_kernel() {
-    const char *e = getenv("ZKHIP_MULVEC_PLAIN");
-    return e && *e && strcmp(e, "0") != 0;
-}
+uint64_t chunk_points() { return env_number("ZKHIP_PTAU_CONTRIB_CHUNK", DEFAULT_CHUNK, 1, 1ull << 28, "a number of points from 1 to 2^28", ENV_LAX); }
 
 // The squarings of the base and the factor on the device.  In the contribution they are the secrets: the host copy is
 // wiped as soon as it is uploaded, the device copy before it is freed, after the lanes that read it have drained (the
@@ -98,137 +86,68 @@ struct PowerTable {
     }
 };
 
-const char *const KIND_TEXT[5] = {"", "has a coordinate that is not below q", "is not on the curve", "is not in the subgroup", "is the point at infinity"};
-
-// One of the two buffer sets.  A chunk's whole life runs on the lane's own stream: upload, checks, multiplication,
-// normalisation, download into pinned memory; the host copies it out when it next needs the lane.
-template <class F>
-struct Lane {
-    Stream st;
-    StreamUploader up;
-    DevBuf<Affine<F>> aff;
-    DevBuf<XYZZ<F>> xyzz;
-    DevBuf<F> pref;
-    DevBuf<Fr> sc;
-    DevBuf<uint32_t> err;                             // four words: k_ptau_classify's 0, 1, 3 and the subgroup kernel's 2
-    uint8_t *pin = nullptr;                           // cap points of results, then the four words
-    uint64_t cap = 0, off = 0, cnt = 0;
-    bool busy = false;
-    Lane() : up(st.s) {}
-    Lane(const Lane &) = delete;
-    Lane &operator=(const Lane &) = delete;
-    ~Lane() {
-        (void)hipStreamSynchronize(st.s);
-        if (pin) (void)hipHostFree(pin);
-    }
-    void alloc(uint64_t cap_, bool host_scalars) {
-        cap = cap_;
-        aff.alloc(cap);
-        xyzz.alloc(cap);
-        pref.alloc(cap);
-        if (host_scalars) sc.alloc(cap);
-        err.alloc(4);
-        HIP_TRY(hipHostMalloc((void **)&pin, cap * sizeof(Affine<F>) + 16, hipHostMallocDefault));
-    }
-};
-
-constexpr uint64_t LANES = 2;
 template <class F>
 uint64_t muller_bytes(uint64_t cap, bool host_scalars) {
-    return LANES * (cap * (sizeof(Affine<F>) + sizeof(XYZZ<F>) + sizeof(F) + (host_scalars ? sizeof(Fr) : 0)) + 4096) + TAB_WORDS * sizeof(Fr) + 4096;
+    return ChunkLanes<F>::bytes(cap, host_scalars) + TAB_WORDS * sizeof(Fr) + 4096;
 }
 
 template <class F>
 struct Muller {
-    PowerTable tab;                                   // before the lanes: wiped after they have drained
-    Lane<F> lane[LANES];
-    uint64_t cap;
-    bool plain, plain_sub, host_scalars;
+    PowerTable tab;                                   // before the lanes (chunklanes.hpp): wiped after they have drained
+    ChunkLanes<F> lanes;                              // four words of checks: ptengine.hpp's pass
+    bool plain, plain_sub;
     Fq e;
     PsiConsts psi;
-    Muller(uint64_t cap_, bool host_scalars_)
-        : cap(cap_ ? cap_ : 1), plain(plain_kernel()), plain_sub(plain_subgroup()), host_scalars(host_scalars_), e(endo_const<F>()),
-          psi(sizeof(F) == sizeof(Fq2) ? psi_consts() : PsiConsts{}) {      // the subgroup test's constants: G2 only
-        for (auto &l : lane) l.alloc(cap, host_scalars);
-    }
+    Muller(uint64_t cap, bool host_scalars)
+        : lanes(cap, host_scalars, 4), plain(env_switch("ZKHIP_MULVEC_PLAIN")), plain_sub(plain_subgroup()), e(endo_const<F>()),
+          psi(sizeof(F) == sizeof(Fq2) ? psi_consts() : PsiConsts{}) {}     // the subgroup test's constants: G2 only
     // the checks of the lane's chunk, enqueued; inf_bad: infinity is no legal point (a .ptau's sections)
-    void enqueue_checks(Lane<F> &l, bool inf_bad) {
-        hipStream_t s = l.st.s;
-        HIP_TRY(hipMemsetAsync(l.err.p, 0xFF, 16, s));
-        ZK_LAUNCH(k_ptau_classify<F>, dim3(nblocks(l.cnt, 256)), dim3(256), 0, s, l.err.p, l.aff.p, l.cnt, curve_b<F>(), inf_bad ? 1u : 0u);
-        ZK_LAUNCH_OK("point check");
-        if constexpr (sizeof(F) == sizeof(Fq2)) launch_subgroup(nullptr, l.err.p + 2, l.aff.p, l.cnt, psi, plain_sub, s);
-        HIP_TRY(hipMemcpyAsync(l.pin + cap * sizeof(Affine<F>), l.err.p, 16, hipMemcpyDeviceToHost, s));
-    }
-    // waits for the lane; a point that failed a check is an error naming `what`, the lowest index and what is wrong with it
-    void finish(Lane<F> &l, const char *what) {
-        l.busy = false;
-        HIP_TRY(hipStreamSynchronize(l.st.s));
-        uint32_t h[4], kind = 0, idx = NONE;
-        memcpy(h, l.pin + cap * sizeof(Affine<F>), 16);
-        for (uint32_t k = 0; k < 4; k++)              // of two kinds at one index the first: a point off the curve has no
-            if (h[k] < idx) {                         // meaningful subgroup verdict
-                idx = h[k];
-                kind = k + 1;
-            }
-        if (kind) throw std::invalid_argument(std::string(what) + ": point " + std::to_string(l.off + idx) + " " + KIND_TEXT[kind]);
-    }
-    void collect(Lane<F> &l, uint8_t *out, const char *what) {
-        if (!l.busy) return;
-        finish(l, what);
-        memcpy(out + l.off * sizeof(Affine<F>), l.pin, l.cnt * sizeof(Affine<F>));
+    void enqueue_checks(Lane<F> &l, bool inf_bad) { enqueue_classify<F>(l.words(), l.err.p, l.aff.p, l.cnt, inf_bad, &psi, plain_sub, l.st.s); }
+    // a point of the drained lane's chunk that failed a check is an error naming `what`, the lowest index and what is wrong with it
+    static void judge(const Lane<F> &l, const char *what) {
+        const BadPoint b = lowest_bad(l.words());
+        if (b.kind) throw std::invalid_argument(std::string(what) + ": point " + std::to_string(l.off + b.index) + " " + KIND_TEXT[b.kind]);
     }
     // out[i] = k_i in[i], i < n (host memory).  scalars given: k_i = scalars[i]; else k_i = tab's factor x base^(first_exp + i)
     void run(uint8_t *out, const uint8_t *in, uint64_t n, const uint8_t *scalars, uint64_t first_exp, bool inf_bad, const char *what) {
-        uint64_t c = 0;
-        for (uint64_t off = 0; off < n; off += cap, c++) {
-            Lane<F> &l = lane[c % LANES];
-            collect(l, out, what);                    // the chunk two back: the other lane's goes on meanwhile
-            l.off = off;
-            l.cnt = n - off < cap ? n - off : cap;
-            hipStream_t s = l.st.s;
-            l.up.copy(l.aff.p, in + off * sizeof(Affine<F>), l.cnt * sizeof(Affine<F>));
-            if (scalars) l.up.copy(l.sc.p, scalars + off * sizeof(Fr), l.cnt * sizeof(Fr));
-            enqueue_checks(l, inf_bad);               // on the chunk as uploaded: the normalisation below writes its results there
-            const dim3 grid(nblocks(l.cnt, 64)), block(64);
-            const uint64_t e0 = first_exp + off;
-            if (scalars) {
-                if (plain) ZK_LAUNCH((k_mul_vec<F, true, false>), grid, block, 0, s, l.xyzz.p, l.aff.p, l.cnt, l.sc.p, (const Fr *)nullptr, e0, e);
-                else ZK_LAUNCH((k_mul_vec<F, false, false>), grid, block, 0, s, l.xyzz.p, l.aff.p, l.cnt, l.sc.p, (const Fr *)nullptr, e0, e);
-            } else {
-                if (plain) ZK_LAUNCH((k_mul_vec<F, true, true>), grid, block, 0, s, l.xyzz.p, l.aff.p, l.cnt, (const Fr *)nullptr, tab.d.p, e0, e);
-                else ZK_LAUNCH((k_mul_vec<F, false, true>), grid, block, 0, s, l.xyzz.p, l.aff.p, l.cnt, (const Fr *)nullptr, tab.d.p, e0, e);
-            }
-            ZK_LAUNCH_OK("point by scalar");
-            normalize(l.aff.p, l.xyzz.p, l.pref.p, l.cnt, s);
-            HIP_TRY(hipMemcpyAsync(l.pin, l.aff.p, l.cnt * sizeof(Affine<F>), hipMemcpyDeviceToHost, s));
-            l.busy = true;
-        }
-        for (uint64_t j = 0; j < LANES; j++) collect(lane[(c + j) % LANES], out, what);   // oldest first: the lowest index is named
+        lanes.run(
+            out, in, n,
+            [&](Lane<F> &l) {
+                hipStream_t s = l.st.s;
+                if (scalars) l.up.copy(l.sc.p, scalars + l.off * sizeof(Fr), l.cnt * sizeof(Fr));
+                enqueue_checks(l, inf_bad);
+                const dim3 grid(nblocks(l.cnt, 64)), block(64);
+                const uint64_t e0 = first_exp + l.off;
+                if (scalars) {
+                    if (plain) ZK_LAUNCH((k_mul_vec<F, true, false>), grid, block, 0, s, l.xyzz.p, l.aff.p, l.cnt, l.sc.p, (const Fr *)nullptr, e0, e);
+                    else ZK_LAUNCH((k_mul_vec<F, false, false>), grid, block, 0, s, l.xyzz.p, l.aff.p, l.cnt, l.sc.p, (const Fr *)nullptr, e0, e);
+                } else {
+                    if (plain) ZK_LAUNCH((k_mul_vec<F, true, true>), grid, block, 0, s, l.xyzz.p, l.aff.p, l.cnt, (const Fr *)nullptr, tab.d.p, e0, e);
+                    else ZK_LAUNCH((k_mul_vec<F, false, true>), grid, block, 0, s, l.xyzz.p, l.aff.p, l.cnt, (const Fr *)nullptr, tab.d.p, e0, e);
+                }
+                ZK_LAUNCH_OK("point by scalar");
+            },
+            [&](const Lane<F> &l) { judge(l, what); });
     }
     // the checks alone, of a few points (section 6)
     void check(const uint8_t *in, uint64_t n, bool inf_bad, const char *what) {
-        Lane<F> &l = lane[0];
+        Lane<F> &l = lanes.lane[0];
         l.off = 0;
         l.cnt = n;
         l.up.copy(l.aff.p, in, n * sizeof(Affine<F>));
         enqueue_checks(l, inf_bad);
-        finish(l, what);
+        HIP_TRY(hipStreamSynchronize(l.st.s));
+        judge(l, what);
     }
 };
 
 // ---------------------------------------------------------------- the operators
-Fr checked_scalar(const uint8_t s32[32], const std::string &what) {
-    if (!below(s32, FrParams::P)) throw std::invalid_argument(what + " is not below r");
-    return fr_from_std(s32);
-}
-
 template <class F>
 void mul_vec(uint8_t *out, const uint8_t *points, const uint8_t *scalars, uint64_t n, int32_t device, const char *who) {
     if (!n) return;
     if (!out || !points || !scalars) throw std::invalid_argument("null argument");
-    for (uint64_t i = 0; i < n; i++)
-        if (!below(scalars + 32 * i, FrParams::P)) throw std::invalid_argument(std::string(who) + ": scalar " + std::to_string(i) + " is not below r");
+    const uint64_t bad = first_not_below_r(scalars, n);
+    if (bad < n) throw std::invalid_argument(std::string(who) + ": scalar " + std::to_string(bad) + " is not below r");
     const uint64_t chunk = chunk_points(), cap = n < chunk ? n : chunk;
     DeviceGuard g(resolve_device(device));
     need_hbm(who, muller_bytes<F>(cap, true));
@@ -247,7 +166,7 @@ void power_scale(uint8_t *out, const uint8_t *points, uint64_t n, const uint8_t 
     DeviceGuard g(resolve_device(device));
     need_hbm(who, muller_bytes<F>(cap, false));
     Muller<F> m(cap, false);
-    m.tab.build(base, factor, m.lane[0].st.s);
+    m.tab.build(base, factor, m.lanes.lane[0].st.s);
     m.run(out, points, n, nullptr, first_exp, false, who);
 }
 
@@ -314,7 +233,7 @@ void ptau_contribute(const zk_ptau_file_view *v, const uint8_t *tau32, const uin
     const uint8_t *const *in = reinterpret_cast<const uint8_t *const *>(v->sec);
     {
         Muller<Fq> m(pl.cap1, false);
-        hipStream_t s = m.lane[0].st.s;
+        hipStream_t s = m.lanes.lane[0].st.s;
         m.tab.build(sec.tau, sec.one, s);
         m.run(out->tau_g1, in[2], pl.points[2], nullptr, 0, true, "ptau section 2");
         m.tab.build(sec.tau, sec.alpha, s);           // run() has drained both lanes
@@ -324,7 +243,7 @@ void ptau_contribute(const zk_ptau_file_view *v, const uint8_t *tau32, const uin
     }
     {
         Muller<Fq2> m(pl.cap2, false);
-        m.tab.build(sec.tau, sec.one, m.lane[0].st.s);
+        m.tab.build(sec.tau, sec.one, m.lanes.lane[0].st.s);
         m.run(out->tau_g2, in[3], pl.points[3], nullptr, 0, true, "ptau section 3");
         m.check(in[6], 1, true, "ptau section 6");
     }

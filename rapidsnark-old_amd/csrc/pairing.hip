@@ -155,16 +155,7 @@ __global__ __launch_bounds__(64) void k_verify_final(uint8_t *verdict, const Fq1
 }   // namespace
 
 // ---------------------------------------------------------------- host
-uint64_t zkp::chunk_jobs() {
-    const char *e = getenv("ZKHIP_VERIFY_CHUNK");
-    if (e && *e) {
-        char *end = nullptr;
-        const unsigned long long v = strtoull(e, &end, 10);
-        if (*end || v < 1 || v > (1ull << 24)) throw std::invalid_argument("ZKHIP_VERIFY_CHUNK: a number of proofs from 1 to 2^24 expected");
-        return v;
-    }
-    return DEFAULT_CHUNK;
-}
+uint64_t zkp::chunk_jobs() { return env_number("ZKHIP_VERIFY_CHUNK", DEFAULT_CHUNK, 1, 1ull << 24, "a number of proofs from 1 to 2^24", ENV_LAX); }
 
 uint64_t zkp::verify_coop_max() { return coop_threshold("ZKHIP_VERIFY_COOP_MAX", "proofs", DEFAULT_VERIFY_COOP_MAX); }
 

@@ -41,16 +41,14 @@
 //
 // Fields: curve.hpp's 8 x 32-bit Montgomery forms (R = 2^256), the .ptau's own bytes, as ptau_prepare.hip and scale.hip.
 //
-// The subgroup kernel, the point pass, the powers of s and the chunked multiplication (DevMsm, Engine) are in ptengine.hpp:
-// zkey_verify.hip runs the same code over a key's sections.
+// The subgroup kernel, the point pass, the powers of s, the root of unity and the chunked multiplication (DevMsm, Engine,
+// EnginePair, power_sum) are in ptengine.hpp: zkey_verify.hip runs the same code over a key's sections.
 #include "ptengine.hpp"
 
 namespace {
 
 constexpr uint64_t DEFAULT_CHUNK = 1ull << 22;        // points per chunk: 512 MiB of G2 input
 constexpr uint32_t MAX_LOG_N = 28;
-// w_(2^28), standard form (ntt.hip)
-const uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
 
 // a^(r-2); the exponent is shifted, not indexed
 __device__ __forceinline__ Fr fr_inv_dev(const Fr &a) {
@@ -97,24 +95,7 @@ __global__ __launch_bounds__(256) void k_power_dft(Fr *out, const Fr *__restrict
     }
 }
 
-Fr root_of_unity(uint32_t log_n) {                    // the 2^log_n-th root zk_fr_ntt uses
-    Fr w;
-    for (int i = 0; i < 8; i++) w.v[i] = ROOT_2_28_STD[i];
-    w = Fr::to_mont(w);
-    for (uint32_t i = log_n; i < MAX_LOG_N; i++) w = Fr::sqr(w);
-    return w;
-}
-
-uint64_t chunk_points() {
-    const char *e = getenv("ZKHIP_PTAU_CHUNK");
-    if (e && *e) {
-        char *end = nullptr;
-        const unsigned long long v = strtoull(e, &end, 10);
-        if (*end || v < 1 || v > (1ull << 28)) throw std::invalid_argument("ZKHIP_PTAU_CHUNK: a number of points from 1 to 2^28 expected");
-        return v;
-    }
-    return DEFAULT_CHUNK;
-}
+uint64_t chunk_points() { return env_number("ZKHIP_PTAU_CHUNK", DEFAULT_CHUNK, 1, 1ull << 28, "a number of points from 1 to 2^28", ENV_LAX); }
 
 // the scalars c_j of one transform size
 struct DftScalars {
@@ -164,15 +145,10 @@ void g2_in_subgroup(uint8_t *out, const uint8_t *points, uint64_t n, int32_t dev
     }
 }
 
-Fr checked_scalar(const uint8_t s32[32], const char *who) {
-    if (!below(s32, FrParams::P)) throw std::invalid_argument(std::string(who) + ": the scalar is not below r");
-    return fr_from_std(s32);
-}
-
 template <class F>
 void power_msm(uint8_t *out, const uint8_t *points, uint64_t n, const uint8_t s32[32], uint64_t first_exp, int32_t device, const char *who) {
     if (!out || !s32 || (n && !points)) throw std::invalid_argument("null argument");
-    const Fr s = checked_scalar(s32, who);
+    const Fr s = checked_scalar(s32, std::string(who) + ": the scalar");
     if (first_exp + n < first_exp) throw std::invalid_argument(std::string(who) + ": first_exp + n exceeds 2^64");
     memset(out, 0, sizeof(Affine<F>));
     if (!n) return;
@@ -184,22 +160,19 @@ void power_msm(uint8_t *out, const uint8_t *points, uint64_t n, const uint8_t s3
     stab.build(s, st.s);
     Engine<F> e(st.s, cap);
     Pt<F> acc;
-    for (uint64_t off = 0; off < n; off += cap) {
-        const uint64_t cnt = n - off < cap ? n - off : cap;
+    power_sum(e, acc, n, stab, first_exp, [&](uint64_t off, uint64_t cnt) {
         e.load(points + off * sizeof(Affine<F>), cnt);
         const uint32_t bad = e.first_off_curve(cnt);
         if (bad != NONE) throw std::invalid_argument(std::string(who) + ": point " + std::to_string(off + bad) + " is not on the curve");
-        ZK_LAUNCH(k_fr_powers, dim3(nblocks(cnt, 256)), dim3(256), 0, st.s, e.sc.p, stab.d.p, first_exp + off, cnt);
-        ZK_LAUNCH_OK("powers");
-        e.accumulate(acc, cnt);
-    }
+        return true;
+    });
     memcpy(out, acc.b, sizeof acc.b);
 }
 
 void fr_power_dft(uint8_t *out, const uint8_t s32[32], uint32_t log_n, int32_t device) {
     if (!out || !s32) throw std::invalid_argument("null argument");
     if (log_n > MAX_LOG_N) throw std::invalid_argument("zk_fr_power_dft: log_n " + std::to_string(log_n) + " exceeds 28");
-    const DftScalars ds(checked_scalar(s32, "zk_fr_power_dft"), log_n);
+    const DftScalars ds(checked_scalar(s32, "zk_fr_power_dft: the scalar"), log_n);
     const uint64_t n = 1ull << log_n, chunk = chunk_points(), cap = n < chunk ? n : chunk;
     DeviceGuard g(resolve_device(device));
     need_hbm("zk_fr_power_dft", cap * sizeof(Fr) + 65536);
@@ -267,76 +240,46 @@ void check_view(const zk_ptau_file_view *v, FilePlan &pl) {
     }
     const uint64_t chunk = chunk_points(), most = pl.prepared ? 2 * n : n;     // the largest range or level
     pl.cap = most < chunk ? most : chunk;
-    pl.device_bytes = Engine<Fq>::bytes(pl.cap) + Engine<Fq2>::bytes(pl.cap) + 2 * POW_BITS * sizeof(Fr) + 65536;
+    pl.device_bytes = EnginePair::bytes(pl.cap) + 2 * POW_BITS * sizeof(Fr) + 65536;
 }
 
-struct Checker {
+struct Checker : EnginePair {
     const zk_ptau_file_view *v;
     const FilePlan &pl;
     zk_ptau_report *rep;
     hipStream_t st;
     Fr s;
     PowTable stab, wtab;
-    PsiConsts psi;
-    bool plain;
-    Engine<Fq> e1;
-    Engine<Fq2> e2;
     Checker(const zk_ptau_file_view *v_, const FilePlan &pl_, zk_ptau_report *rep_, const Fr &s_, hipStream_t st_)
-        : v(v_), pl(pl_), rep(rep_), st(st_), s(s_), psi(psi_consts()), plain(plain_subgroup()), e1(st_, pl_.cap), e2(st_, pl_.cap) {
+        : EnginePair(st_, pl_.cap), v(v_), pl(pl_), rep(rep_), st(st_), s(s_) {
         stab.build(s, st);
         wtab.build(root_of_unity(MAX_LOG_N), st);
-    }
-    template <class F>
-    Engine<F> &engine() {
-        if constexpr (sizeof(F) == sizeof(Fq)) return e1;
-        else return e2;
     }
 
     // Loads points [first, first + cnt) of section `sec` and checks them; false: the report names a malformed point
     template <class F>
     bool load_checked(int sec, uint64_t first, uint64_t cnt) {
-        Engine<F> &e = engine<F>();
-        e.load(static_cast<const uint8_t *>(v->sec[sec]) + first * sizeof(Affine<F>), cnt);
-        HIP_TRY(hipMemsetAsync(e.err.p, 0xFF, 16, st));
-        ZK_LAUNCH(k_ptau_classify<F>, dim3(nblocks(cnt, 256)), dim3(256), 0, st, e.err.p, e.pts.p, cnt, curve_b<F>(), sec < 12 ? 1u : 0u);
-        ZK_LAUNCH_OK("ptau point check");
-        if constexpr (sizeof(F) == sizeof(Fq2)) {
-            if (sec == 3 || sec == 6 || sec == 13) launch_subgroup(nullptr, e.err.p + 2, e.pts.p, cnt, psi, plain, st);
-        }
-        uint32_t h[4];
-        HIP_TRY(hipMemcpyAsync(h, e.err.p, 16, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        uint32_t kind = 0, idx = NONE;
-        for (uint32_t k = 0; k < 4; k++)              // the lowest index; of two kinds at one index the first (a point off the
-            if (h[k] < idx) {                         // curve has no meaningful subgroup verdict)
-                idx = h[k];
-                kind = k + 1;
-            }
-        if (!kind) return true;
+        engine<F>().load(static_cast<const uint8_t *>(v->sec[sec]) + first * sizeof(Affine<F>), cnt);
+        const BadPoint bad = classify<F>(cnt, sec < 12, sec == 3 || sec == 6 || sec == 13);
+        if (!bad.kind) return true;
         rep->verdict = 2;
         rep->bad_section = (uint32_t)sec;
-        rep->bad_kind = kind;
-        rep->bad_index = first + idx;
+        rep->bad_kind = bad.kind;
+        rep->bad_index = first + bad.index;
         return false;
     }
 
     // prefix[p] = sum_(i < min(2^p, m)) s^i P_i of the m points of section `sec`, p <= top; false: malformed
     template <class F>
     bool power_row(int sec, std::vector<Pt<F>> &prefix) {
-        Engine<F> &e = engine<F>();
         const uint64_t m = pl.points[sec];
         const uint32_t top = pl.top[sec];
         prefix.assign(top + 1, Pt<F>());
         Pt<F> acc;
         for (uint32_t p = 0; p <= top; p++) {
             const uint64_t lo = p ? 1ull << (p - 1) : 0, full = 1ull << p, hi = full < m ? full : m;
-            for (uint64_t off = lo; off < hi; off += e.cap) {
-                const uint64_t cnt = hi - off < e.cap ? hi - off : e.cap;
-                if (!load_checked<F>(sec, off, cnt)) return false;
-                ZK_LAUNCH(k_fr_powers, dim3(nblocks(cnt, 256)), dim3(256), 0, st, e.sc.p, stab.d.p, off, cnt);
-                ZK_LAUNCH_OK("powers");
-                e.accumulate(acc, cnt);
-            }
+            if (lo < hi && !power_sum(engine<F>(), acc, hi - lo, stab, lo, [&](uint64_t off, uint64_t cnt) { return load_checked<F>(sec, lo + off, cnt); }))
+                return false;
             prefix[p] = acc;
         }
         return true;
@@ -379,9 +322,7 @@ void ptau_check(const zk_ptau_file_view *v, const uint8_t *s32_in, int32_t devic
     uint8_t s32[32];
     if (s32_in) {
         memcpy(s32, s32_in, 32);
-        bool small = s32[0] < 2;
-        for (int i = 1; i < 32 && small; i++) small = s32[i] == 0;
-        if (small || !below(s32, FrParams::P)) throw std::invalid_argument("zk_ptau_check: the check scalar must be at least 2 and below r");
+        if (is_0_or_1(s32) || !below(s32, FrParams::P)) throw std::invalid_argument("zk_ptau_check: the check scalar must be at least 2 and below r");
     } else {
         draw_scalar(s32, "zk_ptau_check");                             // after the file is mapped: its maker did not know s
     }

@@ -117,21 +117,14 @@ __global__ __launch_bounds__(64) void k_ptau_scale(XYZZ<F> *y, const Affine<F> *
 }
 
 // ---------------------------------------------------------------- host
-// w_(2^28), standard form (ntt.hip)
-const uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
-
 // The scalars of one call: w_N^(-k) for k < N / 2 (N = 2^top, the largest level) and 2^(-p) for every level
 struct Scalars {
     DevBuf<Fr> tab, ninv;
     uint32_t top = 0;
     void build(uint32_t top_, hipStream_t s) {
         top = top_;
-        Fr w;
-        for (int i = 0; i < 8; i++) w.v[i] = ROOT_2_28_STD[i];
-        w = Fr::to_mont(w);
-        for (uint32_t i = top; i < 28; i++) w = Fr::sqr(w);
         RootPowers pw;
-        pw.w[0] = Fr::inv(w);
+        pw.w[0] = Fr::inv(root_of_unity(top));
         for (uint32_t i = 1; i < MAX_LOG_N; i++) pw.w[i] = Fr::sqr(pw.w[i - 1]);
         const uint64_t count = top ? 1ull << (top - 1) : 1;
         tab.alloc(count);

@@ -8,8 +8,6 @@
 
 namespace zk {
 
-constexpr uint32_t NO_BAD_POINT = 0xFFFFFFFFu;
-
 __device__ __forceinline__ bool below_q(const Fq &a) {
     uint32_t bw = 0;
 #pragma unroll

@@ -1,8 +1,10 @@
 // What the checks of files of points share (ptau_check.hip: is a .ptau sound; zkey_verify.hip: is a .zkey the key of its
 // circuit over a .ptau): the G2 subgroup test, the pass over a row of points that says what is wrong with the first bad
 // one, scalars made on the device (the powers of one s), points as the files' bytes on the host, and the chunked
-// multi-scalar multiplication on device-resident inputs (DevMsm, Engine) with its admission estimate.  One copy for both
-// units; ptau_check.hip's header comment describes the subgroup test and the multiplication.
+// multi-scalar multiplication on device-resident inputs (DevMsm, Engine, EnginePair, power_sum) with its admission
+// estimate.  One copy for both units; ptau_check.hip's header comment describes the subgroup test and the multiplication.
+// mulvec.hip and kzg.hip run the same pass over their points (enqueue_classify, classified); they and frscan.hip take
+// the host's scalar helpers (first_not_below_r, checked_scalar).
 #pragma once
 #include <errno.h>
 #include <sys/random.h>
@@ -139,10 +141,19 @@ inline Fr fr_pow(Fr base, uint64_t e) {
     return acc;
 }
 
-inline bool plain_subgroup() {
-    const char *e = getenv("ZKHIP_SUBGROUP_PLAIN");
-    return e && *e && strcmp(e, "0") != 0;
+// the lowest index of n scalars (32 bytes LE) that is not below r, n when there is none
+inline uint64_t first_not_below_r(const uint8_t *sc, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++)
+        if (!below(sc + i * 32, FrParams::P)) return i;
+    return n;
 }
+// a caller's scalar, Montgomery; "<what> is not below r" otherwise
+inline Fr checked_scalar(const uint8_t s32[32], const std::string &what) {
+    if (!below(s32, FrParams::P)) throw std::invalid_argument(what + " is not below r");
+    return fr_from_std(s32);
+}
+
+inline bool plain_subgroup() { return env_switch("ZKHIP_SUBGROUP_PLAIN"); }
 
 inline PsiConsts psi_consts() {
     PairConsts pc;
@@ -294,6 +305,11 @@ struct Engine {
         HIP_TRY(hipStreamSynchronize(s));
         return bad;
     }
+    // sc[i] = base^(e0 + i), i < cnt; tab: the squarings of base
+    void powers(const PowTable &tab, uint64_t e0, uint64_t cnt) {
+        ZK_LAUNCH(k_fr_powers, dim3(nblocks(cnt, 256)), dim3(256), 0, s, sc.p, tab.d.p, e0, cnt);
+        ZK_LAUNCH_OK("powers");
+    }
     // acc += sum sc[i] pts[i] over the loaded chunk
     void accumulate(Pt<F> &acc, uint64_t cnt) {
         Pt<F> part;
@@ -302,12 +318,71 @@ struct Engine {
     }
 };
 
+// acc += sum_(i < n) base^(e0 + i) P_i, e.cap points at a time.  fetch(off, cnt) brings P_off .. P_(off + cnt - 1) into
+// e.pts and checks them; false: it has said what is wrong, and the sum is given up
+template <class F, class Fetch>
+bool power_sum(Engine<F> &e, Pt<F> &acc, uint64_t n, const PowTable &tab, uint64_t e0, Fetch fetch) {
+    for (uint64_t off = 0; off < n; off += e.cap) {
+        const uint64_t cnt = n - off < e.cap ? n - off : e.cap;
+        if (!fetch(off, cnt)) return false;
+        e.powers(tab, e0 + off, cnt);
+        e.accumulate(acc, cnt);
+    }
+    return true;
+}
+
 inline void launch_subgroup(uint8_t *d_out, uint32_t *d_err, const G2Affine *d_pts, uint64_t n, const PsiConsts &k, bool plain, hipStream_t s) {
     if (!n) return;
     if (plain) ZK_LAUNCH(k_g2_subgroup<true>, dim3(nblocks(n, 64)), dim3(64), 0, s, d_out, d_err, d_pts, n, k);
     else ZK_LAUNCH(k_g2_subgroup<false>, dim3(nblocks(n, 64)), dim3(64), 0, s, d_out, d_err, d_pts, n, k);
     ZK_LAUNCH_OK("g2 subgroup test");
 }
+
+// ---------------------------------------------------------------- host: the pass over a chunk of a file's points
+// Enqueued on s: d_err's four words <- what k_ptau_classify finds in d_pts[0, n) (n >= 1; inf_bad: infinity is no legal
+// point) and, for points of G2 when psi is given, the subgroup kernel's word; then the words go to h (host; pinned memory
+// when the caller goes on without waiting).  The kernels record with atomicMin: the words do not depend on scheduling.
+template <class F>
+inline void enqueue_classify(uint32_t *h, uint32_t *d_err, const Affine<F> *d_pts, uint64_t n, bool inf_bad, const PsiConsts *psi, bool plain, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(d_err, 0xFF, 16, s));
+    ZK_LAUNCH(k_ptau_classify<F>, dim3(nblocks(n, 256)), dim3(256), 0, s, d_err, d_pts, n, curve_b<F>(), inf_bad ? 1u : 0u);
+    ZK_LAUNCH_OK("point check");
+    if constexpr (sizeof(F) == sizeof(Fq2)) {
+        if (psi) launch_subgroup(nullptr, d_err + 2, d_pts, n, *psi, plain, s);
+    }
+    HIP_TRY(hipMemcpyAsync(h, d_err, 16, hipMemcpyDeviceToHost, s));
+}
+// waits for s; the first bad point of the words enqueue_classify sent to h (kind 0: none)
+inline BadPoint classified(const uint32_t *h, hipStream_t s) {
+    HIP_TRY(hipStreamSynchronize(s));
+    uint32_t w[4];
+    memcpy(w, h, sizeof w);
+    return lowest_bad(w);
+}
+
+// The two groups' engines on one stream and what the pass over their chunks needs: what zk_ptau_check and zk_zkey_verify
+// are built on
+struct EnginePair {
+    PsiConsts psi;
+    bool plain;
+    Engine<Fq> e1;
+    Engine<Fq2> e2;
+    EnginePair(hipStream_t s, uint64_t cap) : psi(psi_consts()), plain(plain_subgroup()), e1(s, cap), e2(s, cap) {}
+    static uint64_t bytes(uint64_t cap) { return Engine<Fq>::bytes(cap) + Engine<Fq2>::bytes(cap); }
+    template <class F>
+    Engine<F> &engine() {
+        if constexpr (sizeof(F) == sizeof(Fq)) return e1;
+        else return e2;
+    }
+    // the first bad point of the cnt points engine<F>() holds; subgroup: the points must be in G2's order-r subgroup
+    template <class F>
+    BadPoint classify(uint64_t cnt, bool inf_bad, bool subgroup) {
+        Engine<F> &e = engine<F>();
+        uint32_t h[4];
+        enqueue_classify<F>(h, e.err.p, e.pts.p, cnt, inf_bad, subgroup ? &psi : nullptr, plain, e.s);
+        return classified(h, e.s);
+    }
+};
 
 inline void generators(Pt<Fq> &g1, Pt<Fq2> &g2) {
     // (1, 2), and the generator of G2 of EIP-197, standard form
@@ -334,9 +409,7 @@ inline void draw_scalar(uint8_t s32[32], const char *who) {
             }
             got += (size_t)k;
         }
-        bool small = s32[0] < 2;
-        for (int i = 1; i < 32 && small; i++) small = s32[i] == 0;
-        if (!small && below(s32, FrParams::P)) return;
+        if (!is_0_or_1(s32) && below(s32, FrParams::P)) return;
     }
 }
 

@@ -30,8 +30,7 @@
 // The yardstick.  k_scale_g1_plain is devmem.hpp's scalar_mul_affine with the same shared scalar, one lane per point:
 // what the project had before this file.  ZKHIP_SCALE_PLAIN=1 runs it in place of k_scale_g1: a second route to the
 // same bytes for the tests, and the denominator of tools/contribute_timing.py.
-#include "hiputil.hpp"
-#include "devmem.hpp"
+#include "chunklanes.hpp"
 #include "ptcheck.hpp"
 
 namespace {
@@ -257,24 +256,9 @@ __global__ __launch_bounds__(64) void k_scale_g1_plain(G1XYZZ *__restrict__ out,
 }
 
 // ---------------------------------------------------------------- host: rows of points through the device, in chunks
-uint64_t chunk_points() {
-    const char *e = getenv("ZKHIP_SCALE_CHUNK");
-    if (e && *e) {
-        char *end = nullptr;
-        const unsigned long long v = strtoull(e, &end, 10);
-        if (*end || v < 1 || v > (1ull << 28)) throw std::invalid_argument("ZKHIP_SCALE_CHUNK: a number of points from 1 to 2^28 expected");
-        return v;
-    }
-    return DEFAULT_CHUNK;
-}
-bool plain_kernel() {
-    const char *e = getenv("ZKHIP_SCALE_PLAIN");
-    return e && *e && strcmp(e, "0") != 0;
-}
+uint64_t chunk_points() { return env_number("ZKHIP_SCALE_CHUNK", DEFAULT_CHUNK, 1, 1ull << 28, "a number of points from 1 to 2^28", ENV_LAX); }
 
-constexpr uint64_t LANES = 2;
-uint64_t lane_bytes(uint64_t cap) { return cap * (sizeof(G1Affine) + sizeof(G1XYZZ) + sizeof(Fq)) + 4096; }
-uint64_t scaler_bytes(uint64_t cap) { return LANES * lane_bytes(cap) + 4096; }
+uint64_t scaler_bytes(uint64_t cap) { return ChunkLanes<Fq>::bytes(cap, false) + 4096; }
 
 // The schedule on the device: zeroed before it is freed, after the lanes that read it have drained (declared before them)
 struct SecretSchedule {
@@ -284,76 +268,31 @@ struct SecretSchedule {
     }
 };
 
-// One of the two buffer sets.  A chunk's whole life runs on the lane's own stream: upload, check, multiplication,
-// normalisation, download into pinned memory; the host copies it out when it next needs the lane.
-struct Lane {
-    Stream st;
-    StreamUploader up;
-    DevBuf<G1Affine> aff;
-    DevBuf<G1XYZZ> xyzz;
-    DevBuf<Fq> pref;
-    DevBuf<uint32_t> err;
-    uint8_t *pin = nullptr;                           // cap x 64 bytes of results, then the check's word
-    uint64_t cap = 0, off = 0, cnt = 0;
-    bool busy = false;
-    Lane() : up(st.s) {}
-    Lane(const Lane &) = delete;
-    Lane &operator=(const Lane &) = delete;
-    ~Lane() {
-        (void)hipStreamSynchronize(st.s);
-        if (pin) (void)hipHostFree(pin);
-    }
-    void alloc(uint64_t cap_) {
-        cap = cap_;
-        aff.alloc(cap);
-        xyzz.alloc(cap);
-        pref.alloc(cap);
-        err.alloc(1);
-        HIP_TRY(hipHostMalloc((void **)&pin, cap * sizeof(G1Affine) + 16, hipHostMallocDefault));
-    }
-};
-
 struct Scaler {
-    SecretSchedule sched;
-    Lane lane[LANES];
-    uint64_t cap;
+    SecretSchedule sched;                             // before the lanes (chunklanes.hpp): wiped after they have drained
+    ChunkLanes<Fq> lanes;                             // one word of checks: ptcheck.hpp's
     bool plain;
     Fq beta;
-    Scaler(const ScalePlan &pl, uint64_t cap_) : cap(cap_ ? cap_ : 1), plain(plain_kernel()), beta(fq_std(BETA_STD)) {
+    Scaler(const ScalePlan &pl, uint64_t cap) : lanes(cap, false, 1), plain(env_switch("ZKHIP_SCALE_PLAIN")), beta(fq_std(BETA_STD)) {
         sched.d.alloc(SCHED_WORDS);
         HIP_TRY(hipMemcpy(sched.d.p, pl.words, sizeof pl.words, hipMemcpyHostToDevice));
-        for (auto &l : lane) l.alloc(cap);
     }
-    // the results of the lane's chunk -> out; a point that failed its check is an error naming `what` and the index
-    void collect(Lane &l, uint8_t *out, const char *what) {
-        if (!l.busy) return;
-        l.busy = false;
-        HIP_TRY(hipStreamSynchronize(l.st.s));
-        uint32_t bad;
-        memcpy(&bad, l.pin + cap * sizeof(G1Affine), 4);
-        if (bad != NO_BAD_POINT) throw std::invalid_argument(std::string(what) + ": point " + std::to_string(l.off + bad) + " is not on the curve");
-        memcpy(out + l.off * sizeof(G1Affine), l.pin, l.cnt * sizeof(G1Affine));
-    }
-    // out[i] = k in[i], i < n (host memory, 64 bytes a point)
+    // out[i] = k in[i], i < n (host memory, 64 bytes a point); a point that failed its check is an error naming `what` and the index
     void run(uint8_t *out, const uint8_t *in, uint64_t n, const char *what) {
-        uint64_t c = 0;
-        for (uint64_t off = 0; off < n; off += cap, c++) {
-            Lane &l = lane[c % LANES];
-            collect(l, out, what);                    // the chunk two back: the other lane's goes on meanwhile
-            l.off = off;
-            l.cnt = n - off < cap ? n - off : cap;
-            hipStream_t s = l.st.s;
-            l.up.copy(l.aff.p, in + off * sizeof(G1Affine), l.cnt * sizeof(G1Affine));
-            launch_point_check<Fq>(l.err.p, l.aff.p, l.cnt, s);
-            if (plain) ZK_LAUNCH(k_scale_g1_plain, dim3(nblocks(l.cnt, 64)), dim3(64), 0, s, l.xyzz.p, l.aff.p, l.cnt, sched.d.p);
-            else ZK_LAUNCH(k_scale_g1, dim3(nblocks(l.cnt, 64)), dim3(64), 0, s, l.xyzz.p, l.aff.p, l.cnt, sched.d.p, beta);
-            ZK_LAUNCH_OK("g1 scale");
-            normalize(l.aff.p, l.xyzz.p, l.pref.p, l.cnt, s);
-            HIP_TRY(hipMemcpyAsync(l.pin, l.aff.p, l.cnt * sizeof(G1Affine), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(l.pin + cap * sizeof(G1Affine), l.err.p, 4, hipMemcpyDeviceToHost, s));
-            l.busy = true;
-        }
-        for (uint64_t j = 0; j < LANES; j++) collect(lane[(c + j) % LANES], out, what);   // oldest first: the lowest index is named
+        lanes.run(
+            out, in, n,
+            [&](Lane<Fq> &l) {
+                hipStream_t s = l.st.s;
+                launch_point_check<Fq>(l.err.p, l.aff.p, l.cnt, s);
+                HIP_TRY(hipMemcpyAsync(l.words(), l.err.p, 4, hipMemcpyDeviceToHost, s));
+                if (plain) ZK_LAUNCH(k_scale_g1_plain, dim3(nblocks(l.cnt, 64)), dim3(64), 0, s, l.xyzz.p, l.aff.p, l.cnt, sched.d.p);
+                else ZK_LAUNCH(k_scale_g1, dim3(nblocks(l.cnt, 64)), dim3(64), 0, s, l.xyzz.p, l.aff.p, l.cnt, sched.d.p, beta);
+                ZK_LAUNCH_OK("g1 scale");
+            },
+            [&](const Lane<Fq> &l) {
+                const uint32_t bad = *l.words();
+                if (bad != NO_BAD_POINT) throw std::invalid_argument(std::string(what) + ": point " + std::to_string(l.off + bad) + " is not on the curve");
+            });
     }
 };
 

@@ -255,13 +255,6 @@ void check_views(const zk_r1cs_view *r, const zk_ptau_view *p, Sizes &z) {
     if (z.nnz + z.nP1() >= (1ull << 32)) throw std::invalid_argument("r1cs has 2^32 terms or more: not supported");
 }
 
-void upload_level(DevBuf<uint8_t> &d, const void *section, uint32_t p, uint64_t pt_bytes, hipStream_t s) {
-    const uint64_t count = 1ull << p;
-    d.alloc(count * pt_bytes);
-    StreamUploader up(s);
-    up.copy(d.p, (const uint8_t *)section + (count - 1) * pt_bytes, count * pt_bytes);
-}
-
 // One output table: the points of every wire for the terms [t0, t1), affine in `out` (nWires points)
 template <class F>
 void run_table(Affine<F> *out, const Sizes &z, uint64_t t0, uint64_t t1, const Bases<F> &b, const DevBuf<uint32_t> &wire,

@@ -1,30 +1,17 @@
-// The host side that the batch-verification entries share and that needs no HIP: the strict reading of a number from the
-// environment (the group switches here, the cooperative thresholds in pairing_coop.hpp), the scalars (drawn, or the
+// The host side that the batch-verification entries (and kzg.hip's batch) share and that needs no HIP: the group switch
+// (hostutil.hpp's strict env_number, as the cooperative thresholds in pairing_coop.hpp), the scalars (drawn, or the
 // caller's, refused when zero), the clamp of a caller's report size, and the layout of one chunk of a key set's batch.
 // tools/verify_batch_host_test.cpp builds it for the host alone.
 #pragma once
 #include <errno.h>
-#include <stdint.h>
-#include <stdlib.h>
 #include <sys/random.h>
 
 #include <algorithm>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-namespace zk {
+#include "hostutil.hpp"
 
-// Decimal, from min to max; unset or empty: dflt.  Strict: the first character is a digit and nothing follows the number,
-// so a blank, a sign or a suffix is refused: "<name>: <what> expected".
-inline uint64_t env_number(const char *name, uint64_t dflt, uint64_t min, uint64_t max, const char *what) {
-    const char *e = getenv(name);
-    if (!e || !*e) return dflt;
-    char *end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (*end || *e < '0' || *e > '9' || v < min || v > max) throw std::invalid_argument(std::string(name) + ": " + what + " expected");
-    return v;
-}
+namespace zk {
 
 constexpr uint64_t DEFAULT_GROUP = 1024;              // profiles/verify_batch_timing.txt
 // ZKHIP_VERIFY_GROUP: the proofs of a group, read at every call

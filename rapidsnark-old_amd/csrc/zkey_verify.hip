@@ -77,16 +77,7 @@ __global__ __launch_bounds__(256) void k_zv_gather_odd(uint4 *out, const uint4 *
 }
 
 // ---------------------------------------------------------------- host: the three files against each other
-uint64_t chunk_points() {
-    const char *e = getenv("ZKHIP_ZKEY_VERIFY_CHUNK");
-    if (e && *e) {
-        char *end = nullptr;
-        const unsigned long long v = strtoull(e, &end, 10);
-        if (*end || v < 1 || v > (1ull << 28)) throw std::invalid_argument("ZKHIP_ZKEY_VERIFY_CHUNK: a number of points from 1 to 2^28 expected");
-        return v;
-    }
-    return DEFAULT_CHUNK;
-}
+uint64_t chunk_points() { return env_number("ZKHIP_ZKEY_VERIFY_CHUNK", DEFAULT_CHUNK, 1, 1ull << 28, "a number of points from 1 to 2^28", ENV_LAX); }
 
 struct Plan {
     uint32_t k = 0, m = 0, nWires = 0, nPublic = 0, shape = 0;
@@ -169,7 +160,7 @@ void make_plan(const zk_r1cs_view *r, const zk_ptau_view *p, const zk_zkey_verif
     const uint64_t match = pl.nCoefs * (44 + 36) + n * (16 + 96) + 4096;            // zk_r1cs_match_zkey: records, CSR, a | b | c
     const uint64_t vectors = 2 * nw * 32 + 6 * n * 32;                              // p_pub, p_priv; a, b, c (pub and priv)
     const uint64_t levels = n * (64 + 128 + 64 + 64) + 2 * n * 64;                  // level k of 12 .. 15, level k + 1 of 12
-    pl.device_bytes = circuit + match + vectors + levels + Engine<Fq>::bytes(pl.cap) + Engine<Fq2>::bytes(pl.cap) + POW_BITS * sizeof(Fr) + 65536;
+    pl.device_bytes = circuit + match + vectors + levels + EnginePair::bytes(pl.cap) + POW_BITS * sizeof(Fr) + 65536;
 }
 
 // ---------------------------------------------------------------- the check
@@ -178,67 +169,36 @@ struct R1csHandle {
     ~R1csHandle() { zk_r1cs_destroy(r); }
 };
 
-struct Verifier {
+struct Verifier : EnginePair {
     const Plan &pl;
     zk_zkey_verify_report &rep;
     hipStream_t st;
     PowTable stab;
-    PsiConsts psi;
-    bool plain;
-    Engine<Fq> e1;
-    Engine<Fq2> e2;
-    Verifier(const Plan &pl_, zk_zkey_verify_report &rep_, const Fr &s, hipStream_t st_)
-        : pl(pl_), rep(rep_), st(st_), psi(psi_consts()), plain(plain_subgroup()), e1(st_, pl_.cap), e2(st_, pl_.cap) {
+    Verifier(const Plan &pl_, zk_zkey_verify_report &rep_, const Fr &s, hipStream_t st_) : EnginePair(st_, pl_.cap), pl(pl_), rep(rep_), st(st_) {
         stab.build(s, st);
-    }
-    template <class F>
-    Engine<F> &engine() {
-        if constexpr (sizeof(F) == sizeof(Fq)) return e1;
-        else return e2;
     }
 
     // The pass of zk_ptau_check over the cnt points the engine holds; false: the report names a malformed point of `sec`,
     // index0 + its place
     template <class F>
-    bool classify(int sec, uint64_t index0, uint64_t cnt, bool inf_bad, bool subgroup) {
-        Engine<F> &e = engine<F>();
-        HIP_TRY(hipMemsetAsync(e.err.p, 0xFF, 16, st));
-        ZK_LAUNCH(k_ptau_classify<F>, dim3(nblocks(cnt, 256)), dim3(256), 0, st, e.err.p, e.pts.p, cnt, curve_b<F>(), inf_bad ? 1u : 0u);
-        ZK_LAUNCH_OK("zkey point check");
-        if constexpr (sizeof(F) == sizeof(Fq2)) {
-            if (subgroup) launch_subgroup(nullptr, e.err.p + 2, e.pts.p, cnt, psi, plain, st);
-        }
-        uint32_t h[4];
-        HIP_TRY(hipMemcpyAsync(h, e.err.p, 16, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        uint32_t kind = 0, idx = NONE;
-        for (uint32_t k = 0; k < 4; k++)              // the lowest index; of two kinds at one index the first
-            if (h[k] < idx) {
-                idx = h[k];
-                kind = k + 1;
-            }
-        if (!kind) return true;
+    bool checked(int sec, uint64_t index0, uint64_t cnt, bool inf_bad, bool subgroup) {
+        const BadPoint bad = classify<F>(cnt, inf_bad, subgroup);
+        if (!bad.kind) return true;
         rep.verdict = 2;
         rep.bad_section = (uint32_t)sec;
-        rep.bad_kind = kind;
-        rep.bad_index = index0 + idx;
+        rep.bad_kind = bad.kind;
+        rep.bad_index = index0 + bad.index;
         return false;
     }
 
     // sum = sum_(i < cnt) s^(e0 + i) P_i over the cnt points of key section `sec`, checked chunk by chunk; false: malformed
     template <class F>
     bool key_row(int sec, const void *points, uint64_t cnt_all, uint64_t e0, Pt<F> &sum) {
-        Engine<F> &e = engine<F>();
         sum = Pt<F>();
-        for (uint64_t off = 0; off < cnt_all; off += e.cap) {
-            const uint64_t cnt = cnt_all - off < e.cap ? cnt_all - off : e.cap;
-            e.load(static_cast<const uint8_t *>(points) + off * sizeof(Affine<F>), cnt);
-            if (!classify<F>(sec, off, cnt, false, sec == 7)) return false;
-            ZK_LAUNCH(k_fr_powers, dim3(nblocks(cnt, 256)), dim3(256), 0, st, e.sc.p, stab.d.p, e0 + off, cnt);
-            ZK_LAUNCH_OK("powers");
-            e.accumulate(sum, cnt);
-        }
-        return true;
+        return power_sum(engine<F>(), sum, cnt_all, stab, e0, [&](uint64_t off, uint64_t cnt) {
+            engine<F>().load(static_cast<const uint8_t *>(points) + off * sizeof(Affine<F>), cnt);
+            return checked<F>(sec, off, cnt, false, sec == 7);
+        });
     }
 
     // sum_(i < n) vec[i] lvl[i]: a level that is on the device by a vector that is (standard form)
@@ -257,19 +217,6 @@ struct Verifier {
     }
 };
 
-void upload_level(DevBuf<uint8_t> &d, const void *section, uint32_t p, uint64_t pt_bytes, hipStream_t s) {
-    const uint64_t count = 1ull << p;
-    d.alloc(count * pt_bytes);
-    StreamUploader up(s);
-    up.copy(d.p, static_cast<const uint8_t *>(section) + (count - 1) * pt_bytes, count * pt_bytes);
-}
-
-bool small_scalar(const uint8_t s32[32]) {            // 0 or 1
-    bool small = s32[0] < 2;
-    for (int i = 1; i < 32 && small; i++) small = s32[i] == 0;
-    return small;
-}
-
 void write_report(zk_zkey_verify_report *out, zk_zkey_verify_report &r, uint32_t size) {
     r.size = size;
     memcpy(out, &r, size);
@@ -287,7 +234,7 @@ void zkey_verify(const zk_r1cs_view *rv, const zk_ptau_view *p, const zk_zkey_ve
     uint8_t s32[32];
     if (s32_in) {
         memcpy(s32, s32_in, 32);
-        if (small_scalar(s32) || !below(s32, FrParams::P)) throw std::invalid_argument("zk_zkey_verify: the check scalar must be at least 2 and below r");
+        if (is_0_or_1(s32) || !below(s32, FrParams::P)) throw std::invalid_argument("zk_zkey_verify: the check scalar must be at least 2 and below r");
     } else {
         draw_scalar(s32, "zk_zkey_verify");            // after the files are mapped: their maker did not know s
     }
@@ -333,10 +280,10 @@ void zkey_verify(const zk_r1cs_view *rv, const zk_ptau_view *p, const zk_zkey_ve
             bool ok;
             if (sec2[i].g2) {
                 HIP_TRY(hipMemcpyAsync(v.e2.pts.p, sec2[i].b, 128, hipMemcpyHostToDevice, st));
-                ok = v.classify<Fq2>(2, i, 1, true, true);
+                ok = v.checked<Fq2>(2, i, 1, true, true);
             } else {
                 HIP_TRY(hipMemcpyAsync(v.e1.pts.p, sec2[i].b, 64, hipMemcpyHostToDevice, st));
-                ok = v.classify<Fq>(2, i, 1, true, false);
+                ok = v.checked<Fq>(2, i, 1, true, false);
             }
             if (!ok) return bad();
         }

@@ -130,6 +130,44 @@ def test_operator_errors(zk, group):
         mul_vec(pts, k[:-1])
 
 
+@pytest.mark.parametrize("group", GROUPS)
+def test_chunks_on_both_buffer_sets_name_the_lowest_bad_point(zk, group, monkeypatch):
+    """13 points in chunks of 4: four chunks, the last of one point, so both buffer sets are used again and then drained"""
+    rng = random.Random(13)
+    mul_vec, fixed, nb = ops(zk, group)
+    name = "zk_%s_mul_vec" % group
+    pts = fixed([rng.randrange(1, RM) for _ in range(13)])
+    k = [rng.randrange(RM) for _ in range(13)]
+    whole = mul_vec(pts, k)                                             # one chunk
+    monkeypatch.setenv("ZKHIP_PTAU_CONTRIB_CHUNK", "4")
+
+    def off_curve(p, at):
+        p[nb * at + nb // 2] ^= 1                                       # y changed
+
+    # chunks 1 and 2, one per buffer set and both in flight; the last chunk alone, seen only in the final drain; chunks 2
+    # and 3, both seen in the final drain, which runs oldest first
+    for flipped, named in (((6, 9), 6), ((12,), 12), ((9, 12), 9)):
+        bad = pts.copy()
+        for at in flipped:
+            off_curve(bad, at)
+        with pytest.raises(zk.ZkHipError, match=r"%s: point %d is not on the curve" % (name, named)):
+            mul_vec(bad, k)
+    assert np.array_equal(mul_vec(pts, k), whole)
+    # two kinds, one per buffer set
+    bad = pts.copy()
+    bad[nb * 6:nb * 6 + 32] = np.frombuffer(QM.to_bytes(32, "little"), np.uint8)                # a coordinate = q
+    off_curve(bad, 9)
+    with pytest.raises(zk.ZkHipError, match=r"%s: point 6 has a coordinate that is not below q" % name):
+        mul_vec(bad, k)
+    if group == "g2":
+        p = golden_json("g2_cofactor_points.json")["outside"][0]
+        bad = pts.copy()
+        bad[128 * 5:128 * 6] = np.frombuffer(bn.g2_to_bytes(((int(p["x"][0]), int(p["x"][1])), (int(p["y"][0]), int(p["y"][1])))), np.uint8)
+        off_curve(bad, 9)
+        with pytest.raises(zk.ZkHipError, match=r"zk_g2_mul_vec: point 5 is not in the subgroup"):
+            mul_vec(bad, k)
+
+
 def test_a_g2_point_outside_the_subgroup_is_refused(zk):
     """on the twist, but the endomorphism is no multiplication by a constant there"""
     d = golden_json("g2_cofactor_points.json")

@@ -101,6 +101,23 @@ def test_operator_errors(zk):
         zk.g1_scale(both, 3)
 
 
+def test_chunks_on_both_buffer_sets_name_the_lowest_bad_point(zk, monkeypatch):
+    """13 points in chunks of 4: four chunks, the last of one point, so both buffer sets are used again and then drained"""
+    rng = random.Random(13)
+    pts = zk.fixed_base_g1(G1, [rng.randrange(1, RM) for _ in range(13)])
+    whole = zk.g1_scale(pts, 3)                                     # one chunk
+    monkeypatch.setenv("ZKHIP_SCALE_CHUNK", "4")
+    # chunks 1 and 2, one per buffer set and both in flight; the last chunk alone, seen only in the final drain; chunks 2
+    # and 3, both seen in the final drain, which runs oldest first
+    for flipped, named in (((6, 9), 6), ((12,), 12), ((9, 12), 9)):
+        off = pts.copy()
+        for at in flipped:
+            off[64 * at + 32] ^= 1
+        with pytest.raises(zk.ZkHipError, match=r"zk_g1_scale: point %d is not on the curve" % named):
+            zk.g1_scale(off, 3)
+    assert np.array_equal(zk.g1_scale(pts, 3), whole)
+
+
 # ---------------------------------------------------------------- the contribution on a key whose trapdoor is known
 @pytest.fixture(scope="module")
 def trapdoor_key(zk, tmp_path_factory):

@@ -44,9 +44,10 @@ def test_ctypes_report_has_the_c_layout(tmp_path):
 
 
 def test_shared_host_code_under_the_sanitizers(tmp_path):
-    """csrc/verify_batch_host.hpp alone, in a program of its own (tools/verify_batch_host_test.cpp): the strict reading of the
-    group switches, 4096 drawn scalars (none zero, no two equal), the refusal of a zero scalar, the report's size, and
-    ChunkPlan against a restatement of the grouping rule on the key_of layouts of the device tests."""
+    """csrc/hostutil.hpp and csrc/verify_batch_host.hpp alone, in a program of its own (tools/verify_batch_host_test.cpp): the
+    strict reading of the group switches and the lax one of the chunk sizes, the on/off switch, the pick of the first bad
+    point, 4096 drawn scalars (none zero, no two equal), the refusal of a zero scalar, the report's size, and ChunkPlan
+    against a restatement of the grouping rule on the key_of layouts of the device tests."""
     exe = str(tmp_path / "verify_batch_host_test")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            "-I", os.path.join(ROOT, "rapidsnark-old_amd", "csrc"), os.path.join(ROOT, "tools", "verify_batch_host_test.cpp"), "-o", exe])

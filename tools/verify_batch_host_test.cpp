@@ -1,5 +1,6 @@
-// Host check of what the batch-verification entries share on the host (csrc/verify_batch_host.hpp): the strict reading of a
-// number from the environment, the drawn scalars, the refusal of a zero scalar, the clamp of a report's size, and
+// Host check of what the entries share on the host without HIP.  csrc/hostutil.hpp: the strict and the lax reading of a
+// number from the environment, the on/off switch, the pick of the first bad point and the 0-or-1 scalar test.
+// csrc/verify_batch_host.hpp: the drawn scalars, the refusal of a zero scalar, the clamp of a report's size, and
 // ChunkPlan against a plain restatement of the grouping rule on the key_of layouts the device tests use.
 // tests/test_verify_set_batch_host.py builds it with the address and undefined-behaviour sanitizers and runs it.
 #include <stdio.h>
@@ -69,6 +70,81 @@ static void test_env_number() {
         CHECK(strcmp(e.what(), "ZKHIP_VERIFY_GROUP: a number of proofs from 1 to 2^24 expected") == 0, "group 0: message '%s'", e.what());
     }
     unsetenv("ZKHIP_VERIFY_GROUP");
+}
+
+// ---------------------------------------------------------------- hostutil.hpp: the two readings of a number, the switch, the pick
+// What each reading took before the two became one function, worked out from that code.  Lax is the chunk_points() every
+// streaming unit carried: `if (e && *e) { v = strtoull(e, &end, 10); if (*end || v < min || v > max) throw; return v; } return
+// dflt;`, so what strtoull skips (blanks, a sign) passes and "-1" wraps to 2^64 - 1, above any max.  Strict is env_number as
+// verify_batch_host.hpp had it: the same with `*e < '0' || *e > '9'` refused as well.
+static void test_both_readings() {
+    static const char *V = "ZKHIP_SCALE_CHUNK", *WHAT = "a number of points from 1 to 2^28";
+    const uint64_t DFLT = 7, MAX = 1ull << 28, NO = ~0ull;       // NO: refused
+    const struct {
+        const char *value;
+        uint64_t lax, strict;
+    } rows[] = {{nullptr, DFLT, DFLT}, {"", DFLT, DFLT}, {"5", 5, 5},   {" 5", 5, NO},           {"+5", 5, NO},          {"5 ", NO, NO},
+                {"-1", NO, NO},        {"0", NO, NO},    {"x", NO, NO}, {"268435456", MAX, MAX}, {"268435457", NO, NO}};
+    for (const auto &r : rows)
+        for (const EnvForm form : {ENV_LAX, ENV_STRICT}) {
+            if (r.value) setenv(V, r.value, 1);
+            else unsetenv(V);
+            const uint64_t want = form == ENV_LAX ? r.lax : r.strict;
+            const char *shown = r.value ? r.value : "(unset)", *mode = form == ENV_LAX ? "lax" : "strict";
+            try {
+                const uint64_t v = env_number(V, DFLT, 1, MAX, WHAT, form);
+                CHECK(v == want, "%s '%s': got %llu", mode, shown, (unsigned long long)v);
+            } catch (const std::invalid_argument &e) {
+                CHECK(want == NO, "%s '%s' refused: %s", mode, shown, e.what());
+                CHECK(strcmp(e.what(), "ZKHIP_SCALE_CHUNK: a number of points from 1 to 2^28 expected") == 0, "%s '%s': message '%s'", mode, shown, e.what());
+            }
+        }
+    setenv(V, "0", 1);                                // 0 where the range holds it (the cooperative thresholds): both take it
+    CHECK(env_number(V, DFLT, 0, MAX, WHAT, ENV_LAX) == 0 && env_number(V, DFLT, 0, MAX, WHAT) == 0, "0 with min 0");
+    setenv(V, " 5", 1);                               // the form left out is the strict one
+    try {
+        env_number(V, DFLT, 1, MAX, WHAT);
+        CHECK(false, "' 5' accepted by default");
+    } catch (const std::invalid_argument &) {
+    }
+    unsetenv(V);
+}
+
+static void test_switch_and_pick() {
+    static const char *V = "ZKHIP_SCALE_PLAIN";
+    const struct {
+        const char *value;
+        bool on;
+    } rows[] = {{nullptr, false}, {"", false}, {"0", false}, {"1", true}, {"00", true}};
+    for (const auto &r : rows) {
+        if (r.value) setenv(V, r.value, 1);
+        else unsetenv(V);
+        CHECK(env_switch(V) == r.on, "switch '%s'", r.value ? r.value : "(unset)");
+    }
+    unsetenv(V);
+
+    const uint32_t N = NO_BAD_POINT;
+    const struct {
+        uint32_t h[4], kind, index;
+    } picks[] = {{{N, N, N, N}, 0, N}, {{5, 5, N, N}, 1, 5}, {{N, 7, 7, N}, 2, 7}, {{N, 9, 3, N}, 3, 3}, {{N, N, N, 0}, 4, 0}};
+    for (const auto &p : picks) {
+        const BadPoint b = lowest_bad(p.h);
+        CHECK(b.kind == p.kind && (!p.kind || b.index == p.index), "pick {%u, %u, %u, %u}: kind %u at %u", p.h[0], p.h[1], p.h[2], p.h[3], b.kind, b.index);
+    }
+    CHECK(strcmp(KIND_TEXT[1], "has a coordinate that is not below q") == 0 && strcmp(KIND_TEXT[2], "is not on the curve") == 0 &&
+              strcmp(KIND_TEXT[3], "is not in the subgroup") == 0 && strcmp(KIND_TEXT[4], "is the point at infinity") == 0,
+          "the kinds' texts");
+
+    uint8_t s[32] = {0};
+    CHECK(is_0_or_1(s), "0");
+    s[0] = 1;
+    CHECK(is_0_or_1(s), "1");
+    s[0] = 2;
+    CHECK(!is_0_or_1(s), "2");
+    s[0] = 1, s[31] = 1;
+    CHECK(!is_0_or_1(s), "1 + 2^248");
+    s[0] = 0;
+    CHECK(!is_0_or_1(s), "2^248");
 }
 
 // ---------------------------------------------------------------- scalars and the report's size
@@ -261,6 +337,8 @@ static void test_chunk_plan() {
 
 int main() {
     test_env_number();
+    test_both_readings();
+    test_switch_and_pick();
     test_scalars();
     test_chunk_plan();
     if (bad) {
