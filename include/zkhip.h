@@ -282,6 +282,33 @@ int zk_fr_abc_to_h(uint8_t *h, const uint8_t *a, const uint8_t *b, uint64_t n);
  * scalarSize = 32; result as AFFINE Montgomery (all-zero = infinity). */
 int zk_msm_g1(uint8_t out[64], const uint8_t *bases, const uint8_t *scalars, uint64_t n);
 int zk_msm_g2(uint8_t out[128], const uint8_t *bases, const uint8_t *scalars, uint64_t n);
+/* The first step of every MSM, shown: the signed-digit recoding and the bucket sort of a scalar vector, as zk_msm_g1/g2
+ * (table_mode 0, window_bits 0) and the prover (its table mode and window) run it.  Set plan->size = sizeof(zk_msm_sort_plan)
+ * before the call (only `size` bytes are written).  With offsets == NULL and entries == NULL only the plan is filled: no
+ * device is touched, so this works on a machine without a GPU.  Otherwise the scalars (`batch` vectors of n each, back to
+ * back, 32 B LE standard form; values >= r are reduced first) are uploaded and sorted, and offsets[0 .. total_buckets] and
+ * entries[0 .. E) come back, E = offsets[total_buckets] = plan->entries <= max_entries.  batch: 0 or 1 = one vector.
+ *
+ * What the arrays mean.  A scalar k < r is written k = sum_w d_w 2^(c w), w < W, with signed digits
+ * -2^(c-1) <= d_w < 2^(c-1) (a window value >= 2^(c-1) becomes negative and carries into the next window; the top digit is
+ * never negative).  Every NON-ZERO digit of every scalar is one entry, and the entries of bucket b are
+ * entries[offsets[b] .. offsets[b+1]), in no particular order inside a bucket.  The bucket gives |d| and the bucket set:
+ * b = set * nbuckets + (|d| - 1), nbuckets = 2^(c-1).  An entry word is  row | (d < 0 ? 1u << 31 : 0) : the point the
+ * digit's magnitude multiplies is row `row` of the MSM's point table, negated when bit 31 is set.  Per table mode
+ * (i = index of the scalar in its vector):
+ *   0, tables as in the zkey:       sets = W, set = w;        row = i (the point itself; the host combines the W set sums)
+ *   1, a table row per window:      sets = 1, set = 0;        row = w * n + i (the table holds 2^(c w) P_i)
+ *      with batch > 1:              sets = batch, set = v, the vector; row = w * n + i as before: vectors share the table
+ *   2, a row per second window:     sets = 2, set = w & 1;    row = (w >> 1) * n + i (the table holds 2^(2c u) P_i;
+ *                                   the host doubles the sum of set 1 c times)
+ * plan->n is the number of scalars sorted (batch * n), max_entries = max(plan->n, 1) * W.
+ * Errors: table_mode > 2, batch > 1 with table_mode != 1, n * batch * W >= 2^32 or table rows >= 2^31. */
+typedef struct zk_msm_sort_plan {
+    uint32_t size, c, W, sets, nbuckets, total_buckets, table_mode, batch;
+    uint64_t n, max_entries, entries;
+} zk_msm_sort_plan;
+int zk_msm_sort(const uint8_t *scalars, uint64_t n, uint32_t window_bits, uint32_t table_mode, uint32_t batch,
+                zk_msm_sort_plan *plan, uint32_t *offsets /* total_buckets + 1 */, uint32_t *entries /* max_entries */);
 
 /* ---- synthetic tables & single-point helpers (benchmark inputs) ------ */
 /* out[i] = P0 + i*Q, affine Montgomery, generated on the GPU (host output buffer). */

@@ -13,7 +13,7 @@ from .lib import (ZkHipError, load_library, library_path, fr_mul_vec, fq_mul_vec
                   fr_abc_to_h, msm_g1, msm_g2, proof_to_json, public_to_json, device_count,
                   synth_chain_g1, synth_chain_g2, fixed_base_g1, fixed_base_g2, g1_lagrange, g2_lagrange, g1_scale, g1_scale_plan, g1_mul, g2_mul, assemble, PinnedBuffer,
                   g2_in_subgroup, g1_power_msm, g2_power_msm, fr_power_dft,
-                  g1_mul_vec, g2_mul_vec, g1_power_scale, g2_power_scale, glv_split)
+                  g1_mul_vec, g2_mul_vec, g1_power_scale, g2_power_scale, glv_split, msm_sort)
 from .prover import Prover, MultiProver, prove_files                 # noqa: F401
 from .r1cs import R1cs, R1csReport, write_r1cs                      # noqa: F401
 from .ptau import PtauFile, PtauReport, groth16_setup, prepare_phase2, ptau_check, ptau_check_sizes, write_trapdoor_ptau, ptau_new, ptau_contribute, ptau_contribute_sizes      # noqa: F401

@@ -131,13 +131,17 @@ struct SortBufs {
     uint64_t max_entries() const { return (n ? n : 1) * plan.W; }
     // batch > 1: `batch` scalar vectors of n_ scalars each, sorted together into one bucket set per vector
     // precomp: 0 = tables as in the zkey, 1 = a table row per window, 2 = a row per second window (MsmPlan::precomp)
-    void alloc(uint64_t n_, uint32_t window_bits, uint32_t precomp = 0, uint32_t batch = 1) {
+    // the plan and the size rules alone: nothing is allocated and no device is touched (zk_msm_sort's plan-only call)
+    void set_plan(uint64_t n_, uint32_t window_bits, uint32_t precomp = 0, uint32_t batch = 1) {
         plan = make_msm_plan(n_ ? n_ : 1, window_bits, precomp, batch);
         n = n_ * (batch > 1 ? batch : 1);
         // sort entries are 32-bit (bit 31 = digit sign): positions n*W and, with window-precomputed
         // tables, table rows j*n + i must stay below 2^32 / 2^31
         if ((n ? n : 1) * plan.W >= (1ull << 32)) throw std::invalid_argument("MSM too large: n * windows >= 2^32 sort entries");
         if ((n ? n : 1) * msm_table_rows(plan) >= (1ull << 31)) throw std::invalid_argument("MSM too large: table rows >= 2^31");
+    }
+    void alloc(uint64_t n_, uint32_t window_bits, uint32_t precomp = 0, uint32_t batch = 1) {
+        set_plan(n_, window_bits, precomp, batch);
         MsmSortSizes z = msm_sort_sizes(n, plan);
         lo.alloc(z.lo_u16);
         counts.alloc(z.counts_u32);

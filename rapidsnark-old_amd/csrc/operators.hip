@@ -271,4 +271,42 @@ int zk_msm_g2(uint8_t out[128], const uint8_t *bases, const uint8_t *scalars, ui
     return guarded([&] { msm_generic<G2Affine, G2XYZZ, G2Acc>(out, bases, scalars, n, true); });
 }
 
+// The sort of msm_generic and of the prover, shown: the plan, the bucket starts and the entry list.  No kernel of its own.
+int zk_msm_sort(const uint8_t *scalars, uint64_t n, uint32_t window_bits, uint32_t table_mode, uint32_t batch, zk_msm_sort_plan *plan,
+                uint32_t *offsets, uint32_t *entries) {
+    return guarded([&] {
+        if (!plan) throw std::invalid_argument("null argument");
+        if (plan->size < 4) throw std::invalid_argument("zk_msm_sort: plan->size is not set");
+        if (!offsets != !entries) throw std::invalid_argument("zk_msm_sort: offsets and entries are both given or both NULL");
+        if (n >= (1ull << 32)) throw std::invalid_argument("MSM too large: n * windows >= 2^32 sort entries");
+        SortBufs sb;
+        sb.set_plan(n, window_bits, table_mode, batch ? batch : 1);
+        zk_msm_sort_plan p{};
+        p.size = plan->size < sizeof p ? plan->size : (uint32_t)sizeof p;
+        p.c = sb.plan.c;
+        p.W = sb.plan.W;
+        p.sets = sb.plan.sets;
+        p.nbuckets = sb.plan.nbuckets;
+        p.total_buckets = sb.total_buckets();
+        p.table_mode = sb.plan.precomp;
+        p.batch = sb.plan.batch;
+        p.n = sb.n;
+        p.max_entries = sb.max_entries();
+        if (offsets) {
+            need_device();
+            if (sb.n && !scalars) throw std::invalid_argument("null argument");
+            DevBuf<Fr> sc;
+            sc.alloc(sb.n);
+            sc.upload(scalars, sb.n, 0);
+            sb.alloc(n, window_bits, table_mode, batch ? batch : 1);
+            sb.run(sc.p, 0);
+            HIP_TRY(hipMemcpy(offsets, sb.offsets.p, ((size_t)sb.total_buckets() + 1) * 4, hipMemcpyDeviceToHost));
+            p.entries = offsets[sb.total_buckets()];
+            if (p.entries > p.max_entries) throw std::runtime_error("zk_msm_sort: the sort reports more entries than n * windows");
+            if (p.entries) HIP_TRY(hipMemcpy(entries, sb.entries.p, (size_t)p.entries * 4, hipMemcpyDeviceToHost));
+        }
+        memcpy(plan, &p, p.size);
+    });
+}
+
 }   // extern "C"

@@ -229,7 +229,7 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_zkey_verify_sizes", "zk_zkey_verify",
            "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute",
            "zk_fr_poly_divide", "zk_kzg_create", "zk_kzg_destroy", "zk_kzg_info", "zk_kzg_commit", "zk_kzg_open", "zk_kzg_verify", "zk_kzg_verify_batch",
-           "zk_fr_batch_inverse", "zk_fr_prefix_product", "zk_fr_grand_product", "zk_plonk_permutation_product"]
+           "zk_fr_batch_inverse", "zk_fr_prefix_product", "zk_fr_grand_product", "zk_plonk_permutation_product", "zk_msm_sort"]
 ZK_SCAN_EXCLUSIVE = 1
 ZK_KZG_MONOMIAL, ZK_KZG_LAGRANGE, ZK_KZG_NO_LAGRANGE = 0, 1, 0xffffffff
 ZK_SCALE_PLAN_MAX = 130
@@ -301,6 +301,8 @@ def load_library():
     lib.zk_fr_abc_to_h.argtypes = [u8p, u8p, u8p, C.c_uint64]
     lib.zk_msm_g1.argtypes = [u8p, u8p, u8p, C.c_uint64]
     lib.zk_msm_g2.argtypes = [u8p, u8p, u8p, C.c_uint64]
+    if hasattr(lib, "zk_msm_sort"):
+        lib.zk_msm_sort.argtypes = [u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(zk_msm_sort_plan), C.c_void_p, C.c_void_p]
     lib.zk_synth_chain_g1.argtypes = [u8p, C.c_uint64, u8p, u8p]
     lib.zk_synth_chain_g2.argtypes = [u8p, C.c_uint64, u8p, u8p]
     lib.zk_fixed_base_g1.argtypes = [u8p, u8p, u8p, C.c_uint64]
@@ -488,6 +490,33 @@ def msm_g2(bases, scalars):
     out = np.zeros(128, dtype=np.uint8)
     check(load_library().zk_msm_g2(_ptr(out), _ptr(bases), _ptr(scalars), n))
     return out.tobytes()
+
+
+class zk_msm_sort_plan(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("size", "c", "W", "sets", "nbuckets", "total_buckets", "table_mode", "batch")] + \
+               [(k, C.c_uint64) for k in ("n", "max_entries", "entries")]
+
+
+def msm_sort(scalars, n, window_bits=0, table_mode=0, batch=1, plan_only=False):
+    """zk_msm_sort (include/zkhip.h): the digit recoding and bucket sort of `batch` vectors of n scalars each (n*batch*32
+    bytes, LE standard form).  -> (plan as a dict, offsets uint32[total_buckets + 1], entries uint32[E]); plan_only=True
+    fills the plan alone (no GPU needed; scalars may be None) and returns (plan, None, None)."""
+    fn = getattr(load_library(), "zk_msm_sort", None)
+    if fn is None:
+        raise ZkHipError("zk_msm_sort is not in this build of libzkhip.so")
+    plan = zk_msm_sort_plan()
+    plan.size = C.sizeof(zk_msm_sort_plan)
+    as_dict = lambda: {k: int(getattr(plan, k)) for k, _ in zk_msm_sort_plan._fields_ if k != "size"}
+    check(fn(None, n, window_bits, int(table_mode), batch, C.byref(plan), None, None))
+    if plan_only:
+        return as_dict(), None, None
+    sc = _buf(scalars)
+    if sc.size != plan.n * 32:
+        raise ValueError("scalars: %d bytes expected (batch x n x 32)" % (plan.n * 32))
+    offsets = np.zeros(plan.total_buckets + 1, dtype=np.uint32)
+    entries = np.zeros(plan.max_entries, dtype=np.uint32)
+    check(fn(_ptr(sc), n, window_bits, int(table_mode), batch, C.byref(plan), _ptr(offsets), _ptr(entries)))
+    return as_dict(), offsets, entries[:plan.entries].copy()
 
 
 def proof_to_json(proof_bytes):
