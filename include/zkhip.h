@@ -960,6 +960,75 @@ int zk_fr_grand_product(uint8_t *z, uint8_t last[32], const uint8_t *num, const 
 int zk_plonk_permutation_product(uint8_t *z, uint8_t last[32], const uint8_t *wires, const uint8_t *sigmas, uint32_t cols,
                                  uint32_t log_n, const uint8_t *shifts, const uint8_t beta[32], const uint8_t gamma[32], int32_t device);
 
+/* ---- PLONK quotient and coset transforms --------------------------------------------------- */
+/* Round 3 of a PLONK prover: the quotient t = num / Z_H from evaluations on a coset, and the coset transform it is made of.
+ * Nothing in the reference corresponds to them.  Encodings are the two sections' above: scalars are 32 bytes little-endian
+ * in STANDARD form and must be below r, which is checked before a device is touched; an error names the array and the
+ * lowest index.  Pointers are the host's; the vectors are staged through the device.  device -1: the current one.
+ * ZKHIP_QUOT_SEG=<points a lane takes> (decimal, 1 to 4096, read at every call, 16 otherwise; anything else is an error of the
+ * call, "ZKHIP_QUOT_SEG: a number of points per lane from 1 to 4096 expected") changes the shape of the three kernels of
+ * this section and not one byte of any result. */
+
+/* The transform on the coset g H', H' the m = 2^log_m-th roots of unity, w_m the root zk_fr_ntt uses for m.
+ * Forward (inverse == 0): in holds n_in <= m coefficients of p, out[i] = p(g w_m^i) for i < m, natural order.
+ * Inverse: in holds n_in = m evaluations, out[i] = coefficient i: the inverse transform's i-th value times g^(-i).
+ * shift NULL: g = 1; a forward call with n_in = m then equals zk_fr_ntt.  out == in is legal.  log_m <= 28.
+ * "zk_fr_coset_ntt: log_m 29 is above 28", "zk_fr_coset_ntt: n_in 9 is outside 1 .. 2^log_m = 8", "zk_fr_coset_ntt: n_in 4 is
+ * not 2^log_m = 8" (inverse), "zk_fr_coset_ntt: value 5 is not below r", "zk_fr_coset_ntt: shift is not below r",
+ * "zk_fr_coset_ntt: shift is zero". */
+int zk_fr_coset_ntt(uint8_t *out, const uint8_t *in, uint64_t n_in, uint32_t log_m, const uint8_t shift[32], int inverse, int32_t device);
+
+/* What does not change from proof to proof, kept on the device: the eight circuit polynomials of a three-column PLONK
+ * circuit over n = 2^log_n rows, extended once to the coset x_i = g w_4n^i, i < 4n (w_4n^4 = w, the root of round 2), the
+ * extension of L1 = (X^n - 1) / (n (X - 1)), the tables of the transforms of size 4n and the work vectors of one call. */
+typedef struct zk_plonk_circuit zk_plonk_circuit;
+typedef struct zk_plonk_circuit_view {
+    uint32_t log_n, basis;                  /* ZK_KZG_MONOMIAL: coefficients; ZK_KZG_LAGRANGE: values at w^j (what round 2 takes) */
+    const uint8_t *ql, *qr, *qm, *qo, *qc, *s1, *s2, *s3;   /* n rows each */
+    uint8_t k1[32], k2[32];                 /* NOT checked to give disjoint cosets, as the shifts of round 2 */
+    const uint8_t *shift;                   /* NULL: 5.  Refused unless g^(4n) != 1 */
+} zk_plonk_circuit_view;
+/* 1 <= log_n <= 25: every transform of size 4n <= 2^27 is zk_fr_ntt's pipeline.  Free HBM is checked before anything is
+ * allocated: while it is made the object holds the nine extensions twice (72 n rows), afterwards 76 n rows and the tables.
+ * "zk_plonk_circuit_create: log_n 26 is outside 1 .. 25", "zk_plonk_circuit_create: basis 7 is unknown",
+ * "zk_plonk_circuit_create: qm 5 is not below r" (ql, qr, qm, qo, qc, s1, s2, s3), "zk_plonk_circuit_create: k1 is not below
+ * r" (k2, shift alike), "zk_plonk_circuit_create: shift is zero", "zk_plonk_circuit_create: shift^(4n) is 1: Z_H vanishes on
+ * the coset".  Calls on one object are serialised. */
+int zk_plonk_circuit_create(zk_plonk_circuit **out, const zk_plonk_circuit_view *v, int32_t device);
+void zk_plonk_circuit_destroy(zk_plonk_circuit *c);
+/* Set plan->size = sizeof(zk_plonk_circuit_plan) before the call (only `size` bytes are written). */
+typedef struct zk_plonk_circuit_plan {
+    uint32_t size;
+    uint32_t log_n;
+    uint64_t points;              /* of the extension: 4n */
+    uint64_t device_bytes;        /* HBM the object holds */
+    uint32_t seg;                 /* ZKHIP_QUOT_SEG in effect */
+    uint32_t last_launches;       /* kernel launches of zk_plonk_circuit_create or of the last zk_plonk_quotient on the object */
+} zk_plonk_circuit_plan;
+int zk_plonk_circuit_info(zk_plonk_circuit *c, zk_plonk_circuit_plan *plan);
+
+/* t = num / Z_H, Z_H = X^n - 1, with
+ *   num = ql a + qr b + qm a b + qo c + qc + PI
+ *       + alpha [ (a + beta X + gamma)(b + beta k1 X + gamma)(c + beta k2 X + gamma) z(X)
+ *               - (a + beta s1 + gamma)(b + beta s2 + gamma)(c + beta s3 + gamma) z(w X) ]
+ *       + alpha^2 (z - 1) L1(X):
+ * snarkjs's round-3 terms.  a, b, cc, z: the proof's polynomials by coefficients, a_len .. z_len of them (blinding by
+ * multiples of Z_H makes them longer than n); pi: the n coefficients of the public-input polynomial, NULL: zero.
+ * t receives 4n rows, the coefficients of t with zeros from *t_len on; *t_len is one more than the index of the highest
+ * non-zero coefficient (0 for t = 0).  The quotient is made pointwise on the coset and brought back by one inverse
+ * transform, which is exact iff t has at most 4n coefficients: every length is 1 .. 2n and a_len + b_len + c_len + z_len <=
+ * 5n + 3 (the usual blinding, n + 2, n + 2, n + 2, n + 3, needs n >= 8).  "zk_plonk_quotient: b_len 17 is outside 1 .. 2n =
+ * 16", "zk_plonk_quotient: a_len + b_len + c_len + z_len = 25 exceeds 5n + 3 = 23: t would have more than 4n coefficients",
+ * "zk_plonk_quotient: z 5 is not below r" (a, b, c, z, pi), "zk_plonk_quotient: alpha is not below r" (beta, gamma alike).
+ * When num is NOT divisible by Z_H (a witness that breaks a gate or a copy constraint) the call does not refuse: it returns
+ * the interpolant of num / Z_H on the coset, of degree below 4n, and the caller compares *t_len with its own bound (3n - 3
+ * unblinded, 3n + 6 with the usual blinding).  A t_len above the bound is a necessary sign of a bad witness, NOT a proof of
+ * a good one: a remainder of very low degree can alias below the bound.  It does not replace a gate check.
+ * Splitting t into t_lo, t_mid, t_hi and blinding the parts is the caller's: three slices and two coefficients. */
+int zk_plonk_quotient(zk_plonk_circuit *c, uint8_t *t, uint64_t *t_len, const uint8_t *a, uint64_t a_len, const uint8_t *b, uint64_t b_len,
+                      const uint8_t *cc, uint64_t c_len, const uint8_t *z, uint64_t z_len, const uint8_t *pi, const uint8_t alpha[32],
+                      const uint8_t beta[32], const uint8_t gamma[32]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,16 @@ class zk_kzg_plan(C.Structure):
                 ("seg", C.c_uint32), ("last_launches", C.c_uint32)]
 
 
+class zk_plonk_circuit_view(C.Structure):
+    _fields_ = [("log_n", C.c_uint32), ("basis", C.c_uint32)] + [(name, C.c_void_p) for name in ("ql", "qr", "qm", "qo", "qc", "s1", "s2", "s3")] + \
+               [("k1", C.c_uint8 * 32), ("k2", C.c_uint8 * 32), ("shift", C.c_void_p)]
+
+
+class zk_plonk_circuit_plan(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("log_n", C.c_uint32), ("points", C.c_uint64), ("device_bytes", C.c_uint64), ("seg", C.c_uint32),
+                ("last_launches", C.c_uint32)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -229,7 +239,8 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_zkey_verify_sizes", "zk_zkey_verify",
            "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute",
            "zk_fr_poly_divide", "zk_kzg_create", "zk_kzg_destroy", "zk_kzg_info", "zk_kzg_commit", "zk_kzg_open", "zk_kzg_verify", "zk_kzg_verify_batch",
-           "zk_fr_batch_inverse", "zk_fr_prefix_product", "zk_fr_grand_product", "zk_plonk_permutation_product", "zk_msm_sort"]
+           "zk_fr_batch_inverse", "zk_fr_prefix_product", "zk_fr_grand_product", "zk_plonk_permutation_product", "zk_msm_sort",
+           "zk_fr_coset_ntt", "zk_plonk_circuit_create", "zk_plonk_circuit_destroy", "zk_plonk_circuit_info", "zk_plonk_quotient"]
 ZK_SCAN_EXCLUSIVE = 1
 ZK_KZG_MONOMIAL, ZK_KZG_LAGRANGE, ZK_KZG_NO_LAGRANGE = 0, 1, 0xffffffff
 ZK_SCALE_PLAN_MAX = 130
@@ -389,6 +400,14 @@ def load_library():
         lib.zk_fr_prefix_product.argtypes = [u8p, u8p, C.c_uint64, C.c_uint32, C.c_int32]
         lib.zk_fr_grand_product.argtypes = [u8p, u8p, u8p, u8p, C.c_uint64, C.c_int32]
         lib.zk_plonk_permutation_product.argtypes = [u8p, u8p, u8p, u8p, C.c_uint32, C.c_uint32, u8p, u8p, u8p, C.c_int32]
+    if hasattr(lib, "zk_plonk_quotient"):
+        lib.zk_fr_coset_ntt.argtypes = [u8p, u8p, C.c_uint64, C.c_uint32, u8p, C.c_int, C.c_int32]
+        lib.zk_plonk_circuit_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(zk_plonk_circuit_view), C.c_int32]
+        lib.zk_plonk_circuit_destroy.argtypes = [C.c_void_p]
+        lib.zk_plonk_circuit_destroy.restype = None
+        lib.zk_plonk_circuit_info.argtypes = [C.c_void_p, C.POINTER(zk_plonk_circuit_plan)]
+        lib.zk_plonk_quotient.argtypes = [C.c_void_p, u8p, C.POINTER(C.c_uint64), u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p,
+                                          u8p, u8p, u8p]
     _LIB = lib
     return lib
 
