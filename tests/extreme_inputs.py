@@ -7,9 +7,13 @@ kernels hold is bytes * 2^5 mod p.  A word that must become T inside the kernel 
 leaves (bytes * K_IN + M p) / 2^261 with 0 <= bytes, K_IN < p and M within 2^235 of [0, 2^261): a representative of T in
 (-p / 2^20, p + p / 160).  For p - p / 160 > T > p / 160 the representative is T itself, limb for limb (internal_limbs()).
 
+The coset entries of csrc/plonkquot.hip do NOT convert that way: see held / held_families below.
+
 G1 points (extreme_g1) are in the group whatever their coordinates; G2 points with a chosen coordinate (extreme_g2, half_zero_g2)
 are on the twist but outside its order-r subgroup: see the section comment there for what may receive them.
 """
+import functools
+
 import numpy as np
 
 from oracle import bn254 as bn
@@ -131,6 +135,79 @@ def big_size_inputs(logn):
     n = 1 << logn
     return [("all_top", all_top(n)), ("all_ones_limbs", all_ones_limbs(n)), ("stride(11,top)", stride(n, TILE_BITS, R - 1)),
             ("stride(12,tmax)", stride(n, TILE_BITS + 1, T_MAX_WORD_FR))]
+
+
+# ------------------------------------------------------------------------------------------ Fr rows for the coset transforms
+# csrc/plonkquot.hip does not convert with from_mont256: k_coset_load turns a STANDARD row v_i into the canonical word of
+# v_i g^i 2^261 mod r (one product with the lane's power, then Fr29::store), and that word is what the transform and the
+# quotient kernel load.  Canonical: the limbs are those of the integer itself, for every target in [0, r).
+INV_261 = pow(1 << 261, -1, R)
+
+
+def held(t):
+    """The standard value whose device word, after k_coset_load at row 0 (or with g = 1), has the limbs of t."""
+    assert 0 <= t < R
+    return t * INV_261 % R
+
+
+def loaded_word(v, i=0, g=1):
+    """What the kernels hold for the standard row v at index i on the coset of g: v g^i 2^261 mod r, canonical."""
+    return v * pow(g, i, R) % R * (1 << 261) % R
+
+
+@functools.lru_cache(maxsize=8)
+def _inverse_powers(n, g):
+    gi, x, out = pow(g, -1, R), 1, []
+    for _ in range(n):
+        out.append(x)
+        x = x * gi % R
+    return out
+
+
+def held_rows(targets, g=1):
+    """Standard rows v_i = T_i 2^-261 g^-i: row i is loaded as the word T_i on the coset of g.  A list of integers."""
+    targets = list(targets)
+    if g == 1:
+        return [held(t) for t in targets]
+    return [held(t) * p % R for t, p in zip(targets, _inverse_powers(len(targets), g))]
+
+
+def _family_targets(logn):
+    """[(name, targets)]: the words of the families above as TARGETS of the load, integers in [0, r)."""
+    n = 1 << logn
+    bits = np.random.default_rng(1000 + logn).integers(0, 2, size=n, dtype=np.uint8)
+    fams = [("all_top", [R - 1] * n), ("all_ones_limbs", [T_MAX] * n), ("mask01", [(R - 1) * int(b) for b in bits]),
+            ("alternating", [R - 1, 1] * (n // 2))]
+    for s in STRIDE_BITS:
+        if s <= logn:
+            fams += [("stride(%d,%s)" % (s, vn), [v if i % (1 << s) == 0 else 0 for i in range(n)]) for vn, v in (("top", R - 1), ("tmax", T_MAX))]
+    return fams
+
+
+def held_families(logn, g=1):
+    """[(name, rows)] at m = 2^logn, rows lists of standard integers: all_top, all_ones_limbs, mask01, alternating and
+    stride(s, v) at STRIDE_BITS as words the transform LOADS on the coset of g (forward: the shift in use; inverse: g = 1,
+    its load keeps no power).  The families above aim at x 32 through from_mont256; the coset entry does not pass through it."""
+    return [(name, held_rows(t, g)) for name, t in _family_targets(logn)]
+
+
+def coset_preimages(logn, g=1):
+    """[(name, rows)]: for each family the standard rows whose FORWARD transform on the coset of g ends at it, the
+    transform's last stage leaving the family's words: the C restatement's inverse transform of held(T), times g^-i."""
+    out = []
+    for name, t in _family_targets(logn):
+        c = unpack(co.fr_fft(pack(held_rows(t)), inverse=True))
+        out.append(("coset_preimage(%s)" % name, [v * p % R for v, p in zip(c, _inverse_powers(len(c), g))]))
+    return out
+
+
+@functools.lru_cache(maxsize=2)
+def big_coset_inputs(logn, g=1):
+    """The four inputs of big_size_inputs as loaded words, for one large size."""
+    n = 1 << logn
+    t = [("all_top", [R - 1] * n), ("all_ones_limbs", [T_MAX] * n), ("stride(11,top)", [R - 1 if i % (1 << TILE_BITS) == 0 else 0 for i in range(n)]),
+         ("stride(12,tmax)", [T_MAX if i % (2 << TILE_BITS) == 0 else 0 for i in range(n)])]
+    return [(name, held_rows(v, g)) for name, v in t]
 
 
 def unpack(b):

@@ -260,3 +260,51 @@ def test_c_restatement_product_on_the_edge_cross_product(field, p):
     assert a.size == b.size == 32 * 17 * 17
     fn = co.fr_mul_vec if field == "fr" else co.fq_mul_vec
     assert xi.unpack(fn(a, b)) == want
+
+
+# ------------------------------------------------------------------------------------------ rows for the coset transforms
+COSET_SHIFTS = (1, 5, xi.held(xi.T_MAX), R - 1)
+
+
+def test_held_values_are_loaded_as_their_targets():
+    assert xi.limbs29(xi.loaded_word(xi.held(xi.T_MAX))) == [(1 << 29) - 1] * 8 + [3171405]
+    assert xi.loaded_word(xi.held(R - 1)) == R - 1
+    assert xi.limbs29(xi.loaded_word(xi.held(1))) == [1] + [0] * 8
+    assert xi.loaded_word(1) == (1 << 261) % R and xi.held((1 << 261) % R) == 1
+    # the shift whose own word, the first entry of the lane's power table, sits on full limbs
+    assert xi.limbs29(xi.held(xi.T_MAX) * (1 << 261) % R) == xi.limbs29(xi.T_MAX)
+
+
+@pytest.mark.parametrize("g", COSET_SHIFTS)
+def test_held_families_are_loaded_as_the_families_they_name(g):
+    """the limbs of v_i g^i 2^261 mod r equal the targets, row by row"""
+    logn, n = 7, 128
+    bits = xi.unpack(xi.mask01(n, 1000 + logn))
+    want = {"all_top": [R - 1] * n, "all_ones_limbs": [xi.T_MAX] * n, "mask01": bits, "alternating": [R - 1, 1] * (n // 2)}
+    for s in (1, 3, 6):
+        want["stride(%d,top)" % s] = [R - 1 if i % (1 << s) == 0 else 0 for i in range(n)]
+        want["stride(%d,tmax)" % s] = [xi.T_MAX if i % (1 << s) == 0 else 0 for i in range(n)]
+    fams = xi.held_families(logn, g)
+    assert [name for name, _ in fams] == list(want)
+    for name, rows in fams:
+        assert len(rows) == n and all(0 <= v < R for v in rows), name
+        assert [xi.limbs29(xi.loaded_word(v, i, g)) for i, v in enumerate(rows)] == [xi.limbs29(t) for t in want[name]], name
+    assert [name for name, _ in xi.held_families(12)][-2:] == ["stride(11,top)", "stride(11,tmax)"]
+    assert xi.held_rows([5, 6, 7], g) == [xi.held(t) * pow(g, -i, R) % R for i, t in enumerate((5, 6, 7))]
+
+
+@pytest.mark.parametrize("g", COSET_SHIFTS)
+def test_coset_preimages_end_at_the_families(g):
+    """the forward transform on the coset of g, in Python integers, leaves words with the targets' limbs"""
+    import plonk_instance as pi
+    logn = 6
+    ends = dict(xi.held_families(logn))
+    pre = xi.coset_preimages(logn, g)
+    assert [name for name, _ in pre] == ["coset_preimage(%s)" % name for name in ends]
+    for name, rows in pre:
+        out = pi.coset_ext(rows, logn, g)
+        assert out == ends[name[15:-1]], name
+        assert [xi.loaded_word(v) for v in out] == [xi.loaded_word(v) for v in ends[name[15:-1]]]
+    big = xi.big_coset_inputs(13, 5)
+    assert [name for name, _ in big] == [name for name, _ in xi.big_size_inputs(13)]
+    assert xi.loaded_word(big[3][1][4096], 4096, 5) == xi.T_MAX and big[3][1][2048] == 0 and xi.loaded_word(big[2][1][2048], 2048, 5) == R - 1

@@ -273,3 +273,10 @@ def test_no_product_column_leaves_int64_for_the_job_shapes_in_use(tmp_path):
     for block in ("G2 random chain", "G2 extreme X, self and negative", "G2 extreme X, running sum", "G2 half-zero shapes"):
         line = [ln for ln in out.stdout.splitlines() if ln.startswith(block)]
         assert len(line) == 1 and "(lane pair), overflows 0" in line[0], out.stdout
+    # csrc/plonkquot.hip: k_plonk_quotient's per-point statements and the coset load / store product over the cross products of
+    # T_MAX, r - 1, 1, 0 and random words, every value checked against 64-bit-word arithmetic; spmv_row's sum between reductions
+    for block, words in (("PLONK quotient point", ("peak |column| / 2^58 = ", "largest |num| / r = ", "wrong values 0, overflows 0")),
+                         ("PLONK coset load / store", ("wrong values 0, overflows 0",)),
+                         ("spmv_row, 8 products between reductions", ("largest |running sum| / r = ", "value right, overflows 0"))):
+        line = [ln for ln in out.stdout.splitlines() if ln.startswith(block)]
+        assert len(line) == 1 and all(w in line[0] for w in words) and line[0].endswith("overflows 0"), out.stdout

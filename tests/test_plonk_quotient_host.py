@@ -183,3 +183,47 @@ def test_c_entries_refuse_bad_arguments_before_a_device_is_touched():
     assert ntt(good, 4, 29, None, 0) == "zk_fr_coset_ntt: log_m 29 is above 28"
     assert ntt(le([1] * 9), 9, 3, None, 0) == "zk_fr_coset_ntt: n_in 9 is outside 1 .. 2^log_m = 8"
     assert ntt(good, 4, 3, None, 1) == "zk_fr_coset_ntt: n_in 4 is not 2^log_m = 8"
+
+
+# ---------------------------------------------------------------- instances with chosen coset evaluations
+@pytest.mark.parametrize("log_n", [1, 3, 7])
+def test_the_two_oracles_agree_on_the_empty_circuit(log_n):
+    inst = pi.extreme_instance("empty", log_n)
+    ta, rem = pi.oracle_a(inst)
+    assert not any(rem) and not any(ta)
+    assert ta == pi.oracle_b(inst) == pi.oracle_b(inst, g=7)
+    assert pi.t_len_of(ta) == 0
+
+
+@pytest.mark.parametrize("log_n", [1, 3, 7, 9])
+def test_constant_instances_fill_the_interpolant(log_n):
+    """a constant instance breaks the gate identity: oracle B's t has all 4n coefficients (fewer where alpha = 0 or z = 1)"""
+    for name in pi.CONSTANT_FAMILIES if log_n < 9 else ("const_tmax", "const_top", "const_one"):
+        inst = pi.extreme_instance(name, log_n)
+        assert pi.t_len_of(pi.oracle_b(inst)) == pi.constant_t_len(name, inst.n), name
+        assert any(pi.oracle_a(inst)[1]), name            # and long division leaves a remainder
+
+
+def test_the_builders_hold_the_evaluations_they_name():
+    import extreme_inputs as xi
+    log_n, g = 4, 5
+    n = 1 << log_n
+    inst = pi.extreme_instance("even_alternating", log_n, g)
+    assert [len(p) for p in (inst.a, inst.b, inst.c, inst.z)] == [2 * n, 2 * n, 1, 1]
+    a = pi.coset_ext(inst.a, log_n + 2, g)
+    b = pi.coset_ext(inst.b, log_n + 2, g)
+    assert [xi.loaded_word(v) for v in a[0::2]] == [R - 1, 1] * n and [xi.loaded_word(v) for v in b[0::2]] == [1, R - 1] * n
+    assert [xi.loaded_word(v) for v in pi.coset_ext(inst.ql, log_n + 2, g)[0::4]] == [R - 1, 1] * (n // 2)
+    assert inst.ql_v == pi.ntt(inst.ql) and pi.ntt(inst.ql_v, inverse=True) == inst.ql
+    inst = pi.extreme_instance("even_mask01", log_n, g)
+    assert set(xi.loaded_word(v) for v in pi.coset_ext(inst.a, log_n + 2, g)[0::2]) == {0, R - 1}
+    assert set(xi.loaded_word(v) for v in pi.coset_ext(inst.z, log_n + 2, g)) == {R - 1}
+    # a builder that is handed the wrong evaluations says so: the assertion is the check
+    with pytest.raises(AssertionError):
+        pi.even_point_instance(log_n, [1] * n, [1] * 2 * n, {}, {}, (1, 2, 3))
+    inst = pi.extreme_instance("longest", log_n)
+    assert [len(p) for p in (inst.a, inst.b, inst.c, inst.z)] == [2 * n, 2 * n, n, 3] and inst.a[-1] == inst.b[-1] == R - 1
+    # sigma the identity with a constant z: the permutation term vanishes at any point
+    inst = pi.extreme_instance("sigma_identity", log_n)
+    zeta = 0x1234567
+    assert pi.num_at(inst, zeta) == inst.alpha * inst.alpha * (inst.z[0] - 1) * (pow(zeta, n, R) - 1) * pow(n * (zeta - 1), -1, R) % R

@@ -15,12 +15,16 @@
 //   and 0 in every pairing, a point meeting itself and its negative; those points on a running sum; and the half-zero shapes
 //   of tests/extreme_inputs.py (half_zero_g2: P or R zero in exactly one component, y or x with a zero component).  After
 //   every addition the lane-pair accumulator must equal the Fq2r one, component by component in canonical form.
+//   plus csrc/plonkquot.hip: the per-point statements of k_plonk_quotient and the product of k_coset_load / k_coset_store over
+//   cross products of T_MAX, r - 1, 1, 0 and random words, every value checked against 64-bit-word arithmetic; and the loop of
+//   spmv_row (csrc/fieldops.hip), 8 products between reductions, for its largest running sum.
 // Prints the peak |column| of every block as a multiple of 2^58 and exits 1 on any overflow, wrong all-sums value, lane-pair
-// result that differs from the Fq2r one, or P, -P that does not end at infinity.
+// result that differs from the Fq2r one, P, -P that does not end at infinity, wrong PLONK value, or running sum outside (-16r, 16r).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <vector>
 #include "curve29.hpp"
 
@@ -504,7 +508,338 @@ static int g2_chains(const Fq29 &tq) {
     return bad;
 }
 
-int main() {
+// ---- csrc/plonkquot.hip on the host: the per-point statements of k_plonk_quotient one for one (the mul2 pairs, the run2 of
+// the two JMulAdd2 jobs, add / sub exactly where the kernel has them) and the product of k_coset_load / k_coset_store with
+// its running power, every result checked for its VALUE against arithmetic that shares nothing with field29.hpp: 4 x 64-bit
+// Montgomery products in unsigned __int128 (mont64), K(x, y) = x y 2^-261 = mont64(mont64(x, y), 2^251).
+// -DPLONK_MUTANT=K (0: the kernel as it is) builds one of the deliberate changes of DESIGN.md section 10 into the restatement;
+// the argument `plonk` runs these blocks alone and exits 1 when the change is seen (a wrong value or an overflow).
+struct U256 {
+    uint64_t w[4];
+};
+static U256 R64;                                      // r
+static uint64_t R64_N0;                               // -r^-1 mod 2^64
+static bool u_ge(const U256 &a, const U256 &b) {
+    for (int i = 3; i >= 0; i--)
+        if (a.w[i] != b.w[i]) return a.w[i] > b.w[i];
+    return true;
+}
+static U256 u_sub_raw(const U256 &a, const U256 &b) {
+    U256 r;
+    unsigned __int128 br = 0;
+    for (int i = 0; i < 4; i++) {
+        const unsigned __int128 d = (unsigned __int128)a.w[i] - b.w[i] - br;
+        r.w[i] = (uint64_t)d;
+        br = (d >> 64) & 1;
+    }
+    return r;
+}
+static U256 u_add(const U256 &a, const U256 &b) {     // mod r, operands below r < 2^254
+    U256 r;
+    unsigned __int128 c = 0;
+    for (int i = 0; i < 4; i++) {
+        c += (unsigned __int128)a.w[i] + b.w[i];
+        r.w[i] = (uint64_t)c;
+        c >>= 64;
+    }
+    return u_ge(r, R64) ? u_sub_raw(r, R64) : r;
+}
+static U256 u_sub(const U256 &a, const U256 &b) { return u_ge(a, b) ? u_sub_raw(a, b) : u_sub_raw(R64, u_sub_raw(b, a)); }     // r - (b - a)
+static U256 mont64(const U256 &a, const U256 &b) {    // a b 2^-256 mod r
+    uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; i++) {
+        unsigned __int128 c = 0;
+        for (int j = 0; j < 4; j++) {
+            c += (unsigned __int128)a.w[j] * b.w[i] + t[j];
+            t[j] = (uint64_t)c;
+            c >>= 64;
+        }
+        c += t[4];
+        t[4] = (uint64_t)c;
+        t[5] = (uint64_t)(c >> 64);
+        const uint64_t m = t[0] * R64_N0;
+        c = ((unsigned __int128)m * R64.w[0] + t[0]) >> 64;
+        for (int j = 1; j < 4; j++) {
+            c += (unsigned __int128)m * R64.w[j] + t[j];
+            t[j - 1] = (uint64_t)c;
+            c >>= 64;
+        }
+        c += t[4];
+        t[3] = (uint64_t)c;
+        t[4] = t[5] + (uint64_t)(c >> 64);
+    }
+    U256 r{{t[0], t[1], t[2], t[3]}};
+    return (t[4] || u_ge(r, R64)) ? u_sub_raw(r, R64) : r;
+}
+static U256 u_from_limbs(const int32_t (&l)[9]) {     // non-negative limbs below 2^29, value below 2^256
+    U256 r{{0, 0, 0, 0}};
+    for (int i = 0; i < 9; i++) {
+        const int bit = 29 * i, w = bit >> 6, s = bit & 63;
+        r.w[w] |= (uint64_t)(uint32_t)l[i] << s;
+        if (s > 35 && w < 3) r.w[w + 1] |= (uint64_t)(uint32_t)l[i] >> (64 - s);
+    }
+    return r;
+}
+static U256 u_of(const Fr29 &x) { return u_from_limbs(Fr29::canonical(x).l); }
+static U256 K(const U256 &x, const U256 &y) {
+    static const U256 two251{{0, 0, 0, 1ull << 59}};
+    return mont64(mont64(x, y), two251);
+}
+static bool u_eq(const U256 &a, const U256 &b) { return a.w[0] == b.w[0] && a.w[1] == b.w[1] && a.w[2] == b.w[2] && a.w[3] == b.w[3]; }
+static void u_init() {
+    R64 = u_from_limbs(Fr29Params::P);
+    uint64_t inv = 1;                                 // Newton: r^-1 mod 2^64
+    for (int i = 0; i < 6; i++) inv *= 2 - R64.w[0] * inv;
+    R64_N0 = 0 - inv;
+}
+static double in_units_of_r(const Fr29 &x) {          // the value the limbs stand for, over r
+    long double v = 0, r = 0;
+    for (int i = 8; i >= 0; i--) {
+        v = v * 536870912.0L + x.l[i];
+        r = r * 536870912.0L + Fr29Params::P[i];
+    }
+    return (double)(v / r);
+}
+
+#ifndef PLONK_MUTANT
+#define PLONK_MUTANT 0
+#endif
+struct QuotRows {                                     // what a lane loads for one point: canonical words
+    Fr29 a, b, c, z, zw, ql, qr, qm, qo, qc, s1, s2, s3, l1, pi;
+};
+struct QuotK {                                        // QuotConsts, and the lane's 1 / Z_H
+    Fr29 alpha, alpha2, beta, gamma, bk1, bk2, zh, step;
+};
+struct QuotStats {
+    double num_peak = 0, sum_peak = 0;
+    long points = 0, wrong = 0;
+};
+// the body of k_plonk_quotient's loop; x is the lane's running point and moves on.  M: the deliberate change
+template <int M>
+static Fr29 quot_point(const QuotRows &v, const QuotK &k, Fr29 &x, bool has_pi, QuotStats &st) {
+    typedef Fr29 F;
+    const F &a = v.a, &b = v.b, &c = v.c, &z = v.z, &alpha = k.alpha, &alpha2 = k.alpha2, &beta = k.beta, &gamma = k.gamma, &bk1 = k.bk1, &bk2 = k.bk2;
+    F ab, bx, b1x, b2x, bs1, bs2, bs3, bz;
+    F::mul2(ab, a, b, bx, beta, x);
+    F::mul2(b1x, bk1, x, b2x, bk2, x);
+    const F f1 = M == 1 ? F::add_nc(F::add_nc(a, bx), gamma) : F::add(F::add(a, bx), gamma);
+    const F f2 = M == 1 ? F::add_nc(F::add_nc(b, b1x), gamma) : F::add(F::add(b, b1x), gamma), f3 = F::add(F::add(c, b2x), gamma);
+    F::mul2(bs1, beta, v.s1, bs2, beta, v.s2);
+    F::mul2(bs3, beta, v.s3, bz, M == 6 ? z : F::sub(z, F::one()), v.l1);
+    const F g1 = M == 7 ? F::add_nc(F::add_nc(a, bs1), gamma) : F::add(F::add(a, bs1), gamma);
+    const F g2 = M == 7 ? F::add_nc(F::add_nc(b, bs2), gamma) : F::add(F::add(b, bs2), gamma), g3 = F::add(F::add(c, bs3), gamma);
+    F p12, q12, p3, q3, P, Q, G1, G2, aD, T2, t, xn;
+    F::mul2(p12, f1, f2, q12, g1, g2);
+    F::mul2(p3, f3, z, q3, g3, v.zw);
+    F::mul2(P, p12, p3, Q, q12, q3);
+    {
+        F c3 = c;                                     // M == 3: c + 3r summed lazily, the same value mod r
+        if (M == 3)
+            for (int i = 0; i < 9; i++) c3.l[i] += 3 * Fr29Params::P[i];
+        F::run2(G1, F::JMulAdd2{v.ql, a, v.qr, b}, G2, F::JMulAdd2{v.qm, ab, v.qo, c3});
+    }
+    F::mul2(aD, alpha, M == 5 ? F::sub_nc(Q, P) : F::sub(P, Q), T2, alpha2, bz);
+    F num;
+    if (M == 2) {
+        num = F::add_nc(F::add_nc(G1, G2), F::add_nc(v.qc, aD));
+        num = F::add_nc(num, T2);
+        if (has_pi) num = F::add_nc(num, v.pi);
+    } else {
+        num = F::add(F::add(G1, G2), F::add(v.qc, aD));
+        num = F::add(num, T2);
+        if (has_pi) num = F::add(num, v.pi);
+    }
+    F::mul2(t, num, k.zh, xn, x, k.step);
+    // the same point in 64-bit words
+    const U256 ux = u_of(x), ua = u_of(a), ub = u_of(b), uc = u_of(c), uz = u_of(z), ube = u_of(beta), uga = u_of(gamma);
+    const U256 uf1 = u_add(u_add(ua, K(ube, ux)), uga), uf2 = u_add(u_add(ub, K(u_of(bk1), ux)), uga), uf3 = u_add(u_add(uc, K(u_of(bk2), ux)), uga);
+    const U256 ug1 = u_add(u_add(ua, K(ube, u_of(v.s1))), uga), ug2 = u_add(u_add(ub, K(ube, u_of(v.s2))), uga), ug3 = u_add(u_add(uc, K(ube, u_of(v.s3))), uga);
+    const U256 up = K(K(uf1, uf2), K(uf3, uz)), uq = K(K(ug1, ug2), K(ug3, u_of(v.zw)));
+    U256 un = u_add(u_add(K(u_of(v.ql), ua), K(u_of(v.qr), ub)), u_add(K(u_of(v.qm), K(ua, ub)), K(u_of(v.qo), uc)));
+    un = u_add(un, u_of(v.qc));
+    if (has_pi) un = u_add(un, u_of(v.pi));
+    un = u_add(un, K(u_of(alpha), u_sub(up, uq)));
+    un = u_add(un, K(u_of(alpha2), K(u_sub(uz, u_of(F::one())), u_of(v.l1))));
+    const F tc = F::canonical(t);                     // F::store
+    st.points++;
+    if (!u_eq(u_from_limbs(tc.l), K(un, u_of(k.zh))) || !u_eq(u_of(xn), K(ux, u_of(k.step)))) st.wrong++;
+    const double nv = in_units_of_r(num), fv[6] = {in_units_of_r(f1), in_units_of_r(f2), in_units_of_r(f3), in_units_of_r(g1), in_units_of_r(g2), in_units_of_r(g3)};
+    if ((nv < 0 ? -nv : nv) > st.num_peak) st.num_peak = nv < 0 ? -nv : nv;
+    for (double f : fv)
+        if (f > st.sum_peak) st.sum_peak = f;
+    x = xn;
+    return tc;
+}
+
+static Fr29 fr_extreme(int which) {                   // T_MAX, r - 1, 1, 0 as canonical words; 4: a random canonical word
+    Fr29 r = Fr29::zero();
+    switch (which) {
+    case 0:
+        for (int i = 0; i < 9; i++) r.l[i] = i < 8 ? (1 << 29) - 1 : 3171405;
+        break;
+    case 1:
+        for (int i = 0; i < 9; i++) r.l[i] = Fr29Params::P[i];
+        r.l[0] -= 1;
+        break;
+    case 2: r.l[0] = 1; break;
+    case 3: break;
+    default: r = random_canonical<Fr29>();
+    }
+    return r;
+}
+static Fr29 fr_drawn() { return fr_extreme((int)(rng() % 5)); }
+
+// Operands.  Pass 1: the cross product of {T_MAX, r - 1, 1, 0, random} over the wires a, b, c, z and over alpha, beta, gamma
+// (5^7 points), every other loaded word, 1 / Z_H and the step drawn from the same five by the generator.  Pass 2: the cross
+// product over ql, qr, qm, qo, qc, the three sigmas as one, z(w x) and L1 (5^8), the wires and challenges drawn.  beta k1,
+// beta k2 are beta k by the reference product (k1 = 2, k2 = 3 in that form), alpha^2 likewise.  x: a word of the five at
+// the start of a lane, then the raw product x step of the previous point, as on the device.  PI present at every second point.
+template <int M>
+static int plonk_quotient_points() {
+    zk_column_peak() = 0;
+    const long before = zk_column_overflows();
+    QuotStats st;
+    auto word = [](const U256 &u) {                   // canonical value -> limbs
+        u32 w[8];
+        for (int i = 0; i < 4; i++) w[2 * i] = (u32)u.w[i], w[2 * i + 1] = (u32)(u.w[i] >> 32);
+        return Fr29::from_words(w);
+    };
+    const U256 one = u_of(Fr29::one());
+    const U256 two = u_add(one, one), three = u_add(two, one);
+    Fr29 x = fr_drawn();
+    long idx = 0;
+    auto point = [&](QuotRows &v, QuotK &k) {
+        k.alpha2 = word(K(u_of(k.alpha), u_of(k.alpha)));
+        k.bk1 = word(K(u_of(k.beta), two));
+        k.bk2 = word(K(u_of(k.beta), three));
+        if (idx % 16 == 0) x = fr_drawn();            // a new lane
+        (void)quot_point<M>(v, k, x, (idx & 1) == 0, st);
+        idx++;
+    };
+    for (int i = 0; i < 78125; i++) {                 // 5^7
+        QuotRows v;
+        QuotK k;
+        int d = i;
+        Fr29 *cross[7] = {&v.a, &v.b, &v.c, &v.z, &k.alpha, &k.beta, &k.gamma};
+        for (Fr29 *p : cross) *p = fr_extreme(d % 5), d /= 5;
+        Fr29 *rest[13] = {&v.zw, &v.ql, &v.qr, &v.qm, &v.qo, &v.qc, &v.s1, &v.s2, &v.s3, &v.l1, &v.pi, &k.zh, &k.step};
+        for (Fr29 *p : rest) *p = fr_drawn();
+        point(v, k);
+    }
+    for (int i = 0; i < 390625; i++) {                // 5^8
+        QuotRows v;
+        QuotK k;
+        int d = i;
+        Fr29 *cross[8] = {&v.ql, &v.qr, &v.qm, &v.qo, &v.qc, &v.s1, &v.zw, &v.l1};
+        for (Fr29 *p : cross) *p = fr_extreme(d % 5), d /= 5;
+        v.s2 = v.s3 = v.s1;
+        Fr29 *rest[10] = {&v.a, &v.b, &v.c, &v.z, &v.pi, &k.alpha, &k.beta, &k.gamma, &k.zh, &k.step};
+        for (Fr29 *p : rest) *p = fr_drawn();
+        point(v, k);
+    }
+    const long over = zk_column_overflows() - before;
+    printf("PLONK quotient point: peak |column| / 2^58 = %.3f, largest |num| / r = %.3f, largest f / r = %.3f, %ld points, wrong values %ld, overflows %ld\n",
+           (double)zk_column_peak() / 288230376151711744.0, st.num_peak, st.sum_peak, st.points, st.wrong, over);
+    return st.wrong || over;
+}
+
+// k_coset_load: store(x p), p the lane's power: a word at the start, then the raw product p step.  k_coset_store: the same
+// product made canonical, and the raw-limb zero test that feeds t_len, which must say "zero" exactly where the value is 0
+template <int M>
+static int plonk_coset_products() {
+    zk_column_peak() = 0;
+    const long before = zk_column_overflows();
+    long wrong = 0, products = 0;
+    for (int i = 0; i < 125 * 40; i++) {
+        const Fr29 step = fr_extreme(i % 5), seed = fr_extreme(i / 5 % 5);
+        Fr29 p = seed;
+        for (int k = 0; k < 16; k++) {
+            const Fr29 x = k % 5 == 4 ? fr_extreme(i / 25 % 5) : fr_drawn();
+            const Fr29 prod = Fr29::mul(x, p), o = M == 4 ? prod : Fr29::canonical(prod);
+            const U256 want = K(u_of(x), u_of(p));
+            bool same = true;
+            Fr29 w = Fr29::zero();
+            {
+                u32 ww[8];
+                for (int j = 0; j < 4; j++) ww[2 * j] = (u32)want.w[j], ww[2 * j + 1] = (u32)(want.w[j] >> 32);
+                w = Fr29::from_words(ww);
+            }
+            for (int j = 0; j < 9; j++) same = same && o.l[j] == w.l[j];
+            if (!same || o.is_zero_raw() != w.is_zero_raw()) wrong++;
+            products++;
+            p = Fr29::mul(p, step);
+        }
+    }
+    const long over = zk_column_overflows() - before;
+    printf("PLONK coset load / store: peak |column| / 2^58 = %.3f, %ld products, wrong values %ld, overflows %ld\n",
+           (double)zk_column_peak() / 288230376151711744.0, products, wrong, over);
+    return wrong || over;
+}
+
+// spmv_row of csrc/fieldops.hip (k_spmv_abc, k_spmv_abc_long): a sum reduced after every 8 products, which csrc/r1cs.hip says
+// "touches the bound".  Rows of 64 terms of the witness word 2^256 - 1 (a valid operand: below 6 r) times the coefficient word
+// r - 1, and of words within 2^24 below them; the largest running sum in units of r must stay inside (-16, 16).  (A product
+// of non-negative operands below 2^256 and r lies in [0, r + r / 32): eight of them on a sum below r stay below 9.25 r.)
+static int spmv_row_bound() {
+    zk_column_peak() = 0;
+    const long before = zk_column_overflows();
+    u32 ones[8];
+    for (int i = 0; i < 8; i++) ones[i] = 0xffffffffu;
+    double peak = 0;
+    bool right = true;
+    // row 0: the two words themselves; then rows of words just below them, whose products' reduction parts differ
+    for (int row = 0; row < 2048; row++) {
+        u32 ww[8];
+        for (int i = 0; i < 8; i++) ww[i] = ones[i];
+        Fr29 v = fr_extreme(1);
+        if (row) {
+            ww[0] -= (u32)(rng() & 0xffffff);
+            v.l[0] -= (int32_t)(rng() & 0xffffff);          // r - 1 - k, k < 2^24 < the low limb of r
+        }
+        const Fr29 w = Fr29::from_words(ww);
+        U256 uw{{((uint64_t)ww[1] << 32) | ww[0], ~0ull, ~0ull, ~0ull}};
+        while (u_ge(uw, R64)) uw = u_sub_raw(uw, R64);
+        Fr29 sum = Fr29::zero();
+        uint32_t pending = 0;
+        U256 want{{0, 0, 0, 0}};
+        for (int k = 0; k < 64; k++) {
+            sum = Fr29::add(sum, Fr29::mul(w, v));
+            want = u_add(want, K(uw, u_of(v)));
+            const double s = in_units_of_r(sum);
+            if ((s < 0 ? -s : s) > peak) peak = s < 0 ? -s : s;
+            if (++pending == 8) {
+                sum = Fr29::reduce_near_zero(sum);
+                pending = 0;
+            }
+        }
+        right = right && u_eq(u_of(Fr29::reduce_near_zero(sum)), want);
+    }
+    const long over = zk_column_overflows() - before;
+    printf("spmv_row, 8 products between reductions: largest |running sum| / r = %.3f (operand range 16), value %s, overflows %ld\n", peak,
+           right ? "right" : "WRONG", over);
+    return !right || over || peak >= 16.0;
+}
+
+static int plonk_blocks() {
+    u_init();
+    // the reference arithmetic against known words: K(2^261, 2^261) = 2^261, and one product of field29.hpp
+    const U256 one = u_from_limbs(Fr29Params::ONE);
+    const Fr29 a = random_canonical<Fr29>(), b = random_canonical<Fr29>();
+    if (!u_eq(K(one, one), one) || !u_eq(u_of(Fr29::mul(a, b)), K(u_of(a), u_of(b)))) {
+        printf("FAIL: the 64-bit reference arithmetic disagrees with itself\n");
+        return 1;
+    }
+    int bad = plonk_quotient_points<PLONK_MUTANT>();
+    bad |= plonk_coset_products<PLONK_MUTANT>();
+    return bad;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "plonk") {          // the PLONK blocks alone (builds with -DPLONK_MUTANT=K)
+        const int bad = plonk_blocks();
+        printf(bad ? "FAIL: PLONK blocks (change %d)\n" : "OK: PLONK blocks (change %d)\n", PLONK_MUTANT);
+        return bad;
+    }
     if (families()) return 1;
     zk_column_peak() = 0;
     job_shapes<Fq29>("Fq", true);
@@ -529,6 +864,14 @@ int main() {
            zk_column_overflows());
     (void)fq_over;
     if (g2_chains(tmax_fq())) return 1;
+    if (plonk_blocks()) {
+        printf("FAIL: the PLONK quotient or coset products\n");
+        return 1;
+    }
+    if (spmv_row_bound()) {
+        printf("FAIL: spmv_row's running sum\n");
+        return 1;
+    }
     if (zk_column_overflows()) {
         printf("FAIL: %ld column overflows\n", zk_column_overflows());
         return 1;
