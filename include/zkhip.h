@@ -1029,6 +1029,84 @@ int zk_plonk_quotient(zk_plonk_circuit *c, uint8_t *t, uint64_t *t_len, const ui
                       const uint8_t *cc, uint64_t c_len, const uint8_t *z, uint64_t z_len, const uint8_t *pi, const uint8_t alpha[32],
                       const uint8_t beta[32], const uint8_t gamma[32]);
 
+/* ---- PLONK evaluations and opening proofs -------------------------------------------------- */
+/* Rounds 4 and 5 of a PLONK prover: the six evaluations at zeta and zeta w, the linearisation polynomial and the two
+ * opening proofs.  Nothing in the reference corresponds to them.  Encodings are the KZG section's: scalars are 32 bytes
+ * little-endian in STANDARD form and must be below r, which is checked before a device is touched; an error names the
+ * array and the lowest index; points are in the .ptau encoding, all-zero = infinity.  Pointers are the host's.  Conventions
+ * are round 3's: n = 2^log_n, w zk_fr_ntt's root for n, shifts (1, k1, k2), terms weighted 1, alpha, alpha^2, Z_H = X^n - 1,
+ * L1 = (X^n - 1) / (n (X - 1)).
+ * ZKHIP_OPEN_SEG=<coefficients a lane takes> (decimal, 1 to 4096, read at every call, 16 otherwise; anything else is an
+ * error of the call, "ZKHIP_OPEN_SEG: a number of coefficients per lane from 1 to 4096 expected") changes the shape of the
+ * kernels of this section and not one byte of any result.  The divisions are zk_fr_poly_divide's (ZKHIP_KZG_SEG). */
+
+/* ys[j] = p_j(zs[j]) for m polynomials of n coefficients (m x n x 32 bytes, one after another; zs, ys: m x 32 bytes): the
+ * convention of zk_kzg_open without the commitment, in two launches for all m (for every 65535 of them).  n = 0 is an
+ * error, "zk_fr_poly_eval: n is 0"; m = 0 is legal.  "zk_fr_poly_eval: n is not below 2^31",
+ * "zk_fr_poly_eval: polynomial 2, coefficient 5 is not below r", "zk_fr_poly_eval: z 3 is not below r".
+ * device -1: the current one. */
+int zk_fr_poly_eval(uint8_t *ys, const uint8_t *coeffs, uint64_t n, uint64_t m, const uint8_t *zs, int32_t device);
+
+/* What rounds 4 and 5 keep on the kzg's device: the eight circuit polynomials by coefficients (ZK_KZG_LAGRANGE: converted
+ * once by zk_fr_ntt's inverse transform; the view's `shift` is ignored), and room for a, b, c, z, the three parts of t, F
+ * and a quotient, max_coeffs rows each.  The object BORROWS the zk_kzg, as a key set borrows its keys: its points and the
+ * work buffers of its multiplication are used by zk_plonk_open; destroying the kzg before the object is the caller's error.
+ * Refused before anything is allocated:
+ *   "zk_plonk_opening_create: log_n 26 is outside 1 .. 25", "zk_plonk_opening_create: basis 7 is unknown",
+ *   "zk_plonk_opening_create: n + 6 = 70 exceeds the kzg's max_coeffs = 64" (F of a blinded proof has n + 6 coefficients),
+ *   "zk_plonk_opening_create: device 1 is not the kzg's device 0" (-1: the kzg's),
+ *   "zk_plonk_opening_create: qm 5 is not below r" (ql, qr, qm, qo, qc, s1, s2, s3),
+ *   "zk_plonk_opening_create: k1 is not below r" (k2 alike).
+ * Free HBM is checked before anything is allocated.  Calls on one object are serialised. */
+typedef struct zk_plonk_opening zk_plonk_opening;
+int zk_plonk_opening_create(zk_plonk_opening **out, zk_kzg *kzg, const zk_plonk_circuit_view *v, int32_t device);
+void zk_plonk_opening_destroy(zk_plonk_opening *o);
+/* Set plan->size = sizeof(zk_plonk_opening_plan) before the call (only `size` bytes are written). */
+typedef struct zk_plonk_opening_plan {
+    uint32_t size;
+    uint32_t log_n;
+    uint64_t device_bytes;        /* HBM the object holds (the kzg's is the kzg's) */
+    uint32_t seg;                 /* ZKHIP_OPEN_SEG in effect */
+    uint32_t last_launches;       /* kernel launches of the last zk_plonk_evaluate or zk_plonk_open on the object */
+    uint32_t pending;             /* 1: an evaluation is pending, zk_plonk_open may follow */
+    uint32_t reserved;
+} zk_plonk_opening_plan;
+int zk_plonk_opening_info(zk_plonk_opening *o, zk_plonk_opening_plan *plan);
+
+/* Round 4.  evals = a(zeta) | b(zeta) | c(zeta) | s1(zeta) | s2(zeta) | z(zeta w), 32 bytes each, in that order: two
+ * launches.  a, b, cc, z: the proof's polynomials by coefficients, a_len .. z_len of them, each 1 .. max_coeffs
+ * ("zk_plonk_evaluate: b_len 0 is outside 1 .. max_coeffs = 70"); "zk_plonk_evaluate: z 5 is not below r" (a, b, c, z),
+ * "zk_plonk_evaluate: zeta is not below r".  The four vectors, zeta and the six values stay in the object for round 5: an
+ * evaluation is then PENDING (a later zk_plonk_evaluate replaces it). */
+int zk_plonk_evaluate(zk_plonk_opening *o, uint8_t evals[6 * 32], const uint8_t *a, uint64_t a_len, const uint8_t *b, uint64_t b_len, const uint8_t *cc,
+                      uint64_t c_len, const uint8_t *z, uint64_t z_len, const uint8_t zeta[32]);
+
+/* Round 5.  With a' = a(zeta), b', c', s1', s2', z'w = z(zeta w) of the pending evaluation and t = t_lo + X^n t_mid + X^2n t_hi:
+ *   r(X) = a' b' qM + a' qL + b' qR + c' qO + PI(zeta) + qC
+ *        + alpha [ (a' + beta zeta + gamma)(b' + beta k1 zeta + gamma)(c' + beta k2 zeta + gamma) z(X)
+ *                - (a' + beta s1' + gamma)(b' + beta s2' + gamma)(c' + beta s3(X) + gamma) z'w ]
+ *        + alpha^2 (z(X) - 1) L1(zeta)
+ *        - Z_H(zeta) (t_lo + zeta^n t_mid + zeta^2n t_hi)
+ *   F(X)    = r + v a + v^2 b + v^3 c + v^4 s1 + v^5 s2
+ *   w_zeta       = commit( (F - F(zeta)) / (X - zeta) )
+ *   w_zeta_omega = commit( (z - z'w) / (X - zeta w) )
+ *   E       = v a' + v^2 b' + v^3 c' + v^4 s1' + v^5 s2'
+ *   r_zeta  = r(zeta) = F(zeta) - E
+ * F is one pass over 15 rows, the divisions are zk_fr_poly_divide's kernels (F(zeta) is the first one's remainder) and the
+ * multiplications zk_kzg_commit's over the kzg's resident points, under the kzg's mutex: F and both quotients never leave
+ * the device.  pi_zeta NULL: 0.  f NULL: F is not wanted; otherwise f receives max_coeffs rows, F's coefficients with zeros
+ * from *f_len on, *f_len the largest of the lengths of the rows F is made of (n + 6 with the usual blinding).  zeta^n = 1 is
+ * legal: Z_H(zeta) = 0, and L1(zeta) is 1 for zeta = 1, else 0.  The parts of t: 1 .. max_coeffs coefficients each,
+ * "zk_plonk_open: mid_len 0 is outside 1 .. max_coeffs = 70"; "zk_plonk_open: t_lo 5 is not below r" (t_lo, t_mid, t_hi),
+ * "zk_plonk_open: alpha is not below r" (beta, gamma, v, pi_zeta alike).  Without a pending evaluation the call is refused,
+ * "zk_plonk_open: no evaluation is pending: call zk_plonk_evaluate first"; a call whose arguments pass consumes it.
+ * r_zeta = 0 exactly when the round-3 identity holds at zeta; the call returns it and does not judge it.
+ * NOT checked: that r(zeta) = 0; that the t parts are the split of the round-3 quotient; that k1 and k2 give disjoint cosets.
+ * Blinding the parts of t is the caller's. */
+int zk_plonk_open(zk_plonk_opening *o, uint8_t w_zeta[64], uint8_t w_zeta_omega[64], uint8_t r_zeta[32], uint8_t *f, uint64_t *f_len, const uint8_t *t_lo,
+                  uint64_t lo_len, const uint8_t *t_mid, uint64_t mid_len, const uint8_t *t_hi, uint64_t hi_len, const uint8_t pi_zeta[32],
+                  const uint8_t alpha[32], const uint8_t beta[32], const uint8_t gamma[32], const uint8_t v[32]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,6 @@ from .zkverify import ZkeyVerifyReport, zkey_verify, zkey_verify_sizes      # no
 from .verify import VerificationKey, VerificationKeySet, pairing, pairing_last_path, groth16_verify, load_proof, load_public      # noqa: F401
 from .kzg import Kzg, fr_poly_divide                                  # noqa: F401
 from .frscan import fr_batch_inverse, fr_prefix_product, fr_grand_product, plonk_permutation_product      # noqa: F401
-from .plonk import PlonkCircuit, fr_coset_ntt                         # noqa: F401
+from .plonk import PlonkCircuit, PlonkOpening, fr_coset_ntt, fr_poly_eval        # noqa: F401
 from . import synth                                     # noqa: F401
 from .dist import gather_partials, ShardedChain                        # noqa: F401

@@ -25,35 +25,14 @@
 // L = C - y G + z pi (mulglv.hpp's mul_glv, one inversion).  k_kzg_pair: one squaring chain, both tables' lines evaluated at L
 // and at -pi, the final exponentiation.  No point of G2 comes from the caller, so there is no variable-Q loop and no
 // subgroup test per opening.
-#include <memory>
-#include <mutex>
-
-#include "hiputil.hpp"
-#include "devmem.hpp"
-#include "ptcheck.hpp"
-#include "pairing.hpp"
-#include "paircheck.hpp"
-#include "mulglv.hpp"
-#include "ptengine.hpp"
-#include "pairing_internal.hpp"
+#include "kzg_internal.hpp"
 #include "verify_batch_host.hpp"
 
 namespace {
 
-constexpr uint32_t DIV_WG = 256, DIV_WAVES = DIV_WG / 64;
-constexpr uint32_t DEFAULT_SEG = 16, MAX_SEG = 4096;   // the default: the best of profiles/kzg_timing.txt's sweep at 2^20
-constexpr uint32_t NO_LEVEL = ZK_KZG_NO_LAGRANGE;
-
 static_assert(sizeof(G1Affine) == 64 && sizeof(G2Affine) == 128 && sizeof(Fr) == 32 && sizeof(Line) == 192, "layout");
 
-// ---------------------------------------------------------------- device: division by X - z
-// The weights of one tier of the scan, Montgomery form
-struct DivPows {
-    Fr z;                                             // between neighbouring elements
-    Fr lane[6];                                       // z^(seg 2^k): between lanes 2^k apart
-    Fr wave;                                          // z^(64 seg): between waves
-};
-
+// ---------------------------------------------------------------- device: division by X - z (the tiers' weights: DivPows, kzg_internal.hpp)
 // sum_(k < cnt) c[k] z^k
 __device__ __forceinline__ Fr horner(const Fr *__restrict__ c, uint32_t cnt, const Fr &z) {
     Fr t = Fr::zero();
@@ -209,7 +188,7 @@ __global__ __launch_bounds__(64) void k_kzg_pair(uint8_t *verdict, const uint32_
 }
 
 // ---------------------------------------------------------------- host: division
-uint32_t seg_in_effect() { return (uint32_t)env_number("ZKHIP_KZG_SEG", DEFAULT_SEG, 1, MAX_SEG, "a number of coefficients per lane from 1 to 4096", ENV_LAX); }
+uint32_t seg_in_effect() { return kzg_seg_in_effect(); }
 
 DivPows make_pows(const Fr &base, uint64_t seg) {
     DivPows p;
@@ -223,23 +202,10 @@ DivPows make_pows(const Fr &base, uint64_t seg) {
     return p;
 }
 
-// the sums between the launches; grown, never shrunk
-struct DivWork {
-    DevBuf<Fr> wsum, gsum, behind;
-    DevBuf<DivPows> pows;                             // [0]: the coefficients' tiers, [1]: the carry pass's
-    DivPows h[2];                                     // their host image: it outlives the copy (every caller drains the stream before the next division)
-    void size(uint64_t groups) {
-        if (!pows.p) pows.alloc(2);
-        if (gsum.n >= groups) return;
-        wsum.alloc(groups * DIV_WAVES);
-        gsum.alloc(groups);
-        behind.alloc(groups);
-    }
-    size_t bytes() const { return wsum.bytes() + gsum.bytes() + behind.bytes() + pows.bytes(); }
-    static uint64_t groups_of(uint64_t n, uint32_t seg) { return (n + (uint64_t)DIV_WG * seg - 1) / ((uint64_t)DIV_WG * seg); }
-};
+}   // namespace
 
-// q[0, n - 1) and *y from c[0, n), n >= 1, all on the device, standard form; z in Montgomery form
+// q[0, n - 1) and *y from c[0, n), n >= 1, all on the device, standard form; z in Montgomery form (declared in
+// kzg_internal.hpp, with DivWork: plonkopen.hip divides too)
 void launch_divide(Fr *q, Fr *y, const Fr *c, uint64_t n, const Fr &z, uint32_t seg, DivWork &w, hipStream_t s) {
     const uint64_t groups = DivWork::groups_of(n, seg);
     if (groups >= (1ull << 31)) throw std::invalid_argument("division: too many coefficients for ZKHIP_KZG_SEG");
@@ -253,6 +219,8 @@ void launch_divide(Fr *q, Fr *y, const Fr *c, uint64_t n, const Fr &z, uint32_t 
     ZK_LAUNCH(k_div_apply, dim3((uint32_t)groups), dim3(DIV_WG), 0, s, q, y, c, w.wsum.p, w.behind.p, n, seg, w.pows.p);
     ZK_LAUNCH_OK("division by X - z");
 }
+
+namespace {
 
 void fr_poly_divide(uint8_t *q, uint8_t *y, const uint8_t *coeffs, uint64_t n, const uint8_t *z, int32_t device) {
     if (!n) throw std::invalid_argument("zk_fr_poly_divide: n is 0");
@@ -278,47 +246,7 @@ void fr_poly_divide(uint8_t *q, uint8_t *y, const uint8_t *coeffs, uint64_t n, c
     HIP_TRY(hipStreamSynchronize(s));
 }
 
-// ---------------------------------------------------------------- host: the multiplication over resident bases
-// operators.hip's msm_generic without the upload and the conversion of the bases: pts is already in the kernels' own form
-void msm_resident(DevMsm<Fq> &e, uint8_t out[64], const G1Affine *pts, const Fr *sc, uint64_t n, hipStream_t s) {
-    e.size(n);
-    e.sb.run(sc, s);
-    launch_msm_accum_g1(e.buckets.p, e.sb.offsets.p, e.sb.entries.p, pts, 0, 0, e.sb.total_buckets(), e.emax, e.ws.p, e.wkey.p, e.wflag.p, s);
-    launch_msm_reduce_g1(e.wsum.p, e.scratch.p, e.buckets.p, 1, e.sb.plan, s);
-    HIP_TRY(hipMemcpyAsync(e.w.data(), e.wsum.p, e.w.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    HostTail::combine_windows_g1(e.w.data(), e.sb.plan.sets, e.sb.plan.c, e.rc, out);
-}
-
-size_t msm_bytes(const DevMsm<Fq> &e) {
-    return e.sb.bytes() + e.buckets.bytes() + e.scratch.bytes() + e.ws.bytes() + e.wsum.bytes() + e.wkey.bytes() + e.wflag.bytes();
-}
-
-}   // namespace
-
-// ---------------------------------------------------------------- the object
-struct zk_kzg {
-    int device = 0;
-    uint32_t power = 0, lag_log = NO_LEVEL;
-    uint64_t max_coeffs = 0, lag_n = 0;
-    std::mutex mu;                                    // calls on one object are serialised
-    std::unique_ptr<Stream> st;
-    Consts kc;
-    DevBuf<G1Affine> tau, lag;                        // section 2's first max_coeffs points, level lag_log of section 12: the bucket kernels' form
-    DevBuf<Line> tab;                                 // the G2 generator's lines, then [tau]G2's
-    DevBuf<Fr> sc, quot, yv;                          // a polynomial, its quotient, its value
-    DivWork div;
-    DevMsm<Fq> msm;                                   // commit and open; sized for max_coeffs when the object is made
-    DevMsm<Fq> bmsm;                                  // verify_batch's three sums over m points: made by the first such call
-    uint8_t g1[64];                                   // the generator, the file's form
-    uint32_t last_launches = 0;
-    size_t bytes() const {
-        return tau.bytes() + lag.bytes() + tab.bytes() + sc.bytes() + quot.bytes() + yv.bytes() + div.bytes() + msm_bytes(msm) + msm_bytes(bmsm) +
-               sizeof(PairConsts);
-    }
-};
-
-namespace {
+// the multiplication over resident bases (msm_resident) and the object (struct zk_kzg): kzg_internal.hpp
 
 // counts the launches of one call into the object
 struct LaunchCount {

@@ -183,6 +183,11 @@ class zk_plonk_circuit_plan(C.Structure):
                 ("last_launches", C.c_uint32)]
 
 
+class zk_plonk_opening_plan(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("log_n", C.c_uint32), ("device_bytes", C.c_uint64), ("seg", C.c_uint32), ("last_launches", C.c_uint32),
+                ("pending", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -240,7 +245,8 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_g1_mul_vec", "zk_g2_mul_vec", "zk_g1_power_scale", "zk_g2_power_scale", "zk_glv_split", "zk_ptau_contribute_sizes", "zk_ptau_contribute",
            "zk_fr_poly_divide", "zk_kzg_create", "zk_kzg_destroy", "zk_kzg_info", "zk_kzg_commit", "zk_kzg_open", "zk_kzg_verify", "zk_kzg_verify_batch",
            "zk_fr_batch_inverse", "zk_fr_prefix_product", "zk_fr_grand_product", "zk_plonk_permutation_product", "zk_msm_sort",
-           "zk_fr_coset_ntt", "zk_plonk_circuit_create", "zk_plonk_circuit_destroy", "zk_plonk_circuit_info", "zk_plonk_quotient"]
+           "zk_fr_coset_ntt", "zk_plonk_circuit_create", "zk_plonk_circuit_destroy", "zk_plonk_circuit_info", "zk_plonk_quotient",
+           "zk_fr_poly_eval", "zk_plonk_opening_create", "zk_plonk_opening_destroy", "zk_plonk_opening_info", "zk_plonk_evaluate", "zk_plonk_open"]
 ZK_SCAN_EXCLUSIVE = 1
 ZK_KZG_MONOMIAL, ZK_KZG_LAGRANGE, ZK_KZG_NO_LAGRANGE = 0, 1, 0xffffffff
 ZK_SCALE_PLAN_MAX = 130
@@ -408,6 +414,15 @@ def load_library():
         lib.zk_plonk_circuit_info.argtypes = [C.c_void_p, C.POINTER(zk_plonk_circuit_plan)]
         lib.zk_plonk_quotient.argtypes = [C.c_void_p, u8p, C.POINTER(C.c_uint64), u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p,
                                           u8p, u8p, u8p]
+    if hasattr(lib, "zk_plonk_open"):
+        lib.zk_fr_poly_eval.argtypes = [u8p, u8p, C.c_uint64, C.c_uint64, u8p, C.c_int32]
+        lib.zk_plonk_opening_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(zk_plonk_circuit_view), C.c_int32]
+        lib.zk_plonk_opening_destroy.argtypes = [C.c_void_p]
+        lib.zk_plonk_opening_destroy.restype = None
+        lib.zk_plonk_opening_info.argtypes = [C.c_void_p, C.POINTER(zk_plonk_opening_plan)]
+        lib.zk_plonk_evaluate.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p]
+        lib.zk_plonk_open.argtypes = [C.c_void_p, u8p, u8p, u8p, u8p, C.POINTER(C.c_uint64), u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p,
+                                      u8p, u8p, u8p, u8p]
     _LIB = lib
     return lib
 

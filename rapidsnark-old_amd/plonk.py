@@ -50,6 +50,134 @@ def fr_coset_ntt(values, log_m=None, shift=None, inverse=False, device=-1):
     return out
 
 
+def _circuit_rows(vectors):
+    """the eight circuit vectors -> (rows, n, log_n); one length, a power of two, log_n in range"""
+    vecs = [_scalars(v, name) for name, v in zip(_CIRCUIT, vectors)]
+    n = vecs[0].size // 32
+    for name, v in zip(_CIRCUIT, vecs):
+        if v.size != n * 32:
+            raise ValueError("%s has %d rows, ql has %d: the eight circuit vectors must have one length" % (name, v.size // 32, n))
+    if n < 1 or n & (n - 1):
+        raise ValueError("n = %d is not a power of two" % n)
+    log_n = n.bit_length() - 1
+    if not MIN_LOG_N <= log_n <= MAX_LOG_N:
+        raise ValueError("log_n %d is outside %d .. %d" % (log_n, MIN_LOG_N, MAX_LOG_N))
+    return vecs, n, log_n
+
+
+def fr_poly_eval(coeffs, zs, device=-1):
+    """a list of m ints p_k(z_k) (zk_fr_poly_eval): coeffs one polynomial (ints, or a flat byte array) or several of one
+    length (a sequence of int sequences, or a 2-d uint8 array), zs one point each.  Nothing is committed to."""
+    from .kzg import _polys
+    a, n, m = _polys(coeffs, "coeffs")
+    zb = _scalars([zs] if isinstance(zs, (int, np.integer)) else zs, "zs")
+    if zb.size != m * 32:
+        raise ValueError("zs: %d values for %d polynomials" % (zb.size // 32, m))
+    ys = np.zeros(m * 32, dtype=np.uint8)
+    L.check(L.load_library().zk_fr_poly_eval(L._ptr(ys), L._ptr(a), n, m, L._ptr(zb), device))
+    yb = ys.tobytes()
+    return [int.from_bytes(yb[i * 32:(i + 1) * 32], "little") for i in range(m)]
+
+
+class PlonkOpening:
+    """Rounds 4 and 5 of a three-column PLONK proof on a Kzg's device (zk_plonk_opening): the eight circuit polynomials by
+    coefficients, resident, and room for a proof's vectors.  basis "lagrange": values at w^j, converted once.  The object
+    keeps a reference to the Kzg, whose points and multiplication it uses.  It is NOT checked that 1, k1, k2 name disjoint
+    cosets."""
+
+    def __init__(self, kzg, ql, qr, qm, qo, qc, s1, s2, s3, k1, k2, basis="monomial"):
+        from .kzg import Kzg
+        if not isinstance(kzg, Kzg):
+            raise TypeError("a Kzg expected")
+        if basis not in _BASES:
+            raise ValueError("basis %r is unknown: 'monomial' or 'lagrange'" % (basis,))
+        vecs, n, log_n = _circuit_rows((ql, qr, qm, qo, qc, s1, s2, s3))
+        kb1, kb2 = _one(k1, "k1"), _one(k2, "k2")
+        if n + 6 > kzg.max_coeffs:
+            raise ValueError("n + 6 = %d exceeds the kzg's max_coeffs = %d" % (n + 6, kzg.max_coeffs))
+        self._h = C.c_void_p()
+        self.kzg, self.n, self.log_n, self.max_coeffs, self.device = kzg, n, log_n, kzg.max_coeffs, kzg.device
+        kh = kzg._handle()
+        v = L.zk_plonk_circuit_view()
+        v.log_n, v.basis = log_n, _BASES[basis]
+        for name, a in zip(_CIRCUIT, vecs):
+            setattr(v, name, a.ctypes.data)
+        C.memmove(v.k1, kb1.ctypes.data, 32)
+        C.memmove(v.k2, kb2.ctypes.data, 32)
+        v.shift = None
+        L.check(L.load_library().zk_plonk_opening_create(C.byref(self._h), kh, C.byref(v), -1))
+
+    def _handle(self):
+        if not self._h:
+            raise L.ZkHipError("the PlonkOpening object is closed")
+        self.kzg._handle()                              # a closed Kzg: its points are gone
+        return self._h
+
+    def _vectors(self, names, lens, vectors):
+        rows = [_scalars(v, name) for name, v in zip(names, vectors)]
+        for name, r in zip(lens, rows):
+            if not 1 <= r.size // 32 <= self.max_coeffs:
+                raise ValueError("%s %d is outside 1 .. max_coeffs = %d" % (name, r.size // 32, self.max_coeffs))
+        return rows
+
+    def evaluate(self, a, b, c, z, zeta):
+        """[a(zeta), b(zeta), c(zeta), s1(zeta), s2(zeta), z(zeta w)] as ints (zk_plonk_evaluate).  The vectors, zeta and the
+        values stay in the object for open()."""
+        rows = self._vectors("abcz", ("a_len", "b_len", "c_len", "z_len"), (a, b, c, z))
+        zb = _one(zeta, "zeta")
+        h = self._handle()
+        ev = np.zeros(6 * 32, dtype=np.uint8)
+        args = []
+        for r in rows:
+            args += [L._ptr(r), r.size // 32]
+        L.check(L.load_library().zk_plonk_evaluate(h, L._ptr(ev), *args, L._ptr(zb)))
+        eb = ev.tobytes()
+        return [int.from_bytes(eb[i * 32:(i + 1) * 32], "little") for i in range(6)]
+
+    def open(self, t_lo, t_mid, t_hi, alpha, beta, gamma, v, pi_zeta=0, want_f=False):
+        """(W_zeta, W_zeta_omega, r_zeta[, F]) (zk_plonk_open): the two opening proofs (numpy uint8 [64] each), r(zeta) as an
+        int (0 exactly when the round-3 identity holds at zeta; NOT judged here) and, when want_f, F's coefficients (numpy
+        uint8 [f_len * 32]).  It consumes the evaluation evaluate() left."""
+        rows = self._vectors(("t_lo", "t_mid", "t_hi"), ("lo_len", "mid_len", "hi_len"), (t_lo, t_mid, t_hi))
+        sc = [_one(x, name) for name, x in zip(("alpha", "beta", "gamma", "v", "pi_zeta"), (alpha, beta, gamma, v, pi_zeta))]
+        h = self._handle()
+        wz, wzw, rz = np.zeros(64, dtype=np.uint8), np.zeros(64, dtype=np.uint8), np.zeros(32, dtype=np.uint8)
+        f = np.zeros(self.max_coeffs * 32, dtype=np.uint8) if want_f else None
+        f_len = C.c_uint64(0)
+        args = []
+        for r in rows:
+            args += [L._ptr(r), r.size // 32]
+        L.check(L.load_library().zk_plonk_open(h, L._ptr(wz), L._ptr(wzw), L._ptr(rz), L._ptr(f) if want_f else None, C.byref(f_len), *args,
+                                               L._ptr(sc[4]), L._ptr(sc[0]), L._ptr(sc[1]), L._ptr(sc[2]), L._ptr(sc[3])))
+        out = (wz, wzw, int.from_bytes(rz.tobytes(), "little"))
+        return out + (f[:int(f_len.value) * 32],) if want_f else out
+
+    def info(self):
+        """zk_plonk_opening_info -> dict: log_n, device_bytes, seg (ZKHIP_OPEN_SEG in effect), last_launches, pending"""
+        h = self._handle()
+        plan = L.zk_plonk_opening_plan()
+        plan.size = C.sizeof(plan)
+        L.check(L.load_library().zk_plonk_opening_info(h, C.byref(plan)))
+        return {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name not in ("size", "reserved")}
+
+    def close(self):
+        if self._h:
+            L.load_library().zk_plonk_opening_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PlonkCircuit:
     """What does not change from proof to proof of a three-column PLONK circuit, on a device (zk_plonk_circuit): the eight
     polynomials extended to the coset shift * (4n-th roots of unity).  basis "monomial": coefficients; "lagrange": values at
@@ -58,16 +186,7 @@ class PlonkCircuit:
     def __init__(self, ql, qr, qm, qo, qc, s1, s2, s3, k1, k2, basis="monomial", shift=None, device=-1):
         if basis not in _BASES:
             raise ValueError("basis %r is unknown: 'monomial' or 'lagrange'" % (basis,))
-        vecs = [_scalars(v, name) for name, v in zip(_CIRCUIT, (ql, qr, qm, qo, qc, s1, s2, s3))]
-        n = vecs[0].size // 32
-        for name, v in zip(_CIRCUIT, vecs):
-            if v.size != n * 32:
-                raise ValueError("%s has %d rows, ql has %d: the eight circuit vectors must have one length" % (name, v.size // 32, n))
-        if n < 1 or n & (n - 1):
-            raise ValueError("n = %d is not a power of two" % n)
-        log_n = n.bit_length() - 1
-        if not MIN_LOG_N <= log_n <= MAX_LOG_N:
-            raise ValueError("log_n %d is outside %d .. %d" % (log_n, MIN_LOG_N, MAX_LOG_N))
+        vecs, n, log_n = _circuit_rows((ql, qr, qm, qo, qc, s1, s2, s3))
         kb1, kb2 = _one(k1, "k1"), _one(k2, "k2")
         g = _shift(shift)
         if g is not None and pow(int.from_bytes(g.tobytes(), "little") % R_MOD, 4 * n, R_MOD) == 1:
