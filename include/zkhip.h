@@ -1107,6 +1107,109 @@ int zk_plonk_open(zk_plonk_opening *o, uint8_t w_zeta[64], uint8_t w_zeta_omega[
                   uint64_t lo_len, const uint8_t *t_mid, uint64_t mid_len, const uint8_t *t_hi, uint64_t hi_len, const uint8_t pi_zeta[32],
                   const uint8_t alpha[32], const uint8_t beta[32], const uint8_t gamma[32], const uint8_t v[32]);
 
+/* ---- PLONK prover and verifier ------------------------------------------------------------- */
+/* The five rounds above chained on the device, the Fiat-Shamir transcript that draws their challenges, and the verifier
+ * of the proofs they make.  Nothing in the reference corresponds to them; the counterpart is snarkjs's PLONK prover and
+ * verifier for a three-column circuit.  Encodings are the sections' above: scalars are 32 bytes little-endian in STANDARD
+ * form and must be below r; points are in the .ptau encoding (affine, Montgomery, 64 bytes, all-zero = infinity).
+ * Conventions are rounds 2 to 5's: n = 2^log_n, w zk_fr_ntt's root for n, shifts (1, k1, k2), Z[0] = 1, terms weighted
+ * 1, alpha, alpha^2, Z_H = X^n - 1, L1 = (X^n - 1) / (n (X - 1)).  The knobs of the rounds (ZKHIP_SCAN_SEG, ZKHIP_QUOT_SEG,
+ * ZKHIP_OPEN_SEG, ZKHIP_KZG_SEG) shape the kernels of a proof and change not one byte of it; the prover's own kernels (the
+ * wire gather, the blinding, the split of t) follow ZKHIP_QUOT_SEG.
+ *
+ * The transcript.  The hash is Keccak-256 with the ORIGINAL padding byte 0x01 (Ethereum's), not SHA-3's 0x06.  What is
+ * hashed: a scalar as 32 bytes BIG-endian, standard form; a point as x | y, 32 bytes big-endian standard form each,
+ * infinity as 64 zero bytes.  A challenge is the digest read as a big-endian integer, reduced mod r.
+ *   beta  = H([qM], [qL], [qR], [qO], [qC], [s1], [s2], [s3], publics[0 .. n_public), [a], [b], [c])
+ *   gamma = H(beta)
+ *   alpha = H(beta, gamma, [z])
+ *   zeta  = H(alpha, [t_lo], [t_mid], [t_hi])
+ *   v     = H(zeta, a', b', c', s1', s2', z'w)
+ *   u     = H([W_zeta], [W_zeta_omega])
+ * The order follows snarkjs 0.7's; no file made by snarkjs was at hand, so parity with snarkjs is UNPINNED. */
+
+/* out32 = Keccak-256(data[0 .. len)).  No device.  Keccak-256("") = c5d24601 86f7233c 927e7db2 dcc703c0 e500b653 ca82273b
+ * 7bfad804 5d85a470; Keccak-256("abc") = 4e03657a ea45a94f c7d47ba8 26c8d667 c0d1e6e3 3a64a036 ec44f58f a12d6c45. */
+int zk_keccak256(uint8_t out32[32], const uint8_t *data, uint64_t len);
+
+#define ZK_PLONK_PROOF_BYTES 768   /* [a] [b] [c] [z] [t_lo] [t_mid] [t_hi] [W_zeta] [W_zeta_omega], 64 bytes each, then
+                                    * a' b' c' s1' s2' z'w, 32 bytes each */
+#define ZK_PLONK_BLINDS 11
+
+/* What a verifier needs.  The commitments in the transcript's order. */
+typedef struct zk_plonk_vkey {
+    uint32_t size;                /* set to sizeof(zk_plonk_vkey) before zk_plonk_prover_vkey */
+    uint32_t log_n;
+    uint64_t n_public;
+    uint8_t k1[32], k2[32];
+    uint8_t qm[64], ql[64], qr[64], qo[64], qc[64], s1[64], s2[64], s3[64];
+    uint8_t tau_g2[128];          /* [tau] G2, the .ptau encoding */
+} zk_plonk_vkey;
+
+/* A prover for one circuit on the kzg's device.  view: the eight vectors as zk_plonk_circuit_create and
+ * zk_plonk_opening_create take them.  a_map, b_map, c_map: n indices each, row i's wires are witness[a_map[i]],
+ * witness[b_map[i]], witness[c_map[i]].  The object BORROWS the kzg as a zk_plonk_opening does, and keeps on its device: the
+ * maps, s1 .. s3 by values (round 2), what a zk_plonk_circuit keeps for round 3 (the extensions), what a zk_plonk_opening
+ * keeps for rounds 4 and 5 (the coefficients), and room for a witness and a proof's vectors.  It makes the eight commitments once.
+ * 3 <= log_n <= 25 (the usual blinding needs 3n + 6 <= 4n), n + 6 <= the kzg's max_coeffs, n_public <= n, n_witness >= 1.
+ * Refused before a device is touched:
+ *   "zk_plonk_prover_create: log_n 2 is outside 3 .. 25", "zk_plonk_prover_create: basis 7 is unknown",
+ *   "zk_plonk_prover_create: n + 6 = 70 exceeds the kzg's max_coeffs = 64",
+ *   "zk_plonk_prover_create: n_public 9 exceeds n = 8", "zk_plonk_prover_create: n_witness is 0",
+ *   "zk_plonk_prover_create: device 1 is not the kzg's device 0" (-1: the kzg's),
+ *   "zk_plonk_prover_create: b_map 5 is 12, not below n_witness = 12" (a_map, b_map, c_map; the lowest row),
+ *   "zk_plonk_prover_create: qm 5 is not below r" (ql, qr, qm, qo, qc, s1, s2, s3), "zk_plonk_prover_create: k1 is not below r"
+ *   (k2, shift alike), "zk_plonk_prover_create: shift is zero", "zk_plonk_prover_create: shift^(4n) is 1: Z_H vanishes on the
+ *   coset".  Free HBM is checked before anything is allocated.  Calls on one object are serialised. */
+typedef struct zk_plonk_prover zk_plonk_prover;
+int zk_plonk_prover_create(zk_plonk_prover **out, zk_kzg *kzg, const zk_plonk_circuit_view *view, const uint32_t *a_map, const uint32_t *b_map,
+                           const uint32_t *c_map, uint64_t n_witness, uint64_t n_public, int32_t device);
+void zk_plonk_prover_destroy(zk_plonk_prover *p);
+int zk_plonk_prover_vkey(zk_plonk_prover *p, zk_plonk_vkey *vk);
+/* Set plan->size = sizeof(zk_plonk_prover_plan) before the call (only `size` bytes are written). */
+typedef struct zk_plonk_prover_plan {
+    uint32_t size;
+    uint32_t log_n;
+    uint64_t n_witness, n_public;
+    uint64_t device_bytes;        /* HBM the object holds (the kzg's is the kzg's) */
+    uint32_t scan_seg, quot_seg, open_seg, kzg_seg;   /* the knobs in effect */
+    uint32_t last_launches;       /* kernel launches of the last zk_plonk_prove on the object (of the creation before it) */
+    uint32_t round_launches[5];   /* of them, round 1 .. round 5 (the multiplications of a round's commitments with it).  Both
+                                   * counts are differences of the library's one process-wide launch counter, as every *_info's
+                                   * last_launches: launches other threads make meanwhile, on any object, are counted in */
+} zk_plonk_prover_plan;
+int zk_plonk_prover_info(zk_plonk_prover *p, zk_plonk_prover_plan *plan);
+
+/* proof (ZK_PLONK_PROOF_BYTES) from a witness of n_witness scalars.  publics: n_public scalars; PI takes the value
+ * -publics[i] at w^i and 0 elsewhere (NULL with n_public = 0).  blind: NULL, or ZK_PLONK_BLINDS scalars b1 .. b11 (FOR TESTS:
+ * a proof with known blinds hides nothing); with NULL they are drawn from the OS generator (getrandom).  Any value below r is
+ * legal, 0 included.  The usual blinding:
+ *   a += (b1 X + b2) Z_H,  b += (b3 X + b4) Z_H,  c += (b5 X + b6) Z_H,  z += (b7 X^2 + b8 X + b9) Z_H,
+ *   t_lo + b10 X^n,  t_mid - b10 + b11 X^n,  t_hi - b11.
+ * The witness is uploaded once; after that only commitments, the six values, `last`, t's length, r(zeta) and the challenges
+ * cross PCIe.  "zk_plonk_prove: witness 5 is not below r" (publics, blind alike), refused before a device is touched.
+ * A bad witness is refused and NO proof byte is written: "zk_plonk_prove: the copy constraints do not hold" (round 2's
+ * last != 1), "zk_plonk_prove: the witness does not satisfy the gates" (t has more than 3n + 6 coefficients, or r(zeta) != 0),
+ * "zk_plonk_prove: a denominator of the permutation product is zero" (probability about 3n / r over beta, gamma). */
+int zk_plonk_prove(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *witness, const uint8_t *publics, const uint8_t *blind);
+
+/* *verdict = ZK_VERIFY_OK / ZK_VERIFY_INVALID / ZK_VERIFY_MALFORMED for one proof under vk with n_public = vk->n_public
+ * publics.  MALFORMED: a point of the proof that is not on the curve (or a coordinate not below q), or one of the six values
+ * or a public input not below r.  Otherwise the transcript is recomputed, u included, and with
+ *   r0 = alpha (a' + beta s1' + gamma)(b' + beta s2' + gamma)(c' + gamma) z'w + alpha^2 L1(zeta) - PI(zeta)
+ *   D  = a' b' [qM] + a' [qL] + b' [qR] + c' [qO] + [qC]
+ *      + (alpha (a' + beta zeta + gamma)(b' + beta k1 zeta + gamma)(c' + beta k2 zeta + gamma) + alpha^2 L1(zeta) + u) [z]
+ *      - alpha (a' + beta s1' + gamma)(b' + beta s2' + gamma) beta z'w [s3] - Z_H(zeta) ([t_lo] + zeta^n [t_mid] + zeta^2n [t_hi])
+ *   F  = D + v [a] + v^2 [b] + v^3 [c] + v^4 [s1] + v^5 [s2]
+ *   E  = (r0 + v a' + v^2 b' + v^3 c' + v^4 s1' + v^5 s2' + u z'w) [1]
+ * the verdict is OK iff e(W_zeta + u W_zeta_omega, [tau]G2) = e(zeta W_zeta + u zeta w W_zeta_omega + F - E, G2).  The
+ * multiplications are the host's (zk_g1_mul, 18 of them), the pairing product one lane of zk_kzg_verify's kernel over the
+ * kzg's line tables: "zk_plonk_verify: the key's [tau]G2 is not the kzg's".  A bad KEY is an error of the call, not a verdict:
+ * "zk_plonk_verify: vk->size is not sizeof(zk_plonk_vkey)", "zk_plonk_verify: log_n 2 is outside 3 .. 25",
+ * "zk_plonk_verify: n_public 9 exceeds n = 8", "zk_plonk_verify: k1 is not below r" (k2 alike),
+ * "zk_plonk_verify: a commitment of the key is not a point of the curve". */
+int zk_plonk_verify(zk_kzg *kzg, const zk_plonk_vkey *vk, const uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *publics, uint8_t *verdict);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@
 #include "hiputil.hpp"
 #include "devmem.hpp"
 #include "ptengine.hpp"
+#include "plonk_internal.hpp"
 
 namespace {
 
@@ -626,6 +627,23 @@ void plonk_permutation_product(uint8_t *z, uint8_t *last, const uint8_t *wires, 
 }
 
 }   // namespace
+
+// ---------------------------------------------------------------- what plonkprove.hip chains (plonk_internal.hpp)
+struct PlonkPerm {
+    ScanWork w;
+};
+PlonkPerm *plonk_perm_new() { return new PlonkPerm(); }
+void plonk_perm_free(PlonkPerm *p) { delete p; }
+uint32_t plonk_perm_seg() { return seg_in_effect(); }
+uint64_t plonk_perm_need_bytes(uint64_t n) { return ScanWork::bytes_of(ScanWork::groups_of(n, 1)); }
+size_t plonk_perm_bytes(const PlonkPerm *p) { return p->w.groups ? ScanWork::bytes_of(p->w.groups) : 0; }
+bool plonk_perm_dev(PlonkPerm *p, Fr *z, uint8_t last[32], const Fr *wires, const Fr *sigmas, const Fr *shifts, uint32_t log_n, const uint8_t beta[32],
+                    const uint8_t gamma[32], hipStream_t s) {
+    const ScanEnd end = permutation_product_dev(z, wires, sigmas, shifts, 3, log_n, beta, gamma, seg_in_effect(), p->w, s);
+    if (end.den_zero) return false;
+    memcpy(last, end.last.v, 32);
+    return true;
+}
 
 extern "C" {
 

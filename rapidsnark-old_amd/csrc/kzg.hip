@@ -303,6 +303,7 @@ zk_kzg *kzg_create(const zk_kzg_view *v, uint64_t max_coeffs, uint32_t lagrange_
     k->lag_log = lagrange_log_n;
     k->lag_n = lag_n;
     memcpy(k->g1, g1.b, sizeof k->g1);
+    memcpy(k->g2tau, static_cast<const uint8_t *>(v->tau_g2) + sizeof(G2Affine), sizeof k->g2tau);
     DeviceGuard g(k->device);
     const uint64_t nsc = max_coeffs > lag_n ? max_coeffs : lag_n;
     need_hbm("zk_kzg_create", (max_coeffs + lag_n) * sizeof(G1Affine) + 2 * nsc * sizeof(Fr) + DevMsm<Fq>::bytes(nsc) +
@@ -529,6 +530,32 @@ void kzg_verify_batch(zk_kzg *k, const uint8_t *commitments, const uint8_t *zs, 
 }
 
 }   // namespace
+
+// ZK_VERIFY_OK iff e(L, G2) = e(pi, [tau]G2), one lane of k_kzg_pair over the object's line tables (plonk_internal.hpp: the
+// last step of zk_plonk_verify).  L and pi are points of the curve in the file's form: the caller's check
+uint8_t kzg_pair_one(zk_kzg *k, const uint8_t L[64], const uint8_t pi[64]) {
+    std::lock_guard<std::mutex> lock(k->mu);
+    DeviceGuard g(k->device);
+    LaunchCount lc(k);
+    hipStream_t s = k->st->s;
+    DevBuf<G1Affine> dl, dp;
+    DevBuf<uint32_t> st;
+    DevBuf<uint8_t> dv;
+    dl.alloc(1);
+    dp.alloc(1);
+    st.alloc(1);
+    dv.alloc(1);
+    const uint32_t ok = ST_OK;
+    uint8_t verdict = ZK_VERIFY_INVALID;
+    HIP_TRY(hipMemcpyAsync(dl.p, L, 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dp.p, pi, 64, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(st.p, &ok, 4, hipMemcpyHostToDevice, s));
+    ZK_LAUNCH(k_kzg_pair, dim3(1), dim3(64), 0, s, dv.p, st.p, dl.p, dp.p, k->tab.p, (uint64_t)1, k->kc.k.p);
+    ZK_LAUNCH_OK("pairing check");
+    HIP_TRY(hipMemcpyAsync(&verdict, dv.p, 1, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return verdict;
+}
 
 extern "C" {
 

@@ -79,6 +79,7 @@ struct zk_kzg {
     DevMsm<Fq> msm;                                   // commit and open; sized for max_coeffs when the object is made
     DevMsm<Fq> bmsm;                                  // verify_batch's three sums over m points: made by the first such call
     uint8_t g1[64];                                   // the generator, the file's form
+    uint8_t g2tau[128];                               // [tau]G2, the file's form: what a PLONK key names
     uint32_t last_launches = 0;
     size_t bytes() const {
         return tau.bytes() + lag.bytes() + tab.bytes() + sc.bytes() + quot.bytes() + yv.bytes() + div.bytes() + msm_bytes(msm) + msm_bytes(bmsm) +

@@ -1,0 +1,55 @@
+// What plonkprove.hip chains (the five rounds of a PLONK proof on one stream, nothing per-row crossing PCIe): the device-
+// pointer cores of frscan.hip (round 2), plonkquot.hip (round 3) and plonkopen.hip (rounds 4 and 5), and kzg.hip's one-lane
+// pairing check.  Each core stays in its unit with its kernels; the public entries of those units are thin wrappers over
+// the same cores (upload, core, download).  Every core reads its unit's own knob (ZKHIP_SCAN_SEG, _QUOT_SEG, _OPEN_SEG).
+#pragma once
+#include "kzg_internal.hpp"
+
+// ---------------------------------------------------------------- kzg.hip
+// ZK_VERIFY_OK iff e(L, G2) = e(pi, [tau]G2), else ZK_VERIFY_INVALID; L, pi: points of the curve, the file's form
+uint8_t kzg_pair_one(zk_kzg *k, const uint8_t L[64], const uint8_t pi[64]);
+
+// ---------------------------------------------------------------- frscan.hip
+struct PlonkPerm;                                     // the work buffers of the scan
+PlonkPerm *plonk_perm_new();
+void plonk_perm_free(PlonkPerm *p);
+uint32_t plonk_perm_seg();
+uint64_t plonk_perm_need_bytes(uint64_t n);
+size_t plonk_perm_bytes(const PlonkPerm *p);
+// z[0, n) and last of zk_plonk_permutation_product for three columns, all vectors on the device, standard form; beta,
+// gamma: standard, host.  false: a denominator is zero and z was not written.  The stream is drained once inside
+bool plonk_perm_dev(PlonkPerm *p, Fr *z, uint8_t last[32], const Fr *wires, const Fr *sigmas, const Fr *shifts, uint32_t log_n, const uint8_t beta[32],
+                    const uint8_t gamma[32], hipStream_t s);
+
+// ---------------------------------------------------------------- plonkquot.hip
+constexpr uint32_t PLONK_ROWS = 5;                    // a, b, c, z, pi
+uint32_t plonk_quot_seg();
+uint64_t plonk_circuit_need_bytes(uint32_t log_n);
+size_t plonk_circuit_bytes(const zk_plonk_circuit *c);
+// where round 3 reads its rows: a | b | c | z (| pi) back to back, lens[] standard rows each (20n rows of room)
+Fr *plonk_circuit_rows(zk_plonk_circuit *c);
+// zk_plonk_quotient without the staging: t's 4n coefficients (standard, zeros from *t_len on) stay on the device, where the
+// return value points, until the object's next call
+const Fr *plonk_circuit_quotient_dev(zk_plonk_circuit *c, const uint64_t lens[PLONK_ROWS], uint32_t vecs, const Fr &alpha, const Fr &beta, const Fr &gamma,
+                                     uint64_t *t_len, hipStream_t s);
+// values at w^i -> coefficients for `batch` <= 5 vectors of n standard rows, `in` n apart, out[v] n rows each: one load, one
+// batched inverse transform of size n, a store a vector.  Works in the vectors of a quotient call; `in` and out[] lie elsewhere.
+// The tables of size n are made by plonk_circuit_prepare_interpolate, or by the first call
+void plonk_circuit_prepare_interpolate(zk_plonk_circuit *c, hipStream_t s);
+void plonk_circuit_interpolate_dev(zk_plonk_circuit *c, Fr *const out[], const Fr *in, uint32_t batch, hipStream_t s);
+
+// ---------------------------------------------------------------- plonkopen.hip
+uint32_t plonk_open_seg();
+uint64_t plonk_opening_need_bytes(uint64_t n, uint64_t cap, bool lagrange);
+size_t plonk_opening_bytes(const zk_plonk_opening *o);
+Fr *plonk_opening_wit(zk_plonk_opening *o, uint32_t j);          // a, b, c, z: max_coeffs rows each
+Fr *plonk_opening_part(zk_plonk_opening *o, uint32_t j);         // t_lo, t_mid, t_hi: max_coeffs rows each
+const Fr *plonk_opening_circ(const zk_plonk_opening *o, uint32_t j);   // the view's order, n coefficients each
+void plonk_opening_clear(zk_plonk_opening *o, hipStream_t s);    // zeros in every row of a proof: a shorter vector reads as padded
+// zk_plonk_evaluate and zk_plonk_open over the rows already in the object: len[] of a, b, c, z and tlen[] of the parts of t.
+// The scalars are Montgomery.  Both multiplications of plonk_opening_open_dev run over one row more than their quotient has (as
+// many rows as the polynomial divided), which the call zeroes after each division: with every len[] equal, all multiplications of
+// a proof have one size
+void plonk_opening_evaluate_dev(zk_plonk_opening *o, uint8_t evals[6 * 32], const uint64_t len[4], const Fr &zeta, hipStream_t s);
+void plonk_opening_open_dev(zk_plonk_opening *o, uint8_t w_zeta[64], uint8_t w_zeta_omega[64], uint8_t r_zeta[32], uint8_t *f, uint64_t *f_len,
+                            const uint64_t tlen[3], const Fr &pi_zeta, const Fr &alpha, const Fr &beta, const Fr &gamma, const Fr &v, hipStream_t s);

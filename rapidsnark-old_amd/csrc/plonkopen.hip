@@ -23,7 +23,7 @@
 // Form: field.hpp's 8 x 32-bit Fr, as kzg.hip's division.  Every vector stays in STANDARD form: the scalars and the powers
 // are Montgomery, and a Montgomery product of a standard value with such a scalar is standard, so F is what the division
 // reads and the quotient what the sort of the multiplication reads.  One operand term per reduction: no ranges to state.
-#include "kzg_internal.hpp"
+#include "plonk_internal.hpp"
 
 namespace {
 
@@ -318,27 +318,13 @@ zk_plonk_opening *opening_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, in
     return o.release();
 }
 
-void plonk_evaluate(zk_plonk_opening *o, uint8_t *evals, const uint8_t *const in[WIT_VECS], const uint64_t len[WIT_VECS], const uint8_t *zeta) {
-    const char *who = "zk_plonk_evaluate";
-    const uint32_t seg = seg_in_effect();
-    if (!o || !evals || !in[W_A] || !in[W_B] || !in[W_C] || !in[W_Z] || !zeta) throw std::invalid_argument("null argument");
-    static const char *const names[WIT_VECS] = {"a", "b", "c", "z"};
-    for (uint32_t j = 0; j < WIT_VECS; j++)
-        if (len[j] < 1 || len[j] > o->cap)
-            throw std::invalid_argument(std::string(who) + ": " + names[j] + "_len " + std::to_string(len[j]) + " is outside 1 .. max_coeffs = " + std::to_string(o->cap));
-    for (uint32_t j = 0; j < WIT_VECS; j++) check_below_r(who, names[j], in[j], len[j]);
-    const Fr ze = checked_one(who, "zeta", zeta);
-    std::lock_guard<std::mutex> lock(o->mu);
-    DeviceGuard dg(o->device);
-    LaunchCount lc(o);
-    hipStream_t s = o->st->s;
+// Round 4 over the rows already in o->wit, len[] of them each: the two launches, the six values to the host, and the state
+// round 5 consumes.  The caller holds the object (its mutex, or as its only owner) and has set the device
+void evaluate_dev(zk_plonk_opening *o, uint8_t *evals, const uint64_t len[WIT_VECS], const Fr &ze, uint32_t seg, hipStream_t s) {
     o->pending = false;
     const uint64_t n = o->n, cap = o->cap;
     uint64_t longest = n;
-    for (uint32_t j = 0; j < WIT_VECS; j++) {
-        HIP_TRY(hipMemcpyAsync(o->wit.p + j * cap, in[j], len[j] * sizeof(Fr), hipMemcpyHostToDevice, s));
-        longest = len[j] > longest ? len[j] : longest;
-    }
+    for (uint32_t j = 0; j < WIT_VECS; j++) longest = len[j] > longest ? len[j] : longest;
     const uint32_t blocks = blocks_of(longest, seg);
     const uint64_t lanes = (uint64_t)blocks * OP_WG;
     o->hek[0] = eval_consts(ze, lanes);
@@ -359,6 +345,25 @@ void plonk_evaluate(zk_plonk_opening *o, uint8_t *evals, const uint8_t *const in
     for (uint32_t j = 0; j < WIT_VECS; j++) o->lens[j] = len[j];
     o->zeta = ze;
     o->pending = true;
+}
+
+void plonk_evaluate(zk_plonk_opening *o, uint8_t *evals, const uint8_t *const in[WIT_VECS], const uint64_t len[WIT_VECS], const uint8_t *zeta) {
+    const char *who = "zk_plonk_evaluate";
+    const uint32_t seg = seg_in_effect();
+    if (!o || !evals || !in[W_A] || !in[W_B] || !in[W_C] || !in[W_Z] || !zeta) throw std::invalid_argument("null argument");
+    static const char *const names[WIT_VECS] = {"a", "b", "c", "z"};
+    for (uint32_t j = 0; j < WIT_VECS; j++)
+        if (len[j] < 1 || len[j] > o->cap)
+            throw std::invalid_argument(std::string(who) + ": " + names[j] + "_len " + std::to_string(len[j]) + " is outside 1 .. max_coeffs = " + std::to_string(o->cap));
+    for (uint32_t j = 0; j < WIT_VECS; j++) check_below_r(who, names[j], in[j], len[j]);
+    const Fr ze = checked_one(who, "zeta", zeta);
+    std::lock_guard<std::mutex> lock(o->mu);
+    DeviceGuard dg(o->device);
+    LaunchCount lc(o);
+    hipStream_t s = o->st->s;
+    o->pending = false;
+    for (uint32_t j = 0; j < WIT_VECS; j++) HIP_TRY(hipMemcpyAsync(o->wit.p + j * o->cap, in[j], len[j] * sizeof(Fr), hipMemcpyHostToDevice, s));
+    evaluate_dev(o, evals, len, ze, seg, s);
 }
 
 // What the host makes of the six values and the challenges: F's scalars, the constant of index 0, and E.  One inversion
@@ -395,32 +400,15 @@ LinConsts lin_consts(const zk_plonk_opening &o, Fr pi_zeta, Fr alpha, Fr beta, F
     return k;
 }
 
-void plonk_open(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uint8_t *r_zeta, uint8_t *f, uint64_t *f_len, const uint8_t *const t[T_VECS],
-                const uint64_t tlen[T_VECS], const uint8_t *pi_zeta, const uint8_t *alpha, const uint8_t *beta, const uint8_t *gamma, const uint8_t *v) {
-    const char *who = "zk_plonk_open";
-    const uint32_t seg = seg_in_effect(), dseg = kzg_seg_in_effect();
-    if (!o || !w_zeta || !w_zeta_omega || !r_zeta || !t[0] || !t[1] || !t[2] || !alpha || !beta || !gamma || !v || (f && !f_len))
-        throw std::invalid_argument("null argument");
-    static const char *const names[T_VECS] = {"t_lo", "t_mid", "t_hi"};
-    static const char *const lnames[T_VECS] = {"lo_len", "mid_len", "hi_len"};
-    for (uint32_t j = 0; j < T_VECS; j++)
-        if (tlen[j] < 1 || tlen[j] > o->cap)
-            throw std::invalid_argument(std::string(who) + ": " + lnames[j] + " " + std::to_string(tlen[j]) + " is outside 1 .. max_coeffs = " + std::to_string(o->cap));
-    for (uint32_t j = 0; j < T_VECS; j++) check_below_r(who, names[j], t[j], tlen[j]);
-    const Fr pz = pi_zeta ? checked_one(who, "pi_zeta", pi_zeta) : Fr::zero();
-    const Fr al = checked_one(who, "alpha", alpha), be = checked_one(who, "beta", beta), ga = checked_one(who, "gamma", gamma), vv = checked_one(who, "v", v);
-    std::lock_guard<std::mutex> lock(o->mu);
-    if (!o->pending) throw std::invalid_argument(std::string(who) + ": no evaluation is pending: call zk_plonk_evaluate first");
-    o->pending = false;
-    DeviceGuard dg(o->device);
-    LaunchCount lc(o);
-    hipStream_t s = o->st->s;
+// Round 5 over the parts of t already in o->tp, tlen[] rows each, and the pending evaluation's rows and values (the caller
+// has consumed `pending`): the linearisation, the two divisions and the two multiplications.  Held as evaluate_dev
+void open_dev(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uint8_t *r_zeta, uint8_t *f, uint64_t *f_len, const uint64_t tlen[T_VECS],
+              const Fr &pz, const Fr &al, const Fr &be, const Fr &ga, const Fr &vv, uint32_t seg, uint32_t dseg, hipStream_t s, bool pad = false) {
     zk_kzg *k = o->kzg;
     const uint64_t n = o->n, cap = o->cap;
     Fr E;
     o->hlk = lin_consts(*o, pz, al, be, ga, vv, &E);
     HIP_TRY(hipMemcpyAsync(o->lk.p, &o->hlk, sizeof o->hlk, hipMemcpyHostToDevice, s));
-    for (uint32_t j = 0; j < T_VECS; j++) HIP_TRY(hipMemcpyAsync(o->tp.p + j * cap, t[j], tlen[j] * sizeof(Fr), hipMemcpyHostToDevice, s));
     LinArgs A{};
     auto row = [&](int r, const Fr *p, uint64_t len) { A.row[r] = p, A.len[r] = len, A.L = len > A.L ? len : A.L; };
     row(R_QM, o->circ.p + C_QM * n, n), row(R_QL, o->circ.p + C_QL * n, n), row(R_QR, o->circ.p + C_QR * n, n), row(R_QO, o->circ.p + C_QO * n, n);
@@ -449,7 +437,11 @@ void plonk_open(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uin
         if (j == 0) HIP_TRY(hipMemcpyAsync(&fz, o->yv.p, sizeof fz, hipMemcpyDeviceToHost, s));
         if (cnt[j] > 1) {
             std::lock_guard<std::mutex> kl(k->mu);     // the kzg's points and the work buffers of its multiplication
-            msm_resident(k->msm, out[j], k->tau.p, o->quot.p, cnt[j] - 1, s);
+            // pad (the chained prover's): the multiplication runs over one row more than the quotient has, zeroed here after the
+            // division (stream order), so that it has the size of the prover's seven others and the kzg's buffers are not made
+            // again; cnt[j] <= cap rows are there.  A zero scalar adds nothing: the point is the same
+            if (pad) HIP_TRY(hipMemsetAsync(o->quot.p + (cnt[j] - 1), 0, sizeof(Fr), s));
+            msm_resident(k->msm, out[j], k->tau.p, o->quot.p, pad ? cnt[j] : cnt[j] - 1, s);
         } else {
             memset(out[j], 0, 64);
             HIP_TRY(hipStreamSynchronize(s));
@@ -459,7 +451,52 @@ void plonk_open(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uin
     memcpy(r_zeta, r.v, 32);
 }
 
+void plonk_open(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uint8_t *r_zeta, uint8_t *f, uint64_t *f_len, const uint8_t *const t[T_VECS],
+                const uint64_t tlen[T_VECS], const uint8_t *pi_zeta, const uint8_t *alpha, const uint8_t *beta, const uint8_t *gamma, const uint8_t *v) {
+    const char *who = "zk_plonk_open";
+    const uint32_t seg = seg_in_effect(), dseg = kzg_seg_in_effect();
+    if (!o || !w_zeta || !w_zeta_omega || !r_zeta || !t[0] || !t[1] || !t[2] || !alpha || !beta || !gamma || !v || (f && !f_len))
+        throw std::invalid_argument("null argument");
+    static const char *const names[T_VECS] = {"t_lo", "t_mid", "t_hi"};
+    static const char *const lnames[T_VECS] = {"lo_len", "mid_len", "hi_len"};
+    for (uint32_t j = 0; j < T_VECS; j++)
+        if (tlen[j] < 1 || tlen[j] > o->cap)
+            throw std::invalid_argument(std::string(who) + ": " + lnames[j] + " " + std::to_string(tlen[j]) + " is outside 1 .. max_coeffs = " + std::to_string(o->cap));
+    for (uint32_t j = 0; j < T_VECS; j++) check_below_r(who, names[j], t[j], tlen[j]);
+    const Fr pz = pi_zeta ? checked_one(who, "pi_zeta", pi_zeta) : Fr::zero();
+    const Fr al = checked_one(who, "alpha", alpha), be = checked_one(who, "beta", beta), ga = checked_one(who, "gamma", gamma), vv = checked_one(who, "v", v);
+    std::lock_guard<std::mutex> lock(o->mu);
+    if (!o->pending) throw std::invalid_argument(std::string(who) + ": no evaluation is pending: call zk_plonk_evaluate first");
+    o->pending = false;
+    DeviceGuard dg(o->device);
+    LaunchCount lc(o);
+    hipStream_t s = o->st->s;
+    for (uint32_t j = 0; j < T_VECS; j++) HIP_TRY(hipMemcpyAsync(o->tp.p + j * o->cap, t[j], tlen[j] * sizeof(Fr), hipMemcpyHostToDevice, s));
+    open_dev(o, w_zeta, w_zeta_omega, r_zeta, f, f_len, tlen, pz, al, be, ga, vv, seg, dseg, s);
+}
+
 }   // namespace
+
+// ---------------------------------------------------------------- what plonkprove.hip chains (plonk_internal.hpp)
+uint32_t plonk_open_seg() { return seg_in_effect(); }
+uint64_t plonk_opening_need_bytes(uint64_t n, uint64_t cap, bool lagrange) { return resident_bytes(n, cap) + (lagrange ? 2 * n * sizeof(Fr) : 0); }
+size_t plonk_opening_bytes(const zk_plonk_opening *o) { return o->bytes(); }
+Fr *plonk_opening_wit(zk_plonk_opening *o, uint32_t j) { return o->wit.p + j * o->cap; }
+Fr *plonk_opening_part(zk_plonk_opening *o, uint32_t j) { return o->tp.p + j * o->cap; }
+const Fr *plonk_opening_circ(const zk_plonk_opening *o, uint32_t j) { return o->circ.p + j * o->n; }
+void plonk_opening_clear(zk_plonk_opening *o, hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(o->wit.p, 0, o->wit.bytes(), s));
+    HIP_TRY(hipMemsetAsync(o->tp.p, 0, o->tp.bytes(), s));
+}
+void plonk_opening_evaluate_dev(zk_plonk_opening *o, uint8_t evals[6 * 32], const uint64_t len[4], const Fr &zeta, hipStream_t s) {
+    evaluate_dev(o, evals, len, zeta, seg_in_effect(), s);
+}
+void plonk_opening_open_dev(zk_plonk_opening *o, uint8_t w_zeta[64], uint8_t w_zeta_omega[64], uint8_t r_zeta[32], uint8_t *f, uint64_t *f_len,
+                            const uint64_t tlen[3], const Fr &pi_zeta, const Fr &alpha, const Fr &beta, const Fr &gamma, const Fr &v, hipStream_t s) {
+    if (!o->pending) throw std::invalid_argument("zk_plonk_open: no evaluation is pending: call zk_plonk_evaluate first");
+    o->pending = false;
+    open_dev(o, w_zeta, w_zeta_omega, r_zeta, f, f_len, tlen, pi_zeta, alpha, beta, gamma, v, seg_in_effect(), kzg_seg_in_effect(), s, /*pad=*/true);
+}
 
 extern "C" {
 

@@ -29,6 +29,7 @@
 #include "devmem.hpp"
 #include "ptengine.hpp"
 #include "field29.hpp"
+#include "plonk_internal.hpp"
 
 namespace {
 
@@ -397,6 +398,9 @@ struct zk_plonk_circuit {
     QuotConsts hq;                                    // host images
     PowConsts hl;
     CosetWork cw;
+    std::unique_ptr<Xform> small;                     // the transforms of size n: made by the first plonk_circuit_interpolate_dev
+    DevBuf<PowConsts> ks;                             // its load and store records
+    PowConsts hs[2];
     uint32_t last_launches = 0;
     size_t bytes() const {
         return res.bytes() + x.bytes() + y.bytes() + kq.bytes() + kl.bytes() + cw.k.bytes() + cw.hi.bytes() + Xform::bytes_of(log_n + 2);
@@ -588,6 +592,57 @@ void plonk_quotient(zk_plonk_circuit *c, uint8_t *t, uint64_t *t_len, const uint
 }
 
 }   // namespace
+
+// ---------------------------------------------------------------- what plonkprove.hip chains (plonk_internal.hpp)
+uint32_t plonk_quot_seg() { return seg_in_effect(); }
+
+uint64_t plonk_circuit_need_bytes(uint32_t log_n) {
+    const uint64_t m = 4ull << log_n;
+    const uint64_t making = 2 * RES_VECS * m * sizeof(Fr) + Xform::bytes_of(log_n + 2) + Xform::bytes_of(log_n) + CosetWork::bytes_of(m);
+    return (making > steady_bytes(log_n) ? making : steady_bytes(log_n)) + Xform::bytes_of(log_n) + 2 * sizeof(PowConsts);
+}
+
+size_t plonk_circuit_bytes(const zk_plonk_circuit *c) { return c->bytes() + (c->small ? Xform::bytes_of(c->log_n) + c->ks.bytes() : 0); }
+
+Fr *plonk_circuit_rows(zk_plonk_circuit *c) { return c->y.p; }
+
+const Fr *plonk_circuit_quotient_dev(zk_plonk_circuit *c, const uint64_t lens[PLONK_ROWS], uint32_t vecs, const Fr &alpha, const Fr &beta, const Fr &gamma,
+                                     uint64_t *t_len, hipStream_t s) {
+    static_assert(PLONK_ROWS == EXT_VECS, "a, b, c, z, pi");
+    plonk_quotient_dev(*c, lens, vecs, alpha, beta, gamma, seg_in_effect(), t_len, s);
+    return c->x.p + 2 * c->m;
+}
+
+void plonk_circuit_prepare_interpolate(zk_plonk_circuit *c, hipStream_t s) {
+    if (c->small) return;
+    std::unique_ptr<Xform> xf(new Xform());
+    xf->build(c->log_n, s);
+    c->ks.alloc(2);
+    c->small = std::move(xf);
+}
+
+void plonk_circuit_interpolate_dev(zk_plonk_circuit *c, Fr *const out[], const Fr *in, uint32_t batch, hipStream_t s) {
+    const uint32_t seg = seg_in_effect();
+    const uint64_t n = c->n;
+    if (batch < 1 || batch > EXT_VECS) throw std::invalid_argument("plonk_circuit_interpolate_dev: batch is outside 1 .. 5");
+    plonk_circuit_prepare_interpolate(c, s);
+    const uint32_t blocks = blocks_of(n, seg);
+    const uint64_t lanes = (uint64_t)blocks * QT_WG;
+    c->hs[0] = pow_consts(POW_LOAD_STD, Fr::one(), lanes);
+    c->hs[1] = pow_consts(POW_STORE, Fr::one(), lanes);
+    HIP_TRY(hipMemcpyAsync(c->ks.p, c->hs, sizeof c->hs, hipMemcpyHostToDevice, s));
+    // c->x: 20n rows, free between two quotient calls.  The rows go to its first 5n, the transform may leave them in the next 5n
+    LoadArgs U{};
+    for (uint32_t v = 0; v < batch; v++) U.src[v] = in + v * n, U.n_in[v] = n;
+    U.out = c->x.p, U.stride = n, U.m = n, U.seg = seg, U.unit = 1, U.k = c->ks.p;
+    launch_load(U, batch, s);
+    const Fr *r = c->small->run(c->x.p + EXT_VECS * n, c->x.p, n, batch, true, s);
+    for (uint32_t v = 0; v < batch; v++) {
+        StoreArgs S{r + v * n, out[v], nullptr, n, seg, 1u, c->ks.p + 1};
+        ZK_LAUNCH(k_coset_store, dim3(blocks), dim3(QT_WG), 0, s, S);
+    }
+    ZK_LAUNCH_OK("coset store");
+}
 
 extern "C" {
 

@@ -188,6 +188,17 @@ class zk_plonk_opening_plan(C.Structure):
                 ("pending", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class zk_plonk_vkey(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("log_n", C.c_uint32), ("n_public", C.c_uint64), ("k1", C.c_uint8 * 32), ("k2", C.c_uint8 * 32)] + \
+               [(name, C.c_uint8 * 64) for name in ("qm", "ql", "qr", "qo", "qc", "s1", "s2", "s3")] + [("tau_g2", C.c_uint8 * 128)]
+
+
+class zk_plonk_prover_plan(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("log_n", C.c_uint32), ("n_witness", C.c_uint64), ("n_public", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("scan_seg", C.c_uint32), ("quot_seg", C.c_uint32), ("open_seg", C.c_uint32), ("kzg_seg", C.c_uint32), ("last_launches", C.c_uint32),
+                ("round_launches", C.c_uint32 * 5)]
+
+
 class zk_setup_out(C.Structure):
     _fields_ = [("coefs", C.c_void_p), ("pointsIC", C.c_void_p), ("pointsA", C.c_void_p), ("pointsB1", C.c_void_p),
                 ("pointsB2", C.c_void_p), ("pointsC", C.c_void_p), ("pointsH", C.c_void_p)]
@@ -246,7 +257,9 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_fr_poly_divide", "zk_kzg_create", "zk_kzg_destroy", "zk_kzg_info", "zk_kzg_commit", "zk_kzg_open", "zk_kzg_verify", "zk_kzg_verify_batch",
            "zk_fr_batch_inverse", "zk_fr_prefix_product", "zk_fr_grand_product", "zk_plonk_permutation_product", "zk_msm_sort",
            "zk_fr_coset_ntt", "zk_plonk_circuit_create", "zk_plonk_circuit_destroy", "zk_plonk_circuit_info", "zk_plonk_quotient",
-           "zk_fr_poly_eval", "zk_plonk_opening_create", "zk_plonk_opening_destroy", "zk_plonk_opening_info", "zk_plonk_evaluate", "zk_plonk_open"]
+           "zk_fr_poly_eval", "zk_plonk_opening_create", "zk_plonk_opening_destroy", "zk_plonk_opening_info", "zk_plonk_evaluate", "zk_plonk_open",
+           "zk_keccak256", "zk_plonk_prover_create", "zk_plonk_prover_destroy", "zk_plonk_prover_vkey", "zk_plonk_prover_info", "zk_plonk_prove",
+           "zk_plonk_verify"]
 ZK_SCAN_EXCLUSIVE = 1
 ZK_KZG_MONOMIAL, ZK_KZG_LAGRANGE, ZK_KZG_NO_LAGRANGE = 0, 1, 0xffffffff
 ZK_SCALE_PLAN_MAX = 130
@@ -423,6 +436,17 @@ def load_library():
         lib.zk_plonk_evaluate.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p]
         lib.zk_plonk_open.argtypes = [C.c_void_p, u8p, u8p, u8p, u8p, C.POINTER(C.c_uint64), u8p, C.c_uint64, u8p, C.c_uint64, u8p, C.c_uint64, u8p,
                                       u8p, u8p, u8p, u8p]
+    if hasattr(lib, "zk_plonk_prove"):
+        u32p = C.c_void_p
+        lib.zk_keccak256.argtypes = [u8p, u8p, C.c_uint64]
+        lib.zk_plonk_prover_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(zk_plonk_circuit_view), u32p, u32p, u32p, C.c_uint64, C.c_uint64,
+                                               C.c_int32]
+        lib.zk_plonk_prover_destroy.argtypes = [C.c_void_p]
+        lib.zk_plonk_prover_destroy.restype = None
+        lib.zk_plonk_prover_vkey.argtypes = [C.c_void_p, C.POINTER(zk_plonk_vkey)]
+        lib.zk_plonk_prover_info.argtypes = [C.c_void_p, C.POINTER(zk_plonk_prover_plan)]
+        lib.zk_plonk_prove.argtypes = [C.c_void_p, u8p, u8p, u8p, u8p]
+        lib.zk_plonk_verify.argtypes = [C.c_void_p, C.POINTER(zk_plonk_vkey), u8p, u8p, u8p]
     _LIB = lib
     return lib
 

@@ -256,3 +256,231 @@ class PlonkCircuit:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------- the prover and the verifier
+# include/zkhip.h, section "PLONK prover and verifier": the five rounds chained on the device, the Keccak-256 transcript
+# and the verifier.  Parity with snarkjs is unpinned (no file made by snarkjs was at hand): the layout is the header's.
+PROOF_BYTES, BLINDS, MIN_PROVER_LOG_N = 768, 11, 3
+Q_MOD = 21888242871839275222246405745257275088696311157297823662689037894645226208583
+_Q_RINV = pow(1 << 256, -1, Q_MOD)
+_POINTS = ("A", "B", "C", "Z", "T1", "T2", "T3", "Wxi", "Wxiw")         # snarkjs's names, the proof's order
+_EVALS = ("eval_a", "eval_b", "eval_c", "eval_s1", "eval_s2", "eval_zw")
+
+
+def keccak256(data):
+    """32 bytes: Keccak-256 with the original 0x01 padding (zk_keccak256).  No device."""
+    a = L._buf(bytes(data))
+    out = np.zeros(32, dtype=np.uint8)
+    L.check(L.load_library().zk_keccak256(L._ptr(out), L._ptr(a) if a.size else None, a.size))
+    return out.tobytes()
+
+
+def _affine(b):
+    """64 bytes in the .ptau encoding -> (x, y) standard ints, None for infinity"""
+    if not any(b):
+        return None
+    return (int.from_bytes(b[:32], "little") * _Q_RINV % Q_MOD, int.from_bytes(b[32:], "little") * _Q_RINV % Q_MOD)
+
+
+class PlonkProof:
+    """768 bytes: [a] [b] [c] [z] [t_lo] [t_mid] [t_hi] [W_zeta] [W_zeta_omega] in the .ptau encoding, then a(zeta), b(zeta),
+    c(zeta), s1(zeta), s2(zeta), z(zeta w) as 32 bytes little-endian."""
+
+    def __init__(self, data):
+        data = bytes(data)
+        if len(data) != PROOF_BYTES:
+            raise ValueError("a proof of %d bytes expected, got %d" % (PROOF_BYTES, len(data)))
+        self._b = data
+
+    def to_bytes(self):
+        return self._b
+
+    @property
+    def points(self):
+        return [self._b[i * 64:(i + 1) * 64] for i in range(9)]
+
+    @property
+    def evals(self):
+        return [int.from_bytes(self._b[576 + i * 32:576 + (i + 1) * 32], "little") for i in range(6)]
+
+    def to_json(self):
+        """snarkjs's proof.json: its field names, decimal strings, projective points with z = 1 (infinity: 0, 1, 0)"""
+        import json
+        d = {}
+        for name, p in zip(_POINTS, self.points):
+            xy = _affine(p)
+            d[name] = ["0", "1", "0"] if xy is None else [str(xy[0]), str(xy[1]), "1"]
+        for name, v in zip(_EVALS, self.evals):
+            d[name] = str(v)
+        d["protocol"], d["curve"] = "plonk", "bn128"
+        return json.dumps(d, indent=1)
+
+    def __eq__(self, other):
+        return isinstance(other, PlonkProof) and self._b == other._b
+
+    def __hash__(self):
+        return hash(self._b)
+
+
+class PlonkVKey:
+    """What plonk_verify needs (zk_plonk_vkey) and the Kzg whose [tau]G2 it names."""
+
+    def __init__(self, kzg, c):
+        self.kzg, self._c = kzg, c
+
+    log_n = property(lambda self: int(self._c.log_n))
+    n = property(lambda self: 1 << int(self._c.log_n))
+    n_public = property(lambda self: int(self._c.n_public))
+    k1 = property(lambda self: int.from_bytes(bytes(self._c.k1), "little"))
+    k2 = property(lambda self: int.from_bytes(bytes(self._c.k2), "little"))
+    tau_g2 = property(lambda self: bytes(self._c.tau_g2))
+
+    @property
+    def commitments(self):
+        """name -> 64 bytes, the transcript's order"""
+        return {name: bytes(getattr(self._c, name)) for name in ("qm", "ql", "qr", "qo", "qc", "s1", "s2", "s3")}
+
+
+def _maps(maps, n, n_witness):
+    out = []
+    for name, m in zip(("a_map", "b_map", "c_map"), maps):
+        a = np.ascontiguousarray(np.asarray(m, dtype=np.int64).reshape(-1))
+        if a.size != n:
+            raise ValueError("%s has %d indices, n = %d expected" % (name, a.size, n))
+        bad = np.nonzero((a < 0) | (a >= n_witness))[0]
+        if bad.size:
+            raise ValueError("%s %d is %d, not below n_witness = %d" % (name, int(bad[0]), int(a[bad[0]]), n_witness))
+        out.append(a.astype(np.uint32))
+    return out
+
+
+class PlonkProver:
+    """A three-column PLONK prover for one circuit on a Kzg's device (zk_plonk_prover): everything that does not change from
+    proof to proof stays resident, a proof uploads the witness and nothing else per row.  Row i's wires are
+    witness[a_map[i]], witness[b_map[i]], witness[c_map[i]].  The object keeps a reference to the Kzg."""
+
+    def __init__(self, kzg, ql, qr, qm, qo, qc, s1, s2, s3, k1, k2, a_map, b_map, c_map, n_witness, n_public=0, basis="monomial", shift=None):
+        from .kzg import Kzg
+        if not isinstance(kzg, Kzg):
+            raise TypeError("a Kzg expected")
+        if basis not in _BASES:
+            raise ValueError("basis %r is unknown: 'monomial' or 'lagrange'" % (basis,))
+        vecs, n, log_n = _circuit_rows((ql, qr, qm, qo, qc, s1, s2, s3))
+        if log_n < MIN_PROVER_LOG_N:
+            raise ValueError("log_n %d is outside %d .. %d" % (log_n, MIN_PROVER_LOG_N, MAX_LOG_N))
+        kb1, kb2 = _one(k1, "k1"), _one(k2, "k2")
+        g = _shift(shift)
+        if g is not None and pow(int.from_bytes(g.tobytes(), "little") % R_MOD, 4 * n, R_MOD) == 1:
+            raise ValueError("shift^(4n) is 1: Z_H vanishes on the coset")
+        if n + 6 > kzg.max_coeffs:
+            raise ValueError("n + 6 = %d exceeds the kzg's max_coeffs = %d" % (n + 6, kzg.max_coeffs))
+        n_witness, n_public = int(n_witness), int(n_public)
+        if n_witness < 1:
+            raise ValueError("n_witness is %d: at least one value expected" % n_witness)
+        if not 0 <= n_public <= n:
+            raise ValueError("n_public %d is outside 0 .. n = %d" % (n_public, n))
+        maps = _maps((a_map, b_map, c_map), n, n_witness)
+        self._h = C.c_void_p()
+        self.kzg, self.n, self.log_n, self.n_witness, self.n_public, self.device = kzg, n, log_n, n_witness, n_public, kzg.device
+        kh = kzg._handle()
+        v = L.zk_plonk_circuit_view()
+        v.log_n, v.basis = log_n, _BASES[basis]
+        for name, a in zip(_CIRCUIT, vecs):
+            setattr(v, name, a.ctypes.data)
+        C.memmove(v.k1, kb1.ctypes.data, 32)
+        C.memmove(v.k2, kb2.ctypes.data, 32)
+        v.shift = g.ctypes.data if g is not None else None
+        L.check(L.load_library().zk_plonk_prover_create(C.byref(self._h), kh, C.byref(v), L._ptr(maps[0]), L._ptr(maps[1]), L._ptr(maps[2]), n_witness,
+                                                        n_public, -1))
+
+    def _handle(self):
+        if not self._h:
+            raise L.ZkHipError("the PlonkProver object is closed")
+        self.kzg._handle()                              # a closed Kzg: its points are gone
+        return self._h
+
+    def prove(self, witness, publics=None, blind=None):
+        """-> PlonkProof (zk_plonk_prove).  publics None: witness[1 : 1 + n_public], circom's layout.  blind None: eleven
+        scalars from the OS generator; given (FOR TESTS ONLY): b1 .. b11.  ZKHIP_SELFVERIFY=1: the proof is verified before
+        it is returned."""
+        import os
+        w = _scalars(witness, "witness")
+        if w.size != self.n_witness * 32:
+            raise ValueError("witness: %d values, n_witness = %d expected" % (w.size // 32, self.n_witness))
+        if publics is None:
+            if 1 + self.n_public > self.n_witness:
+                raise ValueError("publics: the witness has no %d values after its first" % self.n_public)
+            pb = w[32:32 * (1 + self.n_public)].copy()
+        else:
+            pb = _scalars(publics, "publics")
+            if pb.size != self.n_public * 32:
+                raise ValueError("publics: %d values, n_public = %d expected" % (pb.size // 32, self.n_public))
+        bb = None
+        if blind is not None:
+            bb = _scalars(blind, "blind")
+            if bb.size != BLINDS * 32:
+                raise ValueError("blind: %d values, %d expected" % (bb.size // 32, BLINDS))
+        h = self._handle()
+        out = np.zeros(PROOF_BYTES, dtype=np.uint8)
+        L.check(L.load_library().zk_plonk_prove(h, L._ptr(out), L._ptr(w), L._ptr(pb) if self.n_public else None, L._ptr(bb) if bb is not None else None))
+        proof = PlonkProof(out.tobytes())
+        if os.environ.get("ZKHIP_SELFVERIFY") == "1":
+            verdict = plonk_verify(self.vkey(), proof, pb)
+            if verdict != 0:
+                raise L.ZkHipError("ZKHIP_SELFVERIFY: the proof does not verify (verdict %d)" % verdict)
+        return proof
+
+    def vkey(self):
+        """-> PlonkVKey (zk_plonk_prover_vkey): log_n, n_public, k1, k2, the eight commitments and [tau]G2"""
+        h = self._handle()
+        c = L.zk_plonk_vkey()
+        c.size = C.sizeof(c)
+        L.check(L.load_library().zk_plonk_prover_vkey(h, C.byref(c)))
+        return PlonkVKey(self.kzg, c)
+
+    def info(self):
+        """zk_plonk_prover_info -> dict: log_n, n_witness, n_public, device_bytes, the four knobs in effect, last_launches and
+        round_launches (a list of five)"""
+        h = self._handle()
+        plan = L.zk_plonk_prover_plan()
+        plan.size = C.sizeof(plan)
+        L.check(L.load_library().zk_plonk_prover_info(h, C.byref(plan)))
+        d = {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name not in ("size", "round_launches")}
+        d["round_launches"] = [int(x) for x in plan.round_launches]
+        return d
+
+    def close(self):
+        if self._h:
+            L.load_library().zk_plonk_prover_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def plonk_verify(vkey, proof, publics=(), kzg=None):
+    """VERIFY_OK (0) / VERIFY_INVALID (1) / VERIFY_MALFORMED (2) for one proof (zk_plonk_verify).  proof: a PlonkProof or
+    its 768 bytes.  The pairing product runs on the device of the key's Kzg (or the one given)."""
+    if not isinstance(vkey, PlonkVKey):
+        raise TypeError("a PlonkVKey expected (PlonkProver.vkey())")
+    pr = proof if isinstance(proof, PlonkProof) else PlonkProof(proof)
+    # values that are not below r are the library's to refuse (MALFORMED): they must only fit 32 bytes
+    pb = _scalars(publics, "publics", below_r=False)
+    if pb.size != vkey.n_public * 32:
+        raise ValueError("publics: %d values, n_public = %d expected" % (pb.size // 32, vkey.n_public))
+    k = kzg if kzg is not None else vkey.kzg
+    h = k._handle()
+    a = L._buf(pr.to_bytes())
+    verdict = np.full(1, 255, dtype=np.uint8)
+    L.check(L.load_library().zk_plonk_verify(h, C.byref(vkey._c), L._ptr(a), L._ptr(pb) if vkey.n_public else None, L._ptr(verdict)))
+    return int(verdict[0])
