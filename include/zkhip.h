@@ -1210,6 +1210,81 @@ int zk_plonk_prove(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], cons
  * "zk_plonk_verify: a commitment of the key is not a point of the curve". */
 int zk_plonk_verify(zk_kzg *kzg, const zk_plonk_vkey *vk, const uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *publics, uint8_t *verdict);
 
+/* ---- PLONK from an R1CS ---------------------------------------------------------------------- */
+/* A circom .r1cs compiled on the device to what zk_plonk_prover_create takes: the five selectors, the three wire maps and the
+ * permutation s1 s2 s3; the extension of a circom witness by the wires the compile introduces; and a prover made from the
+ * compiled circuit.  Nothing in the reference corresponds to them; the counterpart is snarkjs's `plonk setup`, whose layout
+ * this follows in spirit only: the layout below is this project's own and parity with snarkjs is UNPINNED.
+ * ZKHIP_R1CS_SEG=<elements a lane takes> (decimal, 1 to 4096, read at every call, 8 otherwise; anything else is an error of the
+ * call, "ZKHIP_R1CS_SEG: a number of elements per lane from 1 to 4096 expected") changes the shape of the scans of this
+ * section and not one byte of any result.
+ *
+ * The layout.  Input: a zk_r1cs_view as zk_r1cs_create takes it (m constraints, nWires, nPublic = nPubOut + nPubIn) and k1, k2.
+ * A linear combination (LC) L of A, B, C of a constraint is normalised first: terms whose coefficient is 0 are dropped; the
+ * constant k_L is the coefficient of L's term on wire 0, or 0 if there is none; the other terms stay in file order, t_L of them
+ * (the same non-zero wire twice is two terms).  L is then reduced to ONE term (s_L, c_L):
+ *   t_L = 0: (wire 0, 0).   t_L = 1: the term itself.
+ *   t_L >= 2: t_L - 1 ADDITION GATES, each introducing a new wire.  The first has a = w_1, b = w_2, c = new, ql = c_1, qr = c_2,
+ *   qo = -1; each later one a = the previous new wire, b = w_i, ql = 1, qr = c_i, qo = -1; qm = qc = 0 in all of them.  The
+ *   term is (the last new wire, 1).
+ * Rows.  Rows 0 .. nPublic - 1 are the public rows: a = wire 1 + i, b = c = wire 0, ql = 1, everything else 0 (the prover's PI
+ * is -publics[i] there).  Then, for each constraint in file order, its addition gates (A's, then B's, then C's) and its FINAL
+ * GATE: a = s_A, b = s_B, c = s_C, qm = c_A c_B, ql = c_A k_B, qr = k_A c_B, qo = -c_C, qc = k_A k_B - k_C.
+ *   N = nPublic + sum over the constraints of (max(t_A - 1, 0) + max(t_B - 1, 0) + max(t_C - 1, 0) + 1),
+ *   log_n = max(3, ceil(log2 N)), n = 2^log_n; rows N .. n - 1 are padding: every selector 0, all three wires wire 0.
+ * New wires are numbered nWires + q, q the addition gate's rank in row order; n_witness = nWires + n_additions.
+ * Sigma.  Cell (col, row) has index col n + row, col 0, 1, 2 for a, b, c.  All 3n cells take part, padding included.  The
+ * cells of one wire, in ascending cell index, form one cycle: each points to the next, the last to the first.
+ * s_col[row] = K_col' w^row' for the cell (col', row') it points to, K = (1, k1, k2), w zk_fr_ntt's root for n.  A wire no cell
+ * names has no cycle.
+ * The extension.  The value of new wire nWires + q is the running sum of c_i w[wire_i] over its LC's kept terms up to the
+ * gate's own (rank r: the terms 0 .. r), so that every addition gate holds.
+ *
+ * Refused by name before a device is touched: "zk_plonk_r1cs_create: k1 is not below r" (k2 alike), "zk_plonk_r1cs_create: k1 or
+ * k2 is zero", "zk_plonk_r1cs_create: 1, k1 and k2 do not name three different cosets of the n-th roots of unity" (k1^n = 1,
+ * k2^n = 1 or (k1 / k2)^n = 1, for the n of the term counts, which is at least the circuit's), "zk_plonk_r1cs_create: N =
+ * 33554433 rows exceed 2^25", "zk_plonk_r1cs_create: n_witness = 4294967296 is not below 2^32", "zk_plonk_r1cs_create: nWires is
+ * 0: wire 0 is the constant", "zk_plonk_r1cs_create: nPublic 4 is not below nWires = 4", the section's own texts of
+ * zk_r1cs_create ("r1cs constraints section is truncated (constraint 5)").  Refused when the object is made, on the device:
+ * "r1cs constraint 5: wire id >= nWires", "r1cs constraint 5: coefficient >= r" (zk_r1cs_create's), and a second kept term on
+ * wire 0 in one LC, "zk_plonk_r1cs_create: constraint 5: B names wire 0 twice": the lowest constraint, A before B before C.
+ * Custom gates (sections 4 and 5 of the file) are the caller's to refuse.  Calls on one object are serialised. */
+typedef struct zk_plonk_r1cs zk_plonk_r1cs;
+int zk_plonk_r1cs_create(zk_plonk_r1cs **out, const zk_r1cs_view *view, const uint8_t k1[32], const uint8_t k2[32], int32_t device);
+void zk_plonk_r1cs_destroy(zk_plonk_r1cs *c);
+/* Set plan->size = sizeof(zk_plonk_r1cs_plan) before the call (only `size` bytes are written). */
+typedef struct zk_plonk_r1cs_plan {
+    uint32_t size;
+    uint32_t log_n;
+    uint64_t rows;                /* N */
+    uint64_t n_public, n_wires, n_additions, n_witness;
+    uint64_t terms;               /* of the section, dropped ones included */
+    uint64_t device_bytes;        /* HBM the object holds */
+    uint32_t seg;                 /* ZKHIP_R1CS_SEG in effect */
+    uint32_t sort_passes;         /* 8-bit digit passes of the sort of the cells: ceil(ceil(log2 n_witness) / 8) */
+    uint32_t last_launches;       /* kernel launches of zk_plonk_r1cs_create, or of the last extension on the object */
+    uint32_t reserved;
+} zk_plonk_r1cs_plan;
+int zk_plonk_r1cs_info(zk_plonk_r1cs *c, zk_plonk_r1cs_plan *plan);
+/* vectors: 8 n rows of 32 bytes, ql qr qm qo qc s1 s2 s3 in zk_plonk_circuit_view's order, as VALUES over the domain
+ * (ZK_KZG_LAGRANGE), standard form; a_map, b_map, c_map: n indices each. */
+int zk_plonk_r1cs_circuit(zk_plonk_r1cs *c, uint8_t *vectors, uint32_t *a_map, uint32_t *b_map, uint32_t *c_map);
+/* out: n_witness scalars, the nVars = nWires of a circom witness and the new wires' values after them.
+ * "witness has 5 values, the r1cs 7 wires", "zk_plonk_r1cs_extend: witness 5 is not below r". */
+int zk_plonk_r1cs_extend(zk_plonk_r1cs *c, uint8_t *out, const uint8_t *wtns, uint32_t nVars);
+
+/* The prover of the section above over a compiled circuit, on the kzg's device.  It goes through zk_plonk_r1cs_circuit and
+ * zk_plonk_prover_create: the 8 n rows and the maps cross the host once a circuit, and the refusals are that entry's.  The
+ * prover BORROWS the compiled object as it borrows the kzg.  shift: as zk_plonk_circuit_view's.
+ * "zk_plonk_prover_create_r1cs: the compiled circuit's device 1 is not the kzg's device 0". */
+int zk_plonk_prover_create_r1cs(zk_plonk_prover **out, zk_kzg *kzg, zk_plonk_r1cs *compiled, const uint8_t *shift, int32_t device);
+/* zk_plonk_prove from a circom witness: the nVars = nWires values are uploaded, extended on the device, the publics are
+ * wtns[1 .. 1 + n_public), and the five rounds run over the resident witness.  blind: as zk_plonk_prove.  The refusals of a bad
+ * witness are zk_plonk_prove's under this entry's name ("zk_plonk_prove_r1cs: the witness does not satisfy the gates"), and
+ * "witness has 5 values, the r1cs 7 wires", "zk_plonk_prove_r1cs: witness 5 is not below r",
+ * "zk_plonk_prove_r1cs: the prover was not made from an r1cs (zk_plonk_prover_create_r1cs)". */
+int zk_plonk_prove_r1cs(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *wtns, uint32_t nVars, const uint8_t *blind);
+
 #ifdef __cplusplus
 }
 #endif

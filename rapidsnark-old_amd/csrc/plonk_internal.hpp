@@ -53,3 +53,18 @@ void plonk_opening_clear(zk_plonk_opening *o, hipStream_t s);    // zeros in eve
 void plonk_opening_evaluate_dev(zk_plonk_opening *o, uint8_t evals[6 * 32], const uint64_t len[4], const Fr &zeta, hipStream_t s);
 void plonk_opening_open_dev(zk_plonk_opening *o, uint8_t w_zeta[64], uint8_t w_zeta_omega[64], uint8_t r_zeta[32], uint8_t *f, uint64_t *f_len,
                             const uint64_t tlen[3], const Fr &pi_zeta, const Fr &alpha, const Fr &beta, const Fr &gamma, const Fr &v, hipStream_t s);
+
+// ---------------------------------------------------------------- plonkr1cs.hip
+struct zk_plonk_r1cs;
+struct PlonkR1csDims {
+    int device;
+    uint32_t log_n;
+    uint64_t n, n_wires, n_public, n_witness;
+    const uint8_t *k1, *k2;                           // standard, 32 bytes each, the object's
+};
+PlonkR1csDims plonk_r1cs_dims(const zk_plonk_r1cs *c);
+// "witness has 5 values, the r1cs 7 wires"; "<who>: witness 5 is not below r"
+void plonk_r1cs_check_witness(const zk_plonk_r1cs *c, const char *who, const uint8_t *wtns, uint32_t nVars);
+// w: n_witness standard rows on the object's device whose first n_wires hold a circom witness; the rest is written.  The
+// stream is drained once inside
+void plonk_r1cs_extend_dev(zk_plonk_r1cs *c, Fr *w, hipStream_t s);

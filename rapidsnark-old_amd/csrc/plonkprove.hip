@@ -299,6 +299,7 @@ uint32_t blocks_of(uint64_t n, uint32_t seg) { return nblocks(n, PV_WG * seg); }
 // ---------------------------------------------------------------- the object
 struct zk_plonk_prover {
     zk_kzg *kzg = nullptr;                            // borrowed: it outlives the object
+    zk_plonk_r1cs *r1cs = nullptr;                    // borrowed too: the compiled circuit of a prover made by zk_plonk_prover_create_r1cs
     int device = 0;
     uint32_t log_n = 0;
     uint64_t n = 0, cap = 0, n_witness = 0, n_public = 0;
@@ -423,35 +424,32 @@ zk_plonk_prover *prover_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, cons
     return p.release();
 }
 
-void plonk_prove(zk_plonk_prover *p, uint8_t *proof, const uint8_t *witness, const uint8_t *publics, const uint8_t *blind) {
-    const char *who = "zk_plonk_prove";
-    if (!p || !proof || !witness || (p->n_public && !publics)) throw std::invalid_argument("null argument");
-    check_below_r(who, "witness", witness, p->n_witness);
-    if (p->n_public) check_below_r(who, "publics", publics, p->n_public);
-    uint8_t drawn[BLINDS * 32];
-    struct Wipe {                                     // drawn blinds are secrets: gone from the stack however the call leaves
-        uint8_t *p;
-        ~Wipe() {
-            volatile uint8_t *v = p;
-            for (size_t i = 0; i < BLINDS * 32; i++) v[i] = 0;
-        }
-    } wipe{drawn};
+// a call's blinds: the caller's, checked, or drawn into `drawn`
+const uint8_t *blinds_of(const char *who, const uint8_t *blind, uint8_t *drawn) {
     if (blind) {
         check_below_r(who, "blind", blind, BLINDS);
-    } else {
-        for (uint32_t j = 0; j < BLINDS; j++) draw_scalar(drawn + j * 32, who);
-        blind = drawn;
+        return blind;
     }
-    const uint32_t seg = plonk_quot_seg();
-    (void)plonk_perm_seg(), (void)plonk_open_seg(), (void)kzg_seg_in_effect();      // a bad knob is an error of the call before any work
-    std::lock_guard<std::mutex> lock(p->mu);
-    DeviceGuard dg(p->device);
+    for (uint32_t j = 0; j < BLINDS; j++) draw_scalar(drawn + j * 32, who);
+    return drawn;
+}
+struct Wipe {                                         // drawn blinds are secrets: gone from the stack however the call leaves
+    uint8_t *p;
+    ~Wipe() {
+        volatile uint8_t *v = p;
+        for (size_t i = 0; i < BLINDS * 32; i++) v[i] = 0;
+    }
+};
+
+// The five rounds over what is resident: the witness in p->wit, the publics in p->pub, the blinds in p->blind (their copies
+// queued on the stream by the caller, who holds p->mu and the device).  publics: the host's copy, for the transcript.
+// first: the launch counter where the call began
+void plonk_prove_core(zk_plonk_prover *p, const char *who, uint8_t *proof, const uint8_t *publics, uint32_t seg, uint64_t first) {
     hipStream_t s = p->st->s;
     zk_kzg *k = p->kzg;
     const uint64_t n = p->n, len = n + 6;               // every committed row is read as n + 6 coefficients: zeros above its own length
     const uint32_t log_n = p->log_n;
     uint64_t mark = launches_now();
-    const uint64_t first = mark;
     uint32_t rounds[ROUNDS];
     auto end_round = [&](int r) {
         const uint64_t now = launches_now();
@@ -464,9 +462,6 @@ void plonk_prove(zk_plonk_prover *p, uint8_t *proof, const uint8_t *witness, con
     Fr *rows[4] = {plonk_opening_wit(p->open, 0), plonk_opening_wit(p->open, 1), plonk_opening_wit(p->open, 2), plonk_opening_wit(p->open, 3)};
 
     // round 1: the wires by values, their coefficients, the blinding, [a] [b] [c]
-    HIP_TRY(hipMemcpyAsync(p->wit.p, witness, p->n_witness * sizeof(Fr), hipMemcpyHostToDevice, s));
-    if (p->n_public) HIP_TRY(hipMemcpyAsync(p->pub.p, publics, p->n_public * sizeof(Fr), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(p->blind.p, blind, BLINDS * sizeof(Fr), hipMemcpyHostToDevice, s));
     const uint32_t vecs = p->n_public ? 4u : 3u;
     GatherArgs G{p->maps.p, p->wit.p, p->pub.p, p->vals.p, n, p->n_public, seg};
     ZK_LAUNCH(k_wire_gather, dim3(blocks_of(n, seg), vecs), dim3(PV_WG), 0, s, G);
@@ -534,6 +529,73 @@ void plonk_prove(zk_plonk_prover *p, uint8_t *proof, const uint8_t *witness, con
     memcpy(proof, out, sizeof out);
     for (uint32_t r = 0; r < ROUNDS; r++) p->round_launches[r] = rounds[r];
     p->last_launches = (uint32_t)(launches_now() - first);
+}
+
+void plonk_prove(zk_plonk_prover *p, uint8_t *proof, const uint8_t *witness, const uint8_t *publics, const uint8_t *blind) {
+    const char *who = "zk_plonk_prove";
+    if (!p || !proof || !witness || (p->n_public && !publics)) throw std::invalid_argument("null argument");
+    check_below_r(who, "witness", witness, p->n_witness);
+    if (p->n_public) check_below_r(who, "publics", publics, p->n_public);
+    uint8_t drawn[BLINDS * 32];
+    Wipe wipe{drawn};
+    blind = blinds_of(who, blind, drawn);
+    const uint32_t seg = plonk_quot_seg();
+    (void)plonk_perm_seg(), (void)plonk_open_seg(), (void)kzg_seg_in_effect();      // a bad knob is an error of the call before any work
+    std::lock_guard<std::mutex> lock(p->mu);
+    DeviceGuard dg(p->device);
+    hipStream_t s = p->st->s;
+    const uint64_t first = launches_now();
+    HIP_TRY(hipMemcpyAsync(p->wit.p, witness, p->n_witness * sizeof(Fr), hipMemcpyHostToDevice, s));
+    if (p->n_public) HIP_TRY(hipMemcpyAsync(p->pub.p, publics, p->n_public * sizeof(Fr), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(p->blind.p, blind, BLINDS * sizeof(Fr), hipMemcpyHostToDevice, s));
+    plonk_prove_core(p, who, proof, publics, seg, first);
+}
+
+// a circom witness: its nWires values go up, the device extends them, the publics are w[1 .. 1 + n_public)
+void plonk_prove_r1cs(zk_plonk_prover *p, uint8_t *proof, const uint8_t *wtns, uint32_t nVars, const uint8_t *blind) {
+    const char *who = "zk_plonk_prove_r1cs";
+    if (!p || !proof || !wtns) throw std::invalid_argument("null argument");
+    if (!p->r1cs) throw std::invalid_argument(std::string(who) + ": the prover was not made from an r1cs (zk_plonk_prover_create_r1cs)");
+    plonk_r1cs_check_witness(p->r1cs, who, wtns, nVars);
+    uint8_t drawn[BLINDS * 32];
+    Wipe wipe{drawn};
+    blind = blinds_of(who, blind, drawn);
+    const uint32_t seg = plonk_quot_seg();
+    (void)plonk_perm_seg(), (void)plonk_open_seg(), (void)kzg_seg_in_effect();
+    const uint8_t *publics = wtns + 32;
+    std::lock_guard<std::mutex> lock(p->mu);
+    DeviceGuard dg(p->device);
+    hipStream_t s = p->st->s;
+    const uint64_t first = launches_now();
+    HIP_TRY(hipMemcpyAsync(p->wit.p, wtns, (size_t)nVars * sizeof(Fr), hipMemcpyHostToDevice, s));
+    if (p->n_public) HIP_TRY(hipMemcpyAsync(p->pub.p, publics, p->n_public * sizeof(Fr), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(p->blind.p, blind, BLINDS * sizeof(Fr), hipMemcpyHostToDevice, s));
+    plonk_r1cs_extend_dev(p->r1cs, p->wit.p, s);
+    plonk_prove_core(p, who, proof, publics, seg, first);
+}
+
+// the existing prover over a compiled circuit: its vectors and maps come through the host once (zk_plonk_r1cs_circuit)
+zk_plonk_prover *prover_create_r1cs(zk_kzg *kzg, zk_plonk_r1cs *c, const uint8_t *shift, int32_t device) {
+    if (!kzg || !c) throw std::invalid_argument("null argument");
+    const PlonkR1csDims d = plonk_r1cs_dims(c);
+    if (d.device != kzg->device)
+        throw std::invalid_argument("zk_plonk_prover_create_r1cs: the compiled circuit's device " + std::to_string(d.device) + " is not the kzg's device " +
+                                    std::to_string(kzg->device));
+    std::vector<uint8_t> vec(8 * d.n * 32);
+    std::vector<uint32_t> maps(3 * d.n);
+    if (zk_plonk_r1cs_circuit(c, vec.data(), maps.data(), maps.data() + d.n, maps.data() + 2 * d.n) != 0)
+        throw std::runtime_error(std::string("zk_plonk_prover_create_r1cs: ") + zk_last_error());
+    zk_plonk_circuit_view v;
+    memset(&v, 0, sizeof v);
+    v.log_n = d.log_n, v.basis = ZK_KZG_LAGRANGE;
+    const uint8_t **vp[CIRC_VECS] = {&v.ql, &v.qr, &v.qm, &v.qo, &v.qc, &v.s1, &v.s2, &v.s3};
+    for (uint32_t j = 0; j < CIRC_VECS; j++) *vp[j] = vec.data() + j * d.n * 32;
+    memcpy(v.k1, d.k1, 32);
+    memcpy(v.k2, d.k2, 32);
+    v.shift = shift;
+    zk_plonk_prover *p = prover_create(kzg, &v, maps.data(), maps.data() + d.n, maps.data() + 2 * d.n, d.n_witness, d.n_public, device);
+    p->r1cs = c;
+    return p;
 }
 
 // ---------------------------------------------------------------- the verifier
@@ -665,6 +727,18 @@ int zk_plonk_prove(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], cons
 
 int zk_plonk_verify(zk_kzg *kzg, const zk_plonk_vkey *vk, const uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *publics, uint8_t *verdict) {
     return guarded([&] { plonk_verify(kzg, vk, proof, publics, verdict); });
+}
+
+int zk_plonk_prover_create_r1cs(zk_plonk_prover **out, zk_kzg *kzg, zk_plonk_r1cs *compiled, const uint8_t *shift, int32_t device) {
+    return guarded([&] {
+        if (!out) throw std::invalid_argument("null argument");
+        *out = nullptr;
+        *out = prover_create_r1cs(kzg, compiled, shift, device);
+    });
+}
+
+int zk_plonk_prove_r1cs(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *wtns, uint32_t nVars, const uint8_t *blind) {
+    return guarded([&] { plonk_prove_r1cs(p, proof, wtns, nVars, blind); });
 }
 
 }   // extern "C"

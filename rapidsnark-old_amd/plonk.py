@@ -394,6 +394,59 @@ class PlonkProver:
         L.check(L.load_library().zk_plonk_prover_create(C.byref(self._h), kh, C.byref(v), L._ptr(maps[0]), L._ptr(maps[1]), L._ptr(maps[2]), n_witness,
                                                         n_public, -1))
 
+    r1cs = None                                         # the PlonkR1cs of a prover made by from_r1cs
+
+    @classmethod
+    def from_r1cs(cls, kzg, r1cs, shift=None):
+        """A prover over a compiled circuit (zk_plonk_prover_create_r1cs).  r1cs: a PlonkR1cs, which the prover borrows, or a
+        .r1cs path or bytes, compiled here with k1 = 2, k2 = 3 on the kzg's device and closed with the prover."""
+        from .kzg import Kzg
+        if not isinstance(kzg, Kzg):
+            raise TypeError("a Kzg expected")
+        g = _shift(shift)
+        own = not isinstance(r1cs, PlonkR1cs)
+        c = PlonkR1cs(r1cs, device=kzg.device) if own else r1cs
+        try:
+            if c.n + 6 > kzg.max_coeffs:
+                raise ValueError("n + 6 = %d exceeds the kzg's max_coeffs = %d" % (c.n + 6, kzg.max_coeffs))
+            self = cls.__new__(cls)
+            self._h = C.c_void_p()
+            self.kzg, self.n, self.log_n, self.n_witness, self.n_public, self.device = kzg, c.n, c.log_n, c.n_witness, c.n_public, kzg.device
+            self.r1cs, self._own_r1cs = c, own
+            L.check(L.load_library().zk_plonk_prover_create_r1cs(C.byref(self._h), kzg._handle(), c._handle(), L._ptr(g) if g is not None else None, -1))
+        except Exception:
+            if own:
+                c.close()
+            raise
+        return self
+
+    def prove_r1cs(self, wtns, blind=None):
+        """-> PlonkProof (zk_plonk_prove_r1cs) from a circom witness: a .wtns path or bytes, or the raw values (a numpy uint8
+        array or a PinnedBuffer), as R1cs.check takes it.  The device extends it; the publics are its values 1 .. n_public.
+        blind and ZKHIP_SELFVERIFY: as prove."""
+        import os
+        if self.r1cs is None:
+            if not self._h:
+                raise L.ZkHipError("the PlonkProver object is closed")
+            raise L.ZkHipError("zk_plonk_prove_r1cs: the prover was not made from an r1cs (zk_plonk_prover_create_r1cs)")
+        a, n_vars = self.r1cs._values(wtns)
+        bb = None
+        if blind is not None:
+            bb = _scalars(blind, "blind")
+            if bb.size != BLINDS * 32:
+                raise ValueError("blind: %d values, %d expected" % (bb.size // 32, BLINDS))
+        h = self._handle()
+        self.r1cs._handle()
+        out = np.zeros(PROOF_BYTES, dtype=np.uint8)
+        L.check(L.load_library().zk_plonk_prove_r1cs(h, L._ptr(out), C.c_void_p(a.ctypes.data) if a.size else None, n_vars,
+                                                     L._ptr(bb) if bb is not None else None))
+        proof = PlonkProof(out.tobytes())
+        if os.environ.get("ZKHIP_SELFVERIFY") == "1":
+            verdict = plonk_verify(self.vkey(), proof, np.array(a[32:32 * (1 + self.n_public)]))
+            if verdict != 0:
+                raise L.ZkHipError("ZKHIP_SELFVERIFY: the proof does not verify (verdict %d)" % verdict)
+        return proof
+
     def _handle(self):
         if not self._h:
             raise L.ZkHipError("the PlonkProver object is closed")
@@ -453,6 +506,87 @@ class PlonkProver:
     def close(self):
         if self._h:
             L.load_library().zk_plonk_prover_destroy(self._h)
+            self._h = C.c_void_p()
+        if self.r1cs is not None and getattr(self, "_own_r1cs", False):
+            self.r1cs.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PlonkR1cs:
+    """A circom .r1cs compiled on a device to a three-column PLONK circuit (zk_plonk_r1cs; include/zkhip.h, section "PLONK
+    from an R1CS", states the layout): .vectors, the eight vectors ql qr qm qo qc s1 s2 s3 as values over the domain (a list of
+    numpy uint8 [n * 32]), .maps (three numpy uint32 [n]), and extend(wtns), the witness a proof needs.  Custom gates are
+    refused as by R1cs.  k1, k2 must name, with 1, three different cosets of the n-th roots of unity."""
+
+    def __init__(self, path_or_bytes, k1=2, k2=3, device=-1):
+        from .r1cs import open_r1cs
+        kb1, kb2 = _one(k1, "k1"), _one(k2, "k2")
+        self.header, sec = open_r1cs(path_or_bytes)
+        h = self.header
+        keep = np.frombuffer(sec, dtype=np.uint8)
+        v = L.zk_r1cs_view(h.nWires, h.nPubOut, h.nPubIn, h.nPrvIn, h.nConstraints, keep.ctypes.data if keep.size else None, keep.size)
+        self._h = C.c_void_p()
+        self.k1, self.k2, self.device = int(k1), int(k2), int(device)
+        self._circuit = None
+        L.check(L.load_library().zk_plonk_r1cs_create(C.byref(self._h), C.byref(v), L._ptr(kb1), L._ptr(kb2), device))
+        d = self.info()
+        self.log_n, self.n, self.rows = d["log_n"], 1 << d["log_n"], d["rows"]
+        self.n_public, self.n_wires, self.n_additions, self.n_witness = d["n_public"], d["n_wires"], d["n_additions"], d["n_witness"]
+
+    def _handle(self):
+        if not self._h:
+            raise L.ZkHipError("the PlonkR1cs object is closed")
+        return self._h
+
+    def _fetch(self):
+        if self._circuit is None:
+            h = self._handle()
+            n = self.n
+            vec = np.zeros(8 * n * 32, dtype=np.uint8)
+            maps = [np.zeros(n, dtype=np.uint32) for _ in range(3)]
+            L.check(L.load_library().zk_plonk_r1cs_circuit(h, L._ptr(vec), *[L._ptr(m) for m in maps]))
+            self._circuit = ([vec[j * n * 32:(j + 1) * n * 32] for j in range(8)], maps)
+        return self._circuit
+
+    vectors = property(lambda self: self._fetch()[0])
+    maps = property(lambda self: self._fetch()[1])
+
+    def _values(self, wtns):
+        from .r1cs import R1cs
+        return R1cs._values(self, wtns)
+
+    def extend(self, wtns):
+        """numpy uint8 [n_witness * 32]: the circom witness (a .wtns path or bytes, or its raw values) and, after it, the
+        values of the wires the addition gates introduced (zk_plonk_r1cs_extend)"""
+        h = self._handle()
+        a, n_vars = self._values(wtns)
+        out = np.zeros(self.n_witness * 32, dtype=np.uint8)
+        L.check(L.load_library().zk_plonk_r1cs_extend(h, L._ptr(out), C.c_void_p(a.ctypes.data) if a.size else None, n_vars))
+        return out
+
+    def info(self):
+        """zk_plonk_r1cs_info -> dict: log_n, rows (N), n_public, n_wires, n_additions, n_witness, terms, device_bytes, seg
+        (ZKHIP_R1CS_SEG in effect), sort_passes, last_launches"""
+        h = self._handle()
+        plan = L.zk_plonk_r1cs_plan()
+        plan.size = C.sizeof(plan)
+        L.check(L.load_library().zk_plonk_r1cs_info(h, C.byref(plan)))
+        return {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name not in ("size", "reserved")}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.load_library().zk_plonk_r1cs_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
