@@ -29,13 +29,14 @@
 #include "hiputil.hpp"
 #include "devmem.hpp"
 #include "ptengine.hpp"
+#include "lanepow.hpp"
 #include "plonk_internal.hpp"
 
 namespace {
 
 constexpr uint32_t SC_WG = 256, SC_WAVES = SC_WG / 64;
 constexpr uint32_t DEFAULT_SEG = 8, MAX_SEG = 4096;   // the default: the best of profiles/frscan_timing.txt's sweep at 2^20
-constexpr uint32_t MAX_COLS = 8, MAX_LOG_N = 28, POW_TAB = 32;
+constexpr uint32_t MAX_COLS = 8, MAX_LOG_N = 28;
 constexpr int OP_PREFIX = 0, OP_INVERSE = 1, OP_GRAND = 2, OP_PLONK = 3;
 
 static_assert(sizeof(Fr) == 32, "layout");
@@ -401,13 +402,7 @@ ScanEnd launch_scan(ScanArgs A, uint32_t seg, ScanWork &w, hipStream_t s) {
     const uint64_t f = OP == OP_PLONK ? A.cols : 1;
     w.h.lift = r_power(f * seg + 1);
     w.h.tail = Fr::zero();
-    if (OP == OP_PLONK) {
-        Fr t = fr_pow(w.h.omega, seg);
-        for (uint32_t b = 0; b < POW_TAB; b++) {
-            w.h.wtab[b] = t;
-            t = Fr::sqr(t);
-        }
-    }
+    if (OP == OP_PLONK) fill_pow_tab(w.h.wtab, fr_pow(w.h.omega, seg), [](Fr a) { return a; });
     HIP_TRY(hipMemcpyAsync(w.k.p, &w.h, sizeof w.h, hipMemcpyHostToDevice, s));
     A.seg = seg;
     A.k = w.k.p;
@@ -492,11 +487,6 @@ uint64_t lowest_zero_den(ScanArgs A, ScanWork &w, hipStream_t s) {
     for (uint64_t v : low)
         if (v < A.n) return v;
     return A.n;
-}
-
-void check_below_r(const char *who, const char *what, const uint8_t *v, uint64_t n) {
-    const uint64_t bad = first_not_below_r(v, n);
-    if (bad < n) throw std::invalid_argument(std::string(who) + ": " + what + " " + std::to_string(bad) + " is not below r");
 }
 
 void need_n(const char *who, uint64_t n) {

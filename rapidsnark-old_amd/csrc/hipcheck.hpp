@@ -40,6 +40,14 @@ struct PerDeviceOnce {
 // shares).
 namespace zk {
 inline std::atomic<uint64_t> g_kernel_launches{0};
+inline uint64_t launches_now() { return g_kernel_launches.load(std::memory_order_relaxed); }
+// counts the launches of one call into its object's last_launches, however the call leaves
+struct LaunchCount {
+    uint32_t &last;
+    uint64_t at;
+    explicit LaunchCount(uint32_t &last_launches) : last(last_launches), at(launches_now()) {}
+    ~LaunchCount() { last = (uint32_t)(launches_now() - at); }
+};
 }
 #define ZK_LAUNCH(...)                                                        \
     do {                                                                      \

@@ -225,6 +225,27 @@ int guarded(Fn fn) {
     }
 }
 
+// a *_destroy entry: the object's memory is freed on its own device (obj->device), the caller's current device comes back
+template <class T>
+void destroy_on_device(T *obj) {
+    if (!obj) return;
+    int prev = -1;
+    const bool switched = hipGetDevice(&prev) == hipSuccess && hipSetDevice(obj->device) == hipSuccess;
+    delete obj;
+    if (switched) (void)hipSetDevice(prev);
+}
+
+// a *_info entry: fill(q) sets every field but `size` of a zeroed plan, and the caller gets as much of it as plan->size says
+// it has room for (an older caller's shorter struct is served)
+template <class Plan, class Fill>
+void info_into(const char *who, Plan *plan, Fill fill) {
+    if (plan->size < 4) throw std::invalid_argument(std::string(who) + ": plan->size is not set");
+    Plan q{};
+    fill(q);
+    q.size = plan->size < sizeof q ? plan->size : (uint32_t)sizeof q;
+    memcpy(plan, &q, q.size);
+}
+
 inline uint32_t ilog2_exact(uint64_t n) {
     uint32_t l = 0;
     while ((1ull << l) < n) l++;

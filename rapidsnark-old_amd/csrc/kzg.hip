@@ -248,14 +248,6 @@ void fr_poly_divide(uint8_t *q, uint8_t *y, const uint8_t *coeffs, uint64_t n, c
 
 // the multiplication over resident bases (msm_resident) and the object (struct zk_kzg): kzg_internal.hpp
 
-// counts the launches of one call into the object
-struct LaunchCount {
-    zk_kzg *k;
-    uint64_t at;
-    explicit LaunchCount(zk_kzg *k_) : k(k_), at(g_kernel_launches.load(std::memory_order_relaxed)) {}
-    ~LaunchCount() { k->last_launches = (uint32_t)(g_kernel_launches.load(std::memory_order_relaxed) - at); }
-};
-
 // ptengine.hpp's pass over n points of section `sec` from its point `first` on; psi (section 3): the subgroup test too.
 // There the two points go through both kernels before the words are read: point 0 is the generator (compared before), so
 // point 1 is the only one either kernel can name, and the pick's order (hostutil.hpp) says which kind comes first.
@@ -364,7 +356,7 @@ void kzg_commit(zk_kzg *k, uint8_t *out, const uint8_t *coeffs, uint64_t n, uint
     check_polys("zk_kzg_commit", coeffs, n, m);
     std::lock_guard<std::mutex> lock(k->mu);
     DeviceGuard g(k->device);
-    LaunchCount lc(k);
+    LaunchCount lc(k->last_launches);
     hipStream_t s = k->st->s;
     const G1Affine *bases = basis == ZK_KZG_LAGRANGE ? k->lag.p : k->tau.p;
     for (uint64_t p = 0; p < m; p++) {
@@ -385,7 +377,7 @@ void kzg_open(zk_kzg *k, uint8_t *ys, uint8_t *proofs, const uint8_t *coeffs, ui
     if (badz < m) throw std::invalid_argument("zk_kzg_open: z " + std::to_string(badz) + " is not below r");
     std::lock_guard<std::mutex> lock(k->mu);
     DeviceGuard g(k->device);
-    LaunchCount lc(k);
+    LaunchCount lc(k->last_launches);
     hipStream_t s = k->st->s;
     for (uint64_t p = 0; p < m; p++) {
         HIP_TRY(hipMemcpyAsync(k->sc.p, coeffs + p * n * 32, n * 32, hipMemcpyHostToDevice, s));
@@ -438,7 +430,7 @@ void kzg_verify(zk_kzg *k, const uint8_t *commitments, const uint8_t *zs, const 
     const uint64_t chunk = chunk_jobs(), cap = m < chunk ? m : chunk;
     std::lock_guard<std::mutex> lock(k->mu);
     DeviceGuard g(k->device);
-    LaunchCount lc(k);
+    LaunchCount lc(k->last_launches);
     need_hbm("zk_kzg_verify", OpenBufs::bytes(cap));
     hipStream_t s = k->st->s;
     OpenBufs b;
@@ -472,7 +464,7 @@ void kzg_verify_batch(zk_kzg *k, const uint8_t *commitments, const uint8_t *zs, 
     }
     std::lock_guard<std::mutex> lock(k->mu);
     DeviceGuard g(k->device);
-    LaunchCount lc(k);
+    LaunchCount lc(k->last_launches);
     need_hbm("zk_kzg_verify_batch", OpenBufs::bytes(m) + 2 * m * sizeof(Fr) + (k->bmsm.n == m ? 0 : DevMsm<Fq>::bytes(m)));
     hipStream_t s = k->st->s;
     OpenBufs b;
@@ -536,7 +528,7 @@ void kzg_verify_batch(zk_kzg *k, const uint8_t *commitments, const uint8_t *zs, 
 uint8_t kzg_pair_one(zk_kzg *k, const uint8_t L[64], const uint8_t pi[64]) {
     std::lock_guard<std::mutex> lock(k->mu);
     DeviceGuard g(k->device);
-    LaunchCount lc(k);
+    LaunchCount lc(k->last_launches);
     hipStream_t s = k->st->s;
     DevBuf<G1Affine> dl, dp;
     DevBuf<uint32_t> st;
@@ -571,28 +563,19 @@ int zk_kzg_create(zk_kzg **out, const zk_kzg_view *view, uint64_t max_coeffs, ui
     });
 }
 
-void zk_kzg_destroy(zk_kzg *k) {
-    if (!k) return;
-    int prev = -1;
-    const bool had = hipGetDevice(&prev) == hipSuccess;
-    (void)hipSetDevice(k->device);
-    delete k;
-    if (had) (void)hipSetDevice(prev);
-}
+void zk_kzg_destroy(zk_kzg *k) { destroy_on_device(k); }
 
 int zk_kzg_info(zk_kzg *k, zk_kzg_plan *plan) {
     return guarded([&] {
         if (!k || !plan) throw std::invalid_argument("null argument");
-        if (plan->size < 4) throw std::invalid_argument("zk_kzg_info: plan->size is not set");
-        zk_kzg_plan p{};
-        std::lock_guard<std::mutex> lock(k->mu);
-        p.size = plan->size < sizeof p ? plan->size : (uint32_t)sizeof p;
-        p.lagrange_log_n = k->lag_log;
-        p.max_coeffs = k->max_coeffs;
-        p.device_bytes = k->bytes();
-        p.seg = seg_in_effect();
-        p.last_launches = k->last_launches;
-        memcpy(plan, &p, p.size);
+        info_into("zk_kzg_info", plan, [&](zk_kzg_plan &p) {
+            std::lock_guard<std::mutex> lock(k->mu);
+            p.lagrange_log_n = k->lag_log;
+            p.max_coeffs = k->max_coeffs;
+            p.device_bytes = k->bytes();
+            p.seg = seg_in_effect();
+            p.last_launches = k->last_launches;
+        });
     });
 }
 

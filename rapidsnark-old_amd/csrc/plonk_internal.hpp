@@ -1,9 +1,58 @@
-// What plonkprove.hip chains (the five rounds of a PLONK proof on one stream, nothing per-row crossing PCIe): the device-
-// pointer cores of frscan.hip (round 2), plonkquot.hip (round 3) and plonkopen.hip (rounds 4 and 5), and kzg.hip's one-lane
-// pairing check.  Each core stays in its unit with its kernels; the public entries of those units are thin wrappers over
-// the same cores (upload, core, download).  Every core reads its unit's own knob (ZKHIP_SCAN_SEG, _QUOT_SEG, _OPEN_SEG).
+// What the PLONK units share and what plonkprove.hip chains.  First the one validation of a zk_plonk_circuit_view and of the
+// coset's shift, for zk_plonk_circuit_create, zk_plonk_opening_create and zk_plonk_prover_create (every message under the
+// calling entry's name).  Then, unit by unit, what the prover chains (the five rounds of a PLONK proof on one stream,
+// nothing per-row crossing PCIe): the device-pointer cores of frscan.hip (round 2), plonkquot.hip (round 3) and plonkopen.hip
+// (rounds 4 and 5), the entries that make a circuit and an opening object from a checked view, and kzg.hip's one-lane
+// pairing check, the last step of plonkverify.hip.  Each core stays in its unit with its kernels; the public entries of
+// those units are thin wrappers over the same cores (check or upload, core, download).  Every core reads its unit's own knob
+// (ZKHIP_SCAN_SEG, _QUOT_SEG, _OPEN_SEG).  The transcript and the scalars prover and verifier share: plonk_transcript.hpp.
 #pragma once
 #include "kzg_internal.hpp"
+
+// ---------------------------------------------------------------- a checked zk_plonk_circuit_view
+constexpr uint32_t PLONK_MAX_LOG_N = 25, PLONK_CIRC_VECS = 8;
+struct CheckedView {
+    uint32_t log_n;
+    uint64_t n;
+    bool lagrange;
+    const uint8_t *vec[PLONK_CIRC_VECS];              // ql qr qm qo qc s1 s2 s3, the view's order: n rows below r each
+    Fr k1, k2;                                        // Montgomery
+};
+// In two steps, since every entry checks its own arguments between them: the dimensions (log_n, basis) ..
+inline CheckedView checked_view_dims(const char *who, const zk_plonk_circuit_view *v, uint32_t min_log_n) {
+    if (v->log_n < min_log_n || v->log_n > PLONK_MAX_LOG_N)
+        throw std::invalid_argument(std::string(who) + ": log_n " + std::to_string(v->log_n) + " is outside " + std::to_string(min_log_n) + " .. 25");
+    if (v->basis != ZK_KZG_MONOMIAL && v->basis != ZK_KZG_LAGRANGE) throw std::invalid_argument(std::string(who) + ": basis " + std::to_string(v->basis) + " is unknown");
+    CheckedView cv{};
+    cv.log_n = v->log_n, cv.n = 1ull << v->log_n, cv.lagrange = v->basis == ZK_KZG_LAGRANGE;
+    return cv;
+}
+// .. then the eight vectors, k1 and k2
+inline void checked_view_rows(const char *who, const zk_plonk_circuit_view *v, CheckedView &cv) {
+    const uint8_t *vec[PLONK_CIRC_VECS] = {v->ql, v->qr, v->qm, v->qo, v->qc, v->s1, v->s2, v->s3};
+    static const char *const names[PLONK_CIRC_VECS] = {"ql", "qr", "qm", "qo", "qc", "s1", "s2", "s3"};
+    for (uint32_t j = 0; j < PLONK_CIRC_VECS; j++) {
+        if (!vec[j]) throw std::invalid_argument("null argument");
+        check_below_r(who, names[j], vec[j], cv.n);
+        cv.vec[j] = vec[j];
+    }
+    cv.k1 = checked_one(who, "k1", v->k1);
+    cv.k2 = checked_one(who, "k2", v->k2);
+}
+// the coset's shift g (a view's: NULL is 5) and g^n, Montgomery.  g^(4n) = 1: the coset is the 4n-th roots of unity themselves
+// and Z_H vanishes on a quarter of it
+struct CheckedShift {
+    Fr g, gn;
+};
+inline CheckedShift checked_shift(const char *who, const uint8_t *shift, uint32_t log_n) {
+    CheckedShift c;
+    c.g = shift ? checked_one(who, "shift", shift) : fr_small(5);
+    if (c.g.is_zero()) throw std::invalid_argument(std::string(who) + ": shift is zero");
+    c.gn = c.g;
+    for (uint32_t i = 0; i < log_n; i++) c.gn = Fr::sqr(c.gn);
+    if (Fr::sqr(Fr::sqr(c.gn)) == Fr::one()) throw std::invalid_argument(std::string(who) + ": shift^(4n) is 1: Z_H vanishes on the coset");
+    return c;
+}
 
 // ---------------------------------------------------------------- kzg.hip
 // ZK_VERIFY_OK iff e(L, G2) = e(pi, [tau]G2), else ZK_VERIFY_INVALID; L, pi: points of the curve, the file's form
@@ -24,6 +73,8 @@ bool plonk_perm_dev(PlonkPerm *p, Fr *z, uint8_t last[32], const Fr *wires, cons
 // ---------------------------------------------------------------- plonkquot.hip
 constexpr uint32_t PLONK_ROWS = 5;                    // a, b, c, z, pi
 uint32_t plonk_quot_seg();
+// zk_plonk_circuit_create past its checks: the public entry checks its view and calls this, a prover calls it with its own
+zk_plonk_circuit *plonk_circuit_make(const CheckedView &cv, const CheckedShift &shift, int32_t device);
 uint64_t plonk_circuit_need_bytes(uint32_t log_n);
 size_t plonk_circuit_bytes(const zk_plonk_circuit *c);
 // where round 3 reads its rows: a | b | c | z (| pi) back to back, lens[] standard rows each (20n rows of room)
@@ -40,6 +91,8 @@ void plonk_circuit_interpolate_dev(zk_plonk_circuit *c, Fr *const out[], const F
 
 // ---------------------------------------------------------------- plonkopen.hip
 uint32_t plonk_open_seg();
+// zk_plonk_opening_create past its checks, on the kzg's device: cv.n + 6 <= the kzg's max_coeffs is the caller's check too
+zk_plonk_opening *plonk_opening_make(zk_kzg *kzg, const CheckedView &cv);
 uint64_t plonk_opening_need_bytes(uint64_t n, uint64_t cap, bool lagrange);
 size_t plonk_opening_bytes(const zk_plonk_opening *o);
 Fr *plonk_opening_wit(zk_plonk_opening *o, uint32_t j);          // a, b, c, z: max_coeffs rows each

@@ -16,20 +16,22 @@
 // Lane map of k_poly_eval and k_plonk_linearise: plonkquot.hip's.  T lanes in the grid (a multiple of 256), lane l takes the
 // coefficients l, l + T, l + 2T, .. : `seg` of them (ZKHIP_OPEN_SEG, read at every call), so neighbouring lanes touch
 // neighbouring rows at any seg.  An evaluating lane runs Horner in z^T (the host's) and multiplies ONCE by z^l, from the bits
-// of l over a host-made record of z^(2^b).  The lanes' sums meet by shuffles within a wave, in LDS across the four waves, one
+// of l over a host-made record of z^(2^b) (lanepow.hpp).  The lanes' sums meet by shuffles within a wave, in LDS across the four waves, one
 // row per workgroup goes to a vector of partial sums, and k_poly_eval_finish (a workgroup per polynomial) adds those.  No
 // atomics; the sums are exact field additions, so no byte depends on seg or on scheduling.
 //
 // Form: field.hpp's 8 x 32-bit Fr, as kzg.hip's division.  Every vector stays in STANDARD form: the scalars and the powers
 // are Montgomery, and a Montgomery product of a standard value with such a scalar is standard, so F is what the division
 // reads and the quotient what the sort of the multiplication reads.  One operand term per reduction: no ranges to state.
+#include "lanepow.hpp"
 #include "plonk_internal.hpp"
+#include "plonk_transcript.hpp"
 
 namespace {
 
 constexpr uint32_t OP_WG = 256;
 constexpr uint32_t DEFAULT_SEG = 16, MAX_SEG = 4096;  // the default: profiles/plonk_opening_timing.txt, the best whole call at log_n 22 (at 18 seg 4's is 10 % shorter)
-constexpr uint32_t MIN_LOG_N = 1, MAX_LOG_N = 25, POW_TAB = 32, MAX_GRID_Y = 65535;
+constexpr uint32_t MAX_GRID_Y = 65535;
 constexpr uint32_t CIRC_VECS = 8, WIT_VECS = 4, T_VECS = 3, EVALS = 6;
 enum { C_QL, C_QR, C_QM, C_QO, C_QC, C_S1, C_S2, C_S3 };           // the resident coefficient rows, the view's order
 enum { W_A, W_B, W_C, W_Z };                                        // round 4's
@@ -37,11 +39,8 @@ enum { W_A, W_B, W_C, W_Z };                                        // round 4's
 enum { R_QM, R_QL, R_QR, R_QO, R_Z, R_S3, R_TLO, R_TMID, R_THI, R_A, R_B, R_C, R_S1, R_S2, LIN_SCALED, R_QC = LIN_SCALED, LIN_ROWS };
 
 // ---------------------------------------------------------------- device
-// The powers of one point z for T lanes, Montgomery: z^T and z^(2^b)
-struct EvalConsts {
-    Fr step;
-    Fr tab[POW_TAB];
-};
+// The powers of one point z for T lanes, Montgomery: z^T and z^(2^b) (lanepow.hpp)
+typedef PowTab EvalConsts;
 struct EvalJob {
     const Fr *c;                                      // n coefficients, standard
     uint64_t n;
@@ -150,13 +149,7 @@ uint32_t blocks_of(uint64_t n, uint32_t seg) { return nblocks(n, OP_WG * seg); }
 
 // the record of one point z (Montgomery) for T lanes
 EvalConsts eval_consts(Fr z, uint64_t lanes) {
-    EvalConsts k;
-    k.step = fr_pow(z, lanes);
-    for (uint32_t b = 0; b < POW_TAB; b++) {
-        k.tab[b] = z;
-        z = Fr::sqr(z);
-    }
-    return k;
+    return pow_tab(z, lanes, [](Fr a) { return a; });
 }
 
 // ys[j] = p_j(z_j) for m jobs on the device: two launches for every MAX_GRID_Y of them (a job names its point's record by
@@ -169,12 +162,6 @@ void launch_eval(Fr *ys, Fr *partials, const EvalJob *jobs, const EvalConsts *co
     }
     ZK_LAUNCH_OK("polynomial evaluation");
 }
-
-void check_below_r(const char *who, const char *what, const uint8_t *v, uint64_t n) {
-    const uint64_t bad = first_not_below_r(v, n);
-    if (bad < n) throw std::invalid_argument(std::string(who) + ": " + what + " " + std::to_string(bad) + " is not below r");
-}
-Fr checked_one(const char *who, const char *what, const uint8_t *v) { return checked_scalar(v, std::string(who) + ": " + what); }
 
 void fr_poly_eval(uint8_t *ys, const uint8_t *coeffs, uint64_t n, uint64_t m, const uint8_t *zs, int32_t device) {
     const char *who = "zk_fr_poly_eval";
@@ -251,45 +238,25 @@ struct zk_plonk_opening {
 
 namespace {
 
-struct LaunchCount {
-    zk_plonk_opening *o;
-    uint64_t at;
-    explicit LaunchCount(zk_plonk_opening *o_) : o(o_), at(g_kernel_launches.load(std::memory_order_relaxed)) {}
-    ~LaunchCount() { o->last_launches = (uint32_t)(g_kernel_launches.load(std::memory_order_relaxed) - at); }
-};
-
 uint64_t resident_bytes(uint64_t n, uint64_t cap) {
     return (CIRC_VECS * n + (WIT_VECS + T_VECS + 2) * cap + (uint64_t)EVALS * blocks_of(cap, 1) + EVALS + 2) * sizeof(Fr) +
            DivWork::groups_of(cap, 1) * 6 * sizeof(Fr) + EVALS * sizeof(EvalJob) + 2 * sizeof(EvalConsts) + sizeof(LinConsts) + 65536;
 }
 
-zk_plonk_opening *opening_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, int32_t device) {
+// the object from a view that was checked and fits the kzg (plonk_internal.hpp: the public entry's, or a prover's)
+zk_plonk_opening *opening_make(zk_kzg *kzg, const CheckedView &cv) {
     const char *who = "zk_plonk_opening_create";
-    if (!kzg || !v) throw std::invalid_argument("null argument");
-    if (v->log_n < MIN_LOG_N || v->log_n > MAX_LOG_N)
-        throw std::invalid_argument(std::string(who) + ": log_n " + std::to_string(v->log_n) + " is outside 1 .. 25");
-    if (v->basis != ZK_KZG_MONOMIAL && v->basis != ZK_KZG_LAGRANGE) throw std::invalid_argument(std::string(who) + ": basis " + std::to_string(v->basis) + " is unknown");
-    const uint64_t n = 1ull << v->log_n, cap = kzg->max_coeffs;
-    if (n + 6 > cap)
-        throw std::invalid_argument(std::string(who) + ": n + 6 = " + std::to_string(n + 6) + " exceeds the kzg's max_coeffs = " + std::to_string(cap));
-    if (device >= 0 && device != kzg->device)
-        throw std::invalid_argument(std::string(who) + ": device " + std::to_string(device) + " is not the kzg's device " + std::to_string(kzg->device));
-    const uint8_t *vec[CIRC_VECS] = {v->ql, v->qr, v->qm, v->qo, v->qc, v->s1, v->s2, v->s3};
-    static const char *const names[CIRC_VECS] = {"ql", "qr", "qm", "qo", "qc", "s1", "s2", "s3"};
-    for (uint32_t j = 0; j < CIRC_VECS; j++) {
-        if (!vec[j]) throw std::invalid_argument("null argument");
-        check_below_r(who, names[j], vec[j], n);
-    }
+    const uint8_t *const *vec = cv.vec;
+    const uint64_t n = cv.n, cap = kzg->max_coeffs;
     std::unique_ptr<zk_plonk_opening> o(new zk_plonk_opening());
-    o->kzg = kzg, o->device = kzg->device, o->log_n = v->log_n, o->n = n, o->cap = cap;
-    o->k1 = checked_one(who, "k1", v->k1);
-    o->k2 = checked_one(who, "k2", v->k2);
-    o->w = root_of_unity(v->log_n);
+    o->kzg = kzg, o->device = kzg->device, o->log_n = cv.log_n, o->n = n, o->cap = cap;
+    o->k1 = cv.k1, o->k2 = cv.k2;
+    o->w = root_of_unity(cv.log_n);
     DeviceGuard dg(o->device);
-    need_hbm(who, resident_bytes(n, cap) + (v->basis == ZK_KZG_LAGRANGE ? 2 * n * sizeof(Fr) : 0));
+    need_hbm(who, resident_bytes(n, cap) + (cv.lagrange ? 2 * n * sizeof(Fr) : 0));
     o->st.reset(new Stream());
     hipStream_t s = o->st->s;
-    LaunchCount lc(o.get());
+    LaunchCount lc(o->last_launches);
     o->circ.alloc(CIRC_VECS * n);
     o->wit.alloc(WIT_VECS * cap);
     o->tp.alloc(T_VECS * cap);
@@ -302,7 +269,7 @@ zk_plonk_opening *opening_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, in
     o->ek.alloc(2);
     o->lk.alloc(1);
     o->div.size(DivWork::groups_of(cap, 1));
-    if (v->basis == ZK_KZG_LAGRANGE) {
+    if (cv.lagrange) {
         // values at w^j -> coefficients: zk_fr_ntt's inverse transform on a copy, vector by vector (once in the object's life)
         std::vector<uint8_t> co(n * 32);
         for (uint32_t j = 0; j < CIRC_VECS; j++) {
@@ -316,6 +283,18 @@ zk_plonk_opening *opening_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, in
         HIP_TRY(hipStreamSynchronize(s));
     }
     return o.release();
+}
+
+zk_plonk_opening *opening_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, int32_t device) {
+    const char *who = "zk_plonk_opening_create";
+    if (!kzg || !v) throw std::invalid_argument("null argument");
+    CheckedView cv = checked_view_dims(who, v, 1);
+    if (cv.n + 6 > kzg->max_coeffs)
+        throw std::invalid_argument(std::string(who) + ": n + 6 = " + std::to_string(cv.n + 6) + " exceeds the kzg's max_coeffs = " + std::to_string(kzg->max_coeffs));
+    if (device >= 0 && device != kzg->device)
+        throw std::invalid_argument(std::string(who) + ": device " + std::to_string(device) + " is not the kzg's device " + std::to_string(kzg->device));
+    checked_view_rows(who, v, cv);
+    return opening_make(kzg, cv);
 }
 
 // Round 4 over the rows already in o->wit, len[] of them each: the two launches, the six values to the host, and the state
@@ -359,44 +338,25 @@ void plonk_evaluate(zk_plonk_opening *o, uint8_t *evals, const uint8_t *const in
     const Fr ze = checked_one(who, "zeta", zeta);
     std::lock_guard<std::mutex> lock(o->mu);
     DeviceGuard dg(o->device);
-    LaunchCount lc(o);
+    LaunchCount lc(o->last_launches);
     hipStream_t s = o->st->s;
     o->pending = false;
     for (uint32_t j = 0; j < WIT_VECS; j++) HIP_TRY(hipMemcpyAsync(o->wit.p + j * o->cap, in[j], len[j] * sizeof(Fr), hipMemcpyHostToDevice, s));
     evaluate_dev(o, evals, len, ze, seg, s);
 }
 
-// What the host makes of the six values and the challenges: F's scalars, the constant of index 0, and E.  One inversion
+// What the host makes of the six values and the challenges (plonk_transcript.hpp's, the verifier's too): F's scalars, the
+// constant of index 0, and E.  One inversion
 LinConsts lin_consts(const zk_plonk_opening &o, Fr pi_zeta, Fr alpha, Fr beta, Fr gamma, Fr v, Fr *E) {
-    const Fr one = Fr::one(), ze = o.zeta;
-    const Fr a = o.evals[0], b = o.evals[1], c = o.evals[2], s1 = o.evals[3], s2 = o.evals[4], zw = o.evals[5];
-    Fr zn = ze;
-    for (uint32_t i = 0; i < o.log_n; i++) zn = Fr::sqr(zn);
-    const Fr zh = Fr::sub(zn, one);                    // Z_H(zeta)
-    Fr l1;                                            // L1(zeta); zeta^n = 1: 1 at zeta = 1, else 0
-    if (ze == one) l1 = one;
-    else if (zh.is_zero()) l1 = Fr::zero();
-    else l1 = Fr::mul(zh, Fr::inv(Fr::mul(fr_small(o.n), Fr::sub(ze, one))));
-    const Fr alpha2 = Fr::sqr(alpha), bz = Fr::mul(beta, ze);
-    const Fr f1 = Fr::add(Fr::add(a, bz), gamma), f2 = Fr::add(Fr::add(b, Fr::mul(bz, o.k1)), gamma), f3 = Fr::add(Fr::add(c, Fr::mul(bz, o.k2)), gamma);
-    const Fr g12 = Fr::mul(Fr::add(Fr::add(a, Fr::mul(beta, s1)), gamma), Fr::add(Fr::add(b, Fr::mul(beta, s2)), gamma));
-    const Fr g12zw_alpha = Fr::mul(Fr::mul(g12, zw), alpha);
-    const Fr al2l1 = Fr::mul(alpha2, l1);
+    AtZeta z = zeta_powers(o.log_n, o.zeta);
+    z.pi = pi_zeta;
+    const LinScalars L = lin_scalars(o.evals, z, o.zeta, o.k1, o.k2, alpha, beta, gamma, v);
     LinConsts k;
-    k.s[R_QM] = Fr::mul(a, b), k.s[R_QL] = a, k.s[R_QR] = b, k.s[R_QO] = c;
-    k.s[R_Z] = Fr::add(Fr::mul(alpha, Fr::mul(Fr::mul(f1, f2), f3)), al2l1);
-    k.s[R_S3] = Fr::neg(Fr::mul(g12zw_alpha, beta));
-    k.s[R_TLO] = Fr::neg(zh);
-    k.s[R_TMID] = Fr::neg(Fr::mul(zh, zn));
-    k.s[R_THI] = Fr::neg(Fr::mul(zh, Fr::sqr(zn)));
-    Fr vp = v;
-    *E = Fr::zero();
-    for (int j = 0; j < 5; j++) {                      // v a + v^2 b + v^3 c + v^4 s1 + v^5 s2
-        k.s[R_A + j] = vp;
-        *E = Fr::add(*E, Fr::mul(vp, o.evals[j]));
-        vp = Fr::mul(vp, v);
-    }
-    k.c0 = Fr::from_mont(Fr::sub(Fr::sub(pi_zeta, Fr::mul(g12zw_alpha, Fr::add(c, gamma))), al2l1));
+    k.s[R_QM] = L.qm, k.s[R_QL] = o.evals[0], k.s[R_QR] = o.evals[1], k.s[R_QO] = o.evals[2];
+    k.s[R_Z] = L.z, k.s[R_S3] = L.s3, k.s[R_TLO] = L.tlo, k.s[R_TMID] = L.tmid, k.s[R_THI] = L.thi;
+    for (int j = 0; j < 5; j++) k.s[R_A + j] = L.v[j];
+    k.c0 = Fr::from_mont(L.c0);
+    *E = L.E;
     return k;
 }
 
@@ -469,7 +429,7 @@ void plonk_open(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uin
     if (!o->pending) throw std::invalid_argument(std::string(who) + ": no evaluation is pending: call zk_plonk_evaluate first");
     o->pending = false;
     DeviceGuard dg(o->device);
-    LaunchCount lc(o);
+    LaunchCount lc(o->last_launches);
     hipStream_t s = o->st->s;
     for (uint32_t j = 0; j < T_VECS; j++) HIP_TRY(hipMemcpyAsync(o->tp.p + j * o->cap, t[j], tlen[j] * sizeof(Fr), hipMemcpyHostToDevice, s));
     open_dev(o, w_zeta, w_zeta_omega, r_zeta, f, f_len, tlen, pz, al, be, ga, vv, seg, dseg, s);
@@ -479,6 +439,7 @@ void plonk_open(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uin
 
 // ---------------------------------------------------------------- what plonkprove.hip chains (plonk_internal.hpp)
 uint32_t plonk_open_seg() { return seg_in_effect(); }
+zk_plonk_opening *plonk_opening_make(zk_kzg *kzg, const CheckedView &cv) { return opening_make(kzg, cv); }
 uint64_t plonk_opening_need_bytes(uint64_t n, uint64_t cap, bool lagrange) { return resident_bytes(n, cap) + (lagrange ? 2 * n * sizeof(Fr) : 0); }
 size_t plonk_opening_bytes(const zk_plonk_opening *o) { return o->bytes(); }
 Fr *plonk_opening_wit(zk_plonk_opening *o, uint32_t j) { return o->wit.p + j * o->cap; }
@@ -512,28 +473,19 @@ int zk_plonk_opening_create(zk_plonk_opening **out, zk_kzg *kzg, const zk_plonk_
     });
 }
 
-void zk_plonk_opening_destroy(zk_plonk_opening *o) {
-    if (!o) return;
-    int prev = -1;
-    const bool switched = hipGetDevice(&prev) == hipSuccess && hipSetDevice(o->device) == hipSuccess;
-    delete o;
-    if (switched) (void)hipSetDevice(prev);
-}
+void zk_plonk_opening_destroy(zk_plonk_opening *o) { destroy_on_device(o); }
 
 int zk_plonk_opening_info(zk_plonk_opening *o, zk_plonk_opening_plan *plan) {
     return guarded([&] {
         if (!o || !plan) throw std::invalid_argument("null argument");
-        if (plan->size < 4) throw std::invalid_argument("zk_plonk_opening_info: plan->size is not set");
-        zk_plonk_opening_plan p{};
-        const uint32_t seg = seg_in_effect();
-        std::lock_guard<std::mutex> lock(o->mu);
-        p.size = plan->size < sizeof p ? plan->size : (uint32_t)sizeof p;
-        p.log_n = o->log_n;
-        p.device_bytes = o->bytes();
-        p.seg = seg;
-        p.last_launches = o->last_launches;
-        p.pending = o->pending ? 1u : 0u;
-        memcpy(plan, &p, p.size);
+        info_into("zk_plonk_opening_info", plan, [&](zk_plonk_opening_plan &p) {
+            p.seg = seg_in_effect();
+            std::lock_guard<std::mutex> lock(o->mu);
+            p.log_n = o->log_n;
+            p.device_bytes = o->bytes();
+            p.last_launches = o->last_launches;
+            p.pending = o->pending ? 1u : 0u;
+        });
     });
 }
 

@@ -1,7 +1,8 @@
-// PLONK prover and verifier (include/zkhip.h, section "PLONK prover and verifier"): the five rounds of a three-column proof
-// chained on one stream, the Fiat-Shamir transcript (Keccak-256, on the host: a few hundred bytes a round) and the
-// verifier.  Nothing in the reference corresponds to it (it proves Groth16 only); the counterpart is snarkjs's PLONK
-// prover and verifier.  DESIGN.md section 31 states the residency, the launches and what was measured.
+// PLONK prover (include/zkhip.h, section "PLONK prover and verifier"): the five rounds of a three-column proof chained on
+// one stream.  The Fiat-Shamir transcript (Keccak-256, on the host: a few hundred bytes a round) and what prover and verifier
+// both make of zeta are plonk_transcript.hpp's; the verifier is plonkverify.hip.  Nothing in the reference corresponds to
+// it (it proves Groth16 only); the counterpart is snarkjs's PLONK prover.  DESIGN.md section 31 states the residency, the
+// launches and what was measured.
 //
 // The rounds are the existing units' device-pointer cores (plonk_internal.hpp): frscan.hip's permutation product,
 // plonkquot.hip's quotient and inverse transform of size n, plonkopen.hip's evaluations, linearisation and openings, kzg.hip's
@@ -19,16 +20,15 @@
 #include <sys/random.h>
 
 #include "plonk_internal.hpp"
+#include "plonk_transcript.hpp"
 
 namespace {
 
 constexpr uint32_t PV_WG = 256;
-constexpr uint32_t MIN_LOG_N = 3, MAX_LOG_N = 25;
-constexpr uint32_t CIRC_VECS = 8, EVALS = 6, POINTS = 9, BLINDS = ZK_PLONK_BLINDS;
+constexpr uint32_t MIN_LOG_N = 3;
+constexpr uint32_t CIRC_VECS = PLONK_CIRC_VECS, POINTS = PLONK_POINTS, BLINDS = ZK_PLONK_BLINDS;
 constexpr uint32_t ROUNDS = 5;
 enum { C_QL, C_QR, C_QM, C_QO, C_QC, C_S1, C_S2, C_S3 };           // the view's order
-enum { P_A, P_B, P_C, P_Z, P_TLO, P_TMID, P_THI, P_WZ, P_WZW };     // the proof's points
-static_assert(ZK_PLONK_PROOF_BYTES == POINTS * 64 + EVALS * 32, "layout");
 
 // ---------------------------------------------------------------- device
 // out[v][i] = wit[map[v][i]] for v < 3; out[3][i] = -pub[i] for i < n_public, else 0 (row 3 only when the grid has it)
@@ -100,198 +100,7 @@ __global__ __launch_bounds__(PV_WG) void k_plonk_split(SplitArgs A) {
     }
 }
 
-// ---------------------------------------------------------------- host: Keccak-256
-const uint64_t KECCAK_RC[24] = {0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull,
-                                0x0000000080000001ull, 0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull,
-                                0x0000000080008009ull, 0x000000008000000aull, 0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull,
-                                0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull, 0x000000000000800aull, 0x800000008000000aull,
-                                0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
-const int KECCAK_ROT[24] = {1, 3, 6, 10, 15, 21, 28, 36, 45, 55, 2, 14, 27, 41, 56, 8, 25, 43, 62, 18, 39, 61, 20, 44};
-const int KECCAK_PIL[24] = {10, 7, 11, 17, 18, 3, 5, 16, 8, 21, 24, 4, 15, 23, 19, 13, 12, 2, 20, 14, 22, 9, 6, 1};
-
-inline uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-
-void keccak_f(uint64_t st[25]) {
-    for (int round = 0; round < 24; round++) {
-        uint64_t bc[5];
-        for (int i = 0; i < 5; i++) bc[i] = st[i] ^ st[i + 5] ^ st[i + 10] ^ st[i + 15] ^ st[i + 20];
-        for (int i = 0; i < 5; i++) {
-            const uint64_t t = bc[(i + 4) % 5] ^ rotl64(bc[(i + 1) % 5], 1);
-            for (int j = 0; j < 25; j += 5) st[j + i] ^= t;
-        }
-        uint64_t t = st[1];
-        for (int i = 0; i < 24; i++) {
-            const int j = KECCAK_PIL[i];
-            const uint64_t keep = st[j];
-            st[j] = rotl64(t, KECCAK_ROT[i]);
-            t = keep;
-        }
-        for (int j = 0; j < 25; j += 5) {
-            for (int i = 0; i < 5; i++) bc[i] = st[j + i];
-            for (int i = 0; i < 5; i++) st[j + i] ^= (~bc[(i + 1) % 5]) & bc[(i + 2) % 5];
-        }
-        st[0] ^= KECCAK_RC[round];
-    }
-}
-
-// rate 136 bytes, the original padding 0x01 .. 0x80
-void keccak256(uint8_t out[32], const uint8_t *data, uint64_t len) {
-    constexpr uint64_t RATE = 136;
-    uint64_t st[25] = {0};
-    auto absorb = [&](const uint8_t *block) {
-        for (uint64_t i = 0; i < RATE / 8; i++) {
-            uint64_t w = 0;
-            for (int b = 7; b >= 0; b--) w = (w << 8) | block[i * 8 + b];
-            st[i] ^= w;
-        }
-        keccak_f(st);
-    };
-    while (len >= RATE) {
-        absorb(data);
-        data += RATE;
-        len -= RATE;
-    }
-    uint8_t last[RATE] = {0};
-    if (len) memcpy(last, data, len);
-    last[len] ^= 0x01;
-    last[RATE - 1] ^= 0x80;
-    absorb(last);
-    for (int i = 0; i < 32; i++) out[i] = (uint8_t)(st[i / 8] >> (8 * (i % 8)));
-}
-
-// ---------------------------------------------------------------- host: the transcript
-// the file's form of a coordinate -> its standard value, little-endian words
-Fq fq_plain(const uint8_t c[32]) {
-    Fq x;
-    memcpy(x.v, c, 32);
-    return Fq::from_mont(x);
-}
-
-struct Transcript {
-    std::vector<uint8_t> buf;
-    void words_be(const uint32_t w[8]) {
-        for (int i = 7; i >= 0; i--)
-            for (int b = 3; b >= 0; b--) buf.push_back((uint8_t)(w[i] >> (8 * b)));
-    }
-    void scalar_std(const uint8_t s[32]) {              // 32 bytes little-endian, standard
-        for (int i = 31; i >= 0; i--) buf.push_back(s[i]);
-    }
-    void scalar(const Fr &m) {                          // Montgomery
-        const Fr x = Fr::from_mont(m);
-        words_be(x.v);
-    }
-    void point(const uint8_t p[64]) {                   // the file's form; infinity: 64 zero bytes
-        words_be(fq_plain(p).v);
-        words_be(fq_plain(p + 32).v);
-    }
-    // the digest as a big-endian integer mod r, Montgomery; the buffer is emptied
-    Fr challenge() {
-        uint8_t d[32], le[32];
-        keccak256(d, buf.data(), buf.size());
-        buf.clear();
-        for (int i = 0; i < 32; i++) le[i] = d[31 - i];
-        while (!below(le, FrParams::P)) {               // 2^256 < 6 r: five rounds at the most
-            uint32_t w[8];
-            memcpy(w, le, 32);
-            uint64_t borrow = 0;
-            for (int i = 0; i < 8; i++) {
-                const uint64_t t = (uint64_t)w[i] - FrParams::P[i] - borrow;
-                w[i] = (uint32_t)t;
-                borrow = (t >> 32) & 1;
-            }
-            memcpy(le, w, 32);
-        }
-        return fr_from_std(le);
-    }
-};
-
-struct Challenges {
-    Fr beta, gamma, alpha, zeta, v, u;                // Montgomery
-};
-
-void round1_challenges(Challenges &c, const zk_plonk_vkey &vk, const uint8_t *publics, const uint8_t *pts) {
-    Transcript t;
-    const uint8_t *vkp[CIRC_VECS] = {vk.qm, vk.ql, vk.qr, vk.qo, vk.qc, vk.s1, vk.s2, vk.s3};
-    for (uint32_t j = 0; j < CIRC_VECS; j++) t.point(vkp[j]);
-    for (uint64_t i = 0; i < vk.n_public; i++) t.scalar_std(publics + i * 32);
-    for (uint32_t j = P_A; j <= P_C; j++) t.point(pts + j * 64);
-    c.beta = t.challenge();
-    t.scalar(c.beta);
-    c.gamma = t.challenge();
-}
-void round2_challenge(Challenges &c, const uint8_t *pts) {
-    Transcript t;
-    t.scalar(c.beta), t.scalar(c.gamma), t.point(pts + P_Z * 64);
-    c.alpha = t.challenge();
-}
-void round3_challenge(Challenges &c, const uint8_t *pts) {
-    Transcript t;
-    t.scalar(c.alpha);
-    for (uint32_t j = P_TLO; j <= P_THI; j++) t.point(pts + j * 64);
-    c.zeta = t.challenge();
-}
-void round4_challenge(Challenges &c, const uint8_t *evals) {
-    Transcript t;
-    t.scalar(c.zeta);
-    for (uint32_t j = 0; j < EVALS; j++) t.scalar_std(evals + j * 32);
-    c.v = t.challenge();
-}
-void round5_challenge(Challenges &c, const uint8_t *pts) {
-    Transcript t;
-    t.point(pts + P_WZ * 64), t.point(pts + P_WZW * 64);
-    c.u = t.challenge();
-}
-
-// ---------------------------------------------------------------- host: what prover and verifier both make of zeta
-struct AtZeta {
-    Fr zn, zh, l1, pi;                                // zeta^n, Z_H(zeta), L1(zeta), PI(zeta): Montgomery
-};
-// PI(zeta) = - sum_(i < l) publics[i] L_i(zeta), L_i = w^i Z_H / (n (X - w^i)): l products and ONE inversion (the prefix
-// products of the denominators).  zeta^n = 1: L_i(zeta) is 1 where zeta = w^i and 0 elsewhere
-AtZeta at_zeta(uint32_t log_n, const Fr &ze, const uint8_t *publics, uint64_t l) {
-    AtZeta z;
-    const Fr one = Fr::one(), w = root_of_unity(log_n), nn = fr_small(1ull << log_n);
-    z.zn = ze;
-    for (uint32_t i = 0; i < log_n; i++) z.zn = Fr::sqr(z.zn);
-    z.zh = Fr::sub(z.zn, one);
-    z.pi = Fr::zero();
-    if (z.zh.is_zero()) {
-        z.l1 = ze == one ? one : Fr::zero();
-        Fr wi = one;
-        for (uint64_t i = 0; i < l; i++, wi = Fr::mul(wi, w))
-            if (wi == ze) z.pi = Fr::neg(fr_from_std(publics + i * 32));
-        return z;
-    }
-    z.l1 = Fr::mul(z.zh, Fr::inv(Fr::mul(nn, Fr::sub(ze, one))));
-    if (!l) return z;
-    std::vector<Fr> den(l), pre(l);
-    Fr wi = one, acc = one;
-    for (uint64_t i = 0; i < l; i++, wi = Fr::mul(wi, w)) {
-        den[i] = Fr::mul(nn, Fr::sub(ze, wi));
-        pre[i] = acc;
-        acc = Fr::mul(acc, den[i]);
-    }
-    Fr inv = Fr::inv(acc);
-    // backwards: 1 / den[i] = pre[i] inv, inv *= den[i]; w^i from w^(l-1) down by w^-1
-    const Fr winv = Fr::inv(w);
-    wi = fr_pow(w, l - 1);
-    Fr sum = Fr::zero();
-    for (uint64_t i = l; i-- > 0;) {
-        const Fr li = Fr::mul(wi, Fr::mul(pre[i], inv));          // w^i / (n (zeta - w^i))
-        sum = Fr::add(sum, Fr::mul(fr_from_std(publics + i * 32), li));
-        inv = Fr::mul(inv, den[i]);
-        wi = Fr::mul(wi, winv);
-    }
-    z.pi = Fr::neg(Fr::mul(sum, z.zh));
-    return z;
-}
-
-void check_below_r(const char *who, const char *what, const uint8_t *v, uint64_t n) {
-    const uint64_t bad = first_not_below_r(v, n);
-    if (bad < n) throw std::invalid_argument(std::string(who) + ": " + what + " " + std::to_string(bad) + " is not below r");
-}
-Fr checked_one(const char *who, const char *what, const uint8_t *v) { return checked_scalar(v, std::string(who) + ": " + what); }
-
+// ---------------------------------------------------------------- host
 uint32_t blocks_of(uint64_t n, uint32_t seg) { return nblocks(n, PV_WG * seg); }
 
 }   // namespace
@@ -331,8 +140,6 @@ uint64_t own_need_bytes(uint64_t n, uint64_t n_witness, uint64_t n_public) {
     return 3 * n * sizeof(uint32_t) + (3 * n + 3 + n_witness + n_public + 1 + BLINDS + 4 * n + 2 * n) * sizeof(Fr) + 65536;
 }
 
-uint64_t launches_now() { return g_kernel_launches.load(std::memory_order_relaxed); }
-
 // [p] for `len` standard rows on the device, over the kzg's resident points
 void commit_dev(zk_kzg *k, uint8_t out[64], const Fr *rows, uint64_t len, hipStream_t s) {
     std::lock_guard<std::mutex> kl(k->mu);             // the kzg's points and the work buffers of its multiplication
@@ -343,10 +150,8 @@ zk_plonk_prover *prover_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, cons
                                uint64_t n_witness, uint64_t n_public, int32_t device) {
     const char *who = "zk_plonk_prover_create";
     if (!kzg || !v || !a_map || !b_map || !c_map) throw std::invalid_argument("null argument");
-    if (v->log_n < MIN_LOG_N || v->log_n > MAX_LOG_N)
-        throw std::invalid_argument(std::string(who) + ": log_n " + std::to_string(v->log_n) + " is outside 3 .. 25");
-    if (v->basis != ZK_KZG_MONOMIAL && v->basis != ZK_KZG_LAGRANGE) throw std::invalid_argument(std::string(who) + ": basis " + std::to_string(v->basis) + " is unknown");
-    const uint64_t n = 1ull << v->log_n, cap = kzg->max_coeffs;
+    CheckedView cv = checked_view_dims(who, v, MIN_LOG_N);
+    const uint64_t n = cv.n, cap = kzg->max_coeffs;
     if (n + 6 > cap)
         throw std::invalid_argument(std::string(who) + ": n + 6 = " + std::to_string(n + 6) + " exceeds the kzg's max_coeffs = " + std::to_string(cap));
     if (n_public > n) throw std::invalid_argument(std::string(who) + ": n_public " + std::to_string(n_public) + " exceeds n = " + std::to_string(n));
@@ -361,27 +166,16 @@ zk_plonk_prover *prover_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, cons
             if (maps[j][i] >= n_witness)
                 throw std::invalid_argument(std::string(who) + ": " + mnames[j] + " " + std::to_string(i) + " is " + std::to_string(maps[j][i]) +
                                             ", not below n_witness = " + std::to_string(n_witness));
-    const uint8_t *vec[CIRC_VECS] = {v->ql, v->qr, v->qm, v->qo, v->qc, v->s1, v->s2, v->s3};
-    static const char *const names[CIRC_VECS] = {"ql", "qr", "qm", "qo", "qc", "s1", "s2", "s3"};
-    for (uint32_t j = 0; j < CIRC_VECS; j++) {
-        if (!vec[j]) throw std::invalid_argument("null argument");
-        check_below_r(who, names[j], vec[j], n);
-    }
-    const Fr k1 = checked_one(who, "k1", v->k1), k2 = checked_one(who, "k2", v->k2);
-    if (v->shift) {
-        Fr g = checked_one(who, "shift", v->shift);
-        if (g.is_zero()) throw std::invalid_argument(std::string(who) + ": shift is zero");
-        for (uint32_t i = 0; i < v->log_n + 2; i++) g = Fr::sqr(g);
-        if (g == Fr::one()) throw std::invalid_argument(std::string(who) + ": shift^(4n) is 1: Z_H vanishes on the coset");
-    }
+    checked_view_rows(who, v, cv);
+    const CheckedShift shift = checked_shift(who, v->shift, cv.log_n);
     std::unique_ptr<zk_plonk_prover> p(new zk_plonk_prover());
-    p->kzg = kzg, p->device = kzg->device, p->log_n = v->log_n, p->n = n, p->cap = cap, p->n_witness = n_witness, p->n_public = n_public;
-    const bool lagrange = v->basis == ZK_KZG_LAGRANGE;
+    p->kzg = kzg, p->device = kzg->device, p->log_n = cv.log_n, p->n = n, p->cap = cap, p->n_witness = n_witness, p->n_public = n_public;
+    const bool lagrange = cv.lagrange;
     DeviceGuard dg(p->device);
-    need_hbm(who, plonk_circuit_need_bytes(v->log_n) + plonk_opening_need_bytes(n, cap, lagrange) + plonk_perm_need_bytes(n) + own_need_bytes(n, n_witness, n_public));
+    need_hbm(who, plonk_circuit_need_bytes(cv.log_n) + plonk_opening_need_bytes(n, cap, lagrange) + plonk_perm_need_bytes(n) + own_need_bytes(n, n_witness, n_public));
     const uint64_t at = launches_now();
-    if (zk_plonk_circuit_create(&p->circ, v, p->device) != 0) throw std::runtime_error(std::string(who) + ": " + zk_last_error());
-    if (zk_plonk_opening_create(&p->open, kzg, v, p->device) != 0) throw std::runtime_error(std::string(who) + ": " + zk_last_error());
+    p->circ = plonk_circuit_make(cv, shift, p->device);             // from the view as checked above: its 8n rows are scanned once
+    p->open = plonk_opening_make(kzg, cv);
     p->perm = plonk_perm_new();
     p->st.reset(new Stream());
     hipStream_t s = p->st->s;
@@ -395,12 +189,12 @@ zk_plonk_prover *prover_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, cons
     p->zval.alloc(n);
     p->pic.alloc(n);
     for (int j = 0; j < 3; j++) HIP_TRY(hipMemcpyAsync(p->maps.p + j * n, maps[j], n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    Fr sh[3] = {Fr::from_mont(Fr::one()), Fr::from_mont(k1), Fr::from_mont(k2)};
+    Fr sh[3] = {Fr::from_mont(Fr::one()), Fr::from_mont(cv.k1), Fr::from_mont(cv.k2)};
     HIP_TRY(hipMemcpyAsync(p->shifts.p, sh, sizeof sh, hipMemcpyHostToDevice, s));
     // s1 .. s3 by values at w^i: the view's rows, or zk_fr_ntt's forward transform of their coefficients (once in the object's life)
     std::vector<uint8_t> sv;
     for (int j = 0; j < 3; j++) {
-        const uint8_t *src = vec[C_S1 + j];
+        const uint8_t *src = cv.vec[C_S1 + j];
         if (!lagrange) {
             sv.assign(src, src + n * 32);
             if (zk_fr_ntt(sv.data(), n, 0) != 0) throw std::runtime_error(std::string(who) + ": " + zk_last_error());
@@ -414,7 +208,7 @@ zk_plonk_prover *prover_create(zk_kzg *kzg, const zk_plonk_circuit_view *v, cons
     // the key: the eight commitments in the transcript's order, from the coefficients rounds 4 and 5 keep
     zk_plonk_vkey &vk = p->vk;
     memset(&vk, 0, sizeof vk);
-    vk.size = sizeof vk, vk.log_n = v->log_n, vk.n_public = n_public;
+    vk.size = sizeof vk, vk.log_n = cv.log_n, vk.n_public = n_public;
     memcpy(vk.k1, v->k1, 32);
     memcpy(vk.k2, v->k2, 32);
     memcpy(vk.tau_g2, kzg->g2tau, sizeof vk.tau_g2);
@@ -531,11 +325,13 @@ void plonk_prove_core(zk_plonk_prover *p, const char *who, uint8_t *proof, const
     p->last_launches = (uint32_t)(launches_now() - first);
 }
 
-void plonk_prove(zk_plonk_prover *p, uint8_t *proof, const uint8_t *witness, const uint8_t *publics, const uint8_t *blind) {
-    const char *who = "zk_plonk_prove";
-    if (!p || !proof || !witness || (p->n_public && !publics)) throw std::invalid_argument("null argument");
-    check_below_r(who, "witness", witness, p->n_witness);
-    if (p->n_public) check_below_r(who, "publics", publics, p->n_public);
+// One proof.  wit: `up` values go up; r1cs: they are a circom witness the caller has checked (nVars = up), which the device
+// extends and whose values 1 .. n_public are the publics; else the caller's witness of n_witness values, checked here
+void plonk_prove(zk_plonk_prover *p, const char *who, uint8_t *proof, const uint8_t *wit, uint64_t up, const uint8_t *publics, const uint8_t *blind, bool r1cs) {
+    if (!r1cs) {
+        check_below_r(who, "witness", wit, up);
+        if (p->n_public) check_below_r(who, "publics", publics, p->n_public);
+    }
     uint8_t drawn[BLINDS * 32];
     Wipe wipe{drawn};
     blind = blinds_of(who, blind, drawn);
@@ -545,32 +341,10 @@ void plonk_prove(zk_plonk_prover *p, uint8_t *proof, const uint8_t *witness, con
     DeviceGuard dg(p->device);
     hipStream_t s = p->st->s;
     const uint64_t first = launches_now();
-    HIP_TRY(hipMemcpyAsync(p->wit.p, witness, p->n_witness * sizeof(Fr), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(p->wit.p, wit, up * sizeof(Fr), hipMemcpyHostToDevice, s));
     if (p->n_public) HIP_TRY(hipMemcpyAsync(p->pub.p, publics, p->n_public * sizeof(Fr), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(p->blind.p, blind, BLINDS * sizeof(Fr), hipMemcpyHostToDevice, s));
-    plonk_prove_core(p, who, proof, publics, seg, first);
-}
-
-// a circom witness: its nWires values go up, the device extends them, the publics are w[1 .. 1 + n_public)
-void plonk_prove_r1cs(zk_plonk_prover *p, uint8_t *proof, const uint8_t *wtns, uint32_t nVars, const uint8_t *blind) {
-    const char *who = "zk_plonk_prove_r1cs";
-    if (!p || !proof || !wtns) throw std::invalid_argument("null argument");
-    if (!p->r1cs) throw std::invalid_argument(std::string(who) + ": the prover was not made from an r1cs (zk_plonk_prover_create_r1cs)");
-    plonk_r1cs_check_witness(p->r1cs, who, wtns, nVars);
-    uint8_t drawn[BLINDS * 32];
-    Wipe wipe{drawn};
-    blind = blinds_of(who, blind, drawn);
-    const uint32_t seg = plonk_quot_seg();
-    (void)plonk_perm_seg(), (void)plonk_open_seg(), (void)kzg_seg_in_effect();
-    const uint8_t *publics = wtns + 32;
-    std::lock_guard<std::mutex> lock(p->mu);
-    DeviceGuard dg(p->device);
-    hipStream_t s = p->st->s;
-    const uint64_t first = launches_now();
-    HIP_TRY(hipMemcpyAsync(p->wit.p, wtns, (size_t)nVars * sizeof(Fr), hipMemcpyHostToDevice, s));
-    if (p->n_public) HIP_TRY(hipMemcpyAsync(p->pub.p, publics, p->n_public * sizeof(Fr), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(p->blind.p, blind, BLINDS * sizeof(Fr), hipMemcpyHostToDevice, s));
-    plonk_r1cs_extend_dev(p->r1cs, p->wit.p, s);
+    if (r1cs) plonk_r1cs_extend_dev(p->r1cs, p->wit.p, s);
     plonk_prove_core(p, who, proof, publics, seg, first);
 }
 
@@ -598,86 +372,9 @@ zk_plonk_prover *prover_create_r1cs(zk_kzg *kzg, zk_plonk_r1cs *c, const uint8_t
     return p;
 }
 
-// ---------------------------------------------------------------- the verifier
-typedef Pt<Fq> P1;
-
-// a point of the curve in the file's form (or infinity), both coordinates below q
-bool g1_well_formed(const uint8_t p[64]) {
-    static const uint8_t zero[64] = {0};
-    if (memcmp(p, zero, 64) == 0) return true;
-    if (!below(p, FqParams::P) || !below(p + 32, FqParams::P)) return false;
-    Fq x, y;
-    memcpy(x.v, p, 32);
-    memcpy(y.v, p + 32, 32);
-    return Fq::sqr(y) == Fq::add(Fq::mul(Fq::sqr(x), x), curve_b<Fq>());
-}
-
-void plonk_verify(zk_kzg *kzg, const zk_plonk_vkey *vk, const uint8_t *proof, const uint8_t *publics, uint8_t *verdict) {
-    const char *who = "zk_plonk_verify";
-    if (!kzg || !vk || !proof || !verdict || (vk->n_public && !publics)) throw std::invalid_argument("null argument");
-    if (vk->size != sizeof(zk_plonk_vkey)) throw std::invalid_argument(std::string(who) + ": vk->size is not sizeof(zk_plonk_vkey)");
-    if (vk->log_n < MIN_LOG_N || vk->log_n > MAX_LOG_N) throw std::invalid_argument(std::string(who) + ": log_n " + std::to_string(vk->log_n) + " is outside 3 .. 25");
-    const uint64_t n = 1ull << vk->log_n;
-    if (vk->n_public > n) throw std::invalid_argument(std::string(who) + ": n_public " + std::to_string(vk->n_public) + " exceeds n = " + std::to_string(n));
-    if (memcmp(vk->tau_g2, kzg->g2tau, sizeof vk->tau_g2) != 0) throw std::invalid_argument(std::string(who) + ": the key's [tau]G2 is not the kzg's");
-    const Fr k1 = checked_one(who, "k1", vk->k1), k2 = checked_one(who, "k2", vk->k2);
-    const uint8_t *vkp[CIRC_VECS] = {vk->qm, vk->ql, vk->qr, vk->qo, vk->qc, vk->s1, vk->s2, vk->s3};
-    for (uint32_t j = 0; j < CIRC_VECS; j++)
-        if (!g1_well_formed(vkp[j])) throw std::invalid_argument(std::string(who) + ": a commitment of the key is not a point of the curve");
-    const uint8_t *pts = proof, *evals = proof + POINTS * 64;
-    *verdict = ZK_VERIFY_MALFORMED;
-    for (uint32_t j = 0; j < POINTS; j++)
-        if (!g1_well_formed(pts + j * 64)) return;
-    if (first_not_below_r(evals, EVALS) < EVALS) return;
-    if (first_not_below_r(publics, vk->n_public) < vk->n_public) return;
-
-    Challenges ch;
-    round1_challenges(ch, *vk, publics, pts);
-    round2_challenge(ch, pts);
-    round3_challenge(ch, pts);
-    round4_challenge(ch, evals);
-    round5_challenge(ch, pts);
-    const Fr al = ch.alpha, be = ch.beta, ga = ch.gamma, ze = ch.zeta, v = ch.v, u = ch.u;
-    const AtZeta z = at_zeta(vk->log_n, ze, publics, vk->n_public);
-    Fr ev[EVALS];
-    for (uint32_t j = 0; j < EVALS; j++) ev[j] = fr_from_std(evals + j * 32);
-    const Fr a = ev[0], b = ev[1], c = ev[2], s1 = ev[3], s2 = ev[4], zw = ev[5];
-    const Fr al2l1 = Fr::mul(Fr::sqr(al), z.l1), bz = Fr::mul(be, ze);
-    const Fr g12 = Fr::mul(Fr::add(Fr::add(a, Fr::mul(be, s1)), ga), Fr::add(Fr::add(b, Fr::mul(be, s2)), ga));
-    const Fr g12zw_alpha = Fr::mul(Fr::mul(g12, zw), al);
-    const Fr r0 = Fr::sub(Fr::add(Fr::mul(g12zw_alpha, Fr::add(c, ga)), al2l1), z.pi);
-    const Fr f123 = Fr::mul(Fr::mul(Fr::add(Fr::add(a, bz), ga), Fr::add(Fr::add(b, Fr::mul(bz, k1)), ga)), Fr::add(Fr::add(c, Fr::mul(bz, k2)), ga));
-    auto pt = [&](uint32_t j) { return P1(pts + j * 64); };
-    // D, then F
-    P1 F = P1(vk->qm).times(Fr::mul(a, b)) + P1(vk->ql).times(a) + P1(vk->qr).times(b) + P1(vk->qo).times(c) + P1(vk->qc);
-    F = F + pt(P_Z).times(Fr::add(Fr::add(Fr::mul(al, f123), al2l1), u));
-    F = F - P1(vk->s3).times(Fr::mul(g12zw_alpha, be));
-    F = F - (pt(P_TLO) + pt(P_TMID).times(z.zn) + pt(P_THI).times(Fr::sqr(z.zn))).times(z.zh);
-    const P1 batch[5] = {pt(P_A), pt(P_B), pt(P_C), P1(vk->s1), P1(vk->s2)};
-    Fr vp = v, e = r0;
-    for (int j = 0; j < 5; j++) {
-        F = F + batch[j].times(vp);
-        e = Fr::add(e, Fr::mul(vp, ev[j]));
-        vp = Fr::mul(vp, v);
-    }
-    e = Fr::add(e, Fr::mul(u, zw));
-    const P1 E = P1(kzg->g1).times(e);
-    const Fr uzw = Fr::mul(u, Fr::mul(ze, root_of_unity(vk->log_n)));
-    const P1 L = pt(P_WZ).times(ze) + pt(P_WZW).times(uzw) + F - E;
-    const P1 W = pt(P_WZ) + pt(P_WZW).times(u);
-    *verdict = kzg_pair_one(kzg, L.b, W.b);
-}
-
 }   // namespace
 
 extern "C" {
-
-int zk_keccak256(uint8_t out32[32], const uint8_t *data, uint64_t len) {
-    return guarded([&] {
-        if (!out32 || (len && !data)) throw std::invalid_argument("null argument");
-        keccak256(out32, data, len);
-    });
-}
 
 int zk_plonk_prover_create(zk_plonk_prover **out, zk_kzg *kzg, const zk_plonk_circuit_view *view, const uint32_t *a_map, const uint32_t *b_map,
                            const uint32_t *c_map, uint64_t n_witness, uint64_t n_public, int32_t device) {
@@ -688,13 +385,7 @@ int zk_plonk_prover_create(zk_plonk_prover **out, zk_kzg *kzg, const zk_plonk_ci
     });
 }
 
-void zk_plonk_prover_destroy(zk_plonk_prover *p) {
-    if (!p) return;
-    int prev = -1;
-    const bool switched = hipGetDevice(&prev) == hipSuccess && hipSetDevice(p->device) == hipSuccess;
-    delete p;
-    if (switched) (void)hipSetDevice(prev);
-}
+void zk_plonk_prover_destroy(zk_plonk_prover *p) { destroy_on_device(p); }
 
 int zk_plonk_prover_vkey(zk_plonk_prover *p, zk_plonk_vkey *vk) {
     return guarded([&] {
@@ -707,26 +398,23 @@ int zk_plonk_prover_vkey(zk_plonk_prover *p, zk_plonk_vkey *vk) {
 int zk_plonk_prover_info(zk_plonk_prover *p, zk_plonk_prover_plan *plan) {
     return guarded([&] {
         if (!p || !plan) throw std::invalid_argument("null argument");
-        if (plan->size < 4) throw std::invalid_argument("zk_plonk_prover_info: plan->size is not set");
-        zk_plonk_prover_plan q{};
-        q.scan_seg = plonk_perm_seg(), q.quot_seg = plonk_quot_seg(), q.open_seg = plonk_open_seg(), q.kzg_seg = kzg_seg_in_effect();
-        std::lock_guard<std::mutex> lock(p->mu);
-        q.size = plan->size < sizeof q ? plan->size : (uint32_t)sizeof q;
-        q.log_n = p->log_n;
-        q.n_witness = p->n_witness, q.n_public = p->n_public;
-        q.device_bytes = p->own_bytes() + plonk_circuit_bytes(p->circ) + plonk_opening_bytes(p->open) + plonk_perm_bytes(p->perm);
-        q.last_launches = p->last_launches;
-        for (uint32_t r = 0; r < ROUNDS; r++) q.round_launches[r] = p->round_launches[r];
-        memcpy(plan, &q, q.size);
+        info_into("zk_plonk_prover_info", plan, [&](zk_plonk_prover_plan &q) {
+            q.scan_seg = plonk_perm_seg(), q.quot_seg = plonk_quot_seg(), q.open_seg = plonk_open_seg(), q.kzg_seg = kzg_seg_in_effect();
+            std::lock_guard<std::mutex> lock(p->mu);
+            q.log_n = p->log_n;
+            q.n_witness = p->n_witness, q.n_public = p->n_public;
+            q.device_bytes = p->own_bytes() + plonk_circuit_bytes(p->circ) + plonk_opening_bytes(p->open) + plonk_perm_bytes(p->perm);
+            q.last_launches = p->last_launches;
+            for (uint32_t r = 0; r < ROUNDS; r++) q.round_launches[r] = p->round_launches[r];
+        });
     });
 }
 
 int zk_plonk_prove(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *witness, const uint8_t *publics, const uint8_t *blind) {
-    return guarded([&] { plonk_prove(p, proof, witness, publics, blind); });
-}
-
-int zk_plonk_verify(zk_kzg *kzg, const zk_plonk_vkey *vk, const uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *publics, uint8_t *verdict) {
-    return guarded([&] { plonk_verify(kzg, vk, proof, publics, verdict); });
+    return guarded([&] {
+        if (!p || !proof || !witness || (p->n_public && !publics)) throw std::invalid_argument("null argument");
+        plonk_prove(p, "zk_plonk_prove", proof, witness, p->n_witness, publics, blind, false);
+    });
 }
 
 int zk_plonk_prover_create_r1cs(zk_plonk_prover **out, zk_kzg *kzg, zk_plonk_r1cs *compiled, const uint8_t *shift, int32_t device) {
@@ -738,7 +426,13 @@ int zk_plonk_prover_create_r1cs(zk_plonk_prover **out, zk_kzg *kzg, zk_plonk_r1c
 }
 
 int zk_plonk_prove_r1cs(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *wtns, uint32_t nVars, const uint8_t *blind) {
-    return guarded([&] { plonk_prove_r1cs(p, proof, wtns, nVars, blind); });
+    return guarded([&] {
+        const char *who = "zk_plonk_prove_r1cs";
+        if (!p || !proof || !wtns) throw std::invalid_argument("null argument");
+        if (!p->r1cs) throw std::invalid_argument(std::string(who) + ": the prover was not made from an r1cs (zk_plonk_prover_create_r1cs)");
+        plonk_r1cs_check_witness(p->r1cs, who, wtns, nVars);
+        plonk_prove(p, who, proof, wtns, nVars, wtns + 32, blind, true);      // a circom witness: the publics are w[1 .. 1 + n_public)
+    });
 }
 
 }   // extern "C"

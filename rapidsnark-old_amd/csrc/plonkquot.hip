@@ -16,8 +16,8 @@
 // Lane map of all three: T lanes in the grid (a multiple of 256), lane l takes the points l, l + T, l + 2T, .. : `seg` of them
 // (ZKHIP_QUOT_SEG, read at every call).  Neighbouring lanes touch neighbouring rows (coalesced), a lane's i mod 4 never
 // changes (its 1 / Z_H is one value), and its power of g or of w_m moves on by ONE product a point (by g^T, w_m^T: the
-// host's).  The starting power comes from the bits of l over a host-made record of the powers g^(2^b), as
-// ScanConsts::wtab of frscan.hip.  Which products are formed depends on indices only and the arithmetic is exact: the bytes
+// host's).  The starting power comes from the bits of l over a host-made record of the powers g^(2^b) (lanepow.hpp, as
+// ScanConsts::wtab of frscan.hip).  Which products are formed depends on indices only and the arithmetic is exact: the bytes
 // depend neither on seg nor on scheduling.  No LDS but four words for k_coset_store's length, no atomics.
 //
 // Forms.  I/O is STANDARD.  Everything between k_coset_load and k_coset_store is the transforms' own form: canonical words of
@@ -29,13 +29,14 @@
 #include "devmem.hpp"
 #include "ptengine.hpp"
 #include "field29.hpp"
+#include "lanepow.hpp"
 #include "plonk_internal.hpp"
 
 namespace {
 
 constexpr uint32_t QT_WG = 256;
 constexpr uint32_t DEFAULT_SEG = 16, MAX_SEG = 4096;  // the default: profiles/plonk_quotient_timing.txt, the best call at log_n 18, 1.3 % behind the best at 22
-constexpr uint32_t MIN_LOG_N = 1, MAX_LOG_N = 25, MAX_LOG_M = 28, POW_TAB = 32;
+constexpr uint32_t MAX_LOG_M = 28;
 constexpr uint32_t RES_VECS = 9, EXT_VECS = 5, MAX_LOAD = 9;
 enum { V_QL, V_QR, V_QM, V_QO, V_QC, V_S1, V_S2, V_S3, V_L1 };      // the resident extensions
 enum { V_A, V_B, V_C, V_Z, V_PI };                                    // a proof's
@@ -43,11 +44,11 @@ enum { V_A, V_B, V_C, V_Z, V_PI };                                    // a proof
 typedef Fr29 F;
 
 // ---------------------------------------------------------------- device
-// A lane's power of a base: p_l = seed * base^l, moved on by `step` = base^T a point.  Words as the kernels multiply them
-// (the host makes them, pow_consts below)
+// A lane's power of a base: p_l = seed * base^l, moved on by pw.step = base^T a point (lanepow.hpp).  Words as the kernels
+// multiply them: x 2^261 (the host makes them, pow_consts below)
 struct PowConsts {
-    Fr seed, step;
-    Fr tab[POW_TAB];                                  // base^(2^b) 2^261
+    Fr seed;
+    PowTab pw;
 };
 
 __device__ __forceinline__ F ld(const Fr *p) { return F::load(load_el(p)); }
@@ -62,7 +63,7 @@ __device__ __forceinline__ F lane_power(const PowConsts *k, uint64_t l) {
     F p = ld(&k->seed);
 #pragma unroll 1
     for (uint32_t b = 0; b < POW_TAB && (l >> b); b++)
-        if ((l >> b) & 1) p = F::mul(p, ld(k->tab + b));
+        if ((l >> b) & 1) p = F::mul(p, ld(k->pw.tab + b));
     return p;
 }
 
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(QT_WG) void k_coset_load(LoadArgs A) {
     const uint64_t n_in = A.n_in[v];
     Fr *out = A.out + v * A.stride;
     F p = A.unit ? ld(&A.k->seed) : lane_power(A.k, l);
-    const F step = ld_uniform(&A.k->step);
+    const F step = ld_uniform(&A.k->pw.step);
 #pragma unroll 1
     for (uint32_t k = 0; k < A.seg; k++) {
         const uint64_t i = l + k * T;
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(QT_WG) void k_coset_store(StoreArgs A) {
     uint32_t top = 0;
     if (l < A.m) {
         F p = A.unit ? ld(&A.k->seed) : lane_power(A.k, l);
-        const F step = ld_uniform(&A.k->step);
+        const F step = ld_uniform(&A.k->pw.step);
 #pragma unroll 1
         for (uint32_t k = 0; k < A.seg; k++) {
             const uint64_t i = l + k * T;
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(QT_WG) void k_plonk_quotient(QuotArgs A) {
     F x = lane_power(&K->x, l);
     const F zh = ld(K->zh + (l & 3));                 // T is a multiple of 4: i mod 4 = l mod 4 at every point of the lane
     const F alpha = ld_uniform(&K->alpha), alpha2 = ld_uniform(&K->alpha2), beta = ld_uniform(&K->beta), gamma = ld_uniform(&K->gamma);
-    const F bk1 = ld_uniform(&K->bk1), bk2 = ld_uniform(&K->bk2), step = ld_uniform(&K->x.step);
+    const F bk1 = ld_uniform(&K->bk1), bk2 = ld_uniform(&K->bk2), step = ld_uniform(&K->x.pw.step);
 #pragma unroll 1
     for (uint32_t k = 0; k < A.seg; k++) {
         const uint64_t i = l + k * T;
@@ -233,11 +234,7 @@ PowConsts pow_consts(PowKind kind, Fr base, uint64_t lanes, Fr g = Fr::one()) {
     case POW_STORE: k.seed = raw_one(); break;
     case POW_POINTS: k.seed = w29(g); break;
     }
-    k.step = w29(fr_pow(base, lanes));
-    for (uint32_t b = 0; b < POW_TAB; b++) {
-        k.tab[b] = w29(base);
-        base = Fr::sqr(base);
-    }
+    k.pw = pow_tab(base, lanes, w29);
     return k;
 }
 
@@ -341,12 +338,6 @@ void coset_ntt_dev(Fr *out, Fr *a, Fr *b, const Fr *in, uint64_t n_in, const Xfo
     *t_len = top;
 }
 
-void check_below_r(const char *who, const char *what, const uint8_t *v, uint64_t n) {
-    const uint64_t bad = first_not_below_r(v, n);
-    if (bad < n) throw std::invalid_argument(std::string(who) + ": " + what + " " + std::to_string(bad) + " is not below r");
-}
-Fr checked_one(const char *who, const char *what, const uint8_t *v) { return checked_scalar(v, std::string(who) + ": " + what); }
-
 void fr_coset_ntt(uint8_t *out, const uint8_t *in, uint64_t n_in, uint32_t log_m, const uint8_t *shift, int inverse, int32_t device) {
     const char *who = "zk_fr_coset_ntt";
     const uint32_t seg = seg_in_effect();
@@ -409,46 +400,25 @@ struct zk_plonk_circuit {
 
 namespace {
 
-struct LaunchCount {
-    zk_plonk_circuit *c;
-    uint64_t at;
-    explicit LaunchCount(zk_plonk_circuit *c_) : c(c_), at(g_kernel_launches.load(std::memory_order_relaxed)) {}
-    ~LaunchCount() { c->last_launches = (uint32_t)(g_kernel_launches.load(std::memory_order_relaxed) - at); }
-};
-
 uint64_t steady_bytes(uint32_t log_n) {
     const uint64_t m = 4ull << log_n;
     return (RES_VECS + 2 * EXT_VECS) * m * sizeof(Fr) + Xform::bytes_of(log_n + 2) + CosetWork::bytes_of(m) + sizeof(QuotConsts) + sizeof(PowConsts);
 }
 
-zk_plonk_circuit *circuit_create(const zk_plonk_circuit_view *v, int32_t device) {
+// the object from a view that was checked (plonk_internal.hpp: the public entry's, or a prover's)
+zk_plonk_circuit *circuit_make(const CheckedView &cv, const CheckedShift &sh, int32_t device) {
     const char *who = "zk_plonk_circuit_create";
-    const uint32_t seg = seg_in_effect();
-    if (!v) throw std::invalid_argument("null argument");
-    if (v->log_n < MIN_LOG_N || v->log_n > MAX_LOG_N)
-        throw std::invalid_argument(std::string(who) + ": log_n " + std::to_string(v->log_n) + " is outside 1 .. 25");
-    if (v->basis != ZK_KZG_MONOMIAL && v->basis != ZK_KZG_LAGRANGE) throw std::invalid_argument(std::string(who) + ": basis " + std::to_string(v->basis) + " is unknown");
-    const uint8_t *vec[8] = {v->ql, v->qr, v->qm, v->qo, v->qc, v->s1, v->s2, v->s3};
-    static const char *const names[8] = {"ql", "qr", "qm", "qo", "qc", "s1", "s2", "s3"};
-    const uint64_t n = 1ull << v->log_n, m = 4 * n;
-    for (int j = 0; j < 8; j++) {
-        if (!vec[j]) throw std::invalid_argument("null argument");
-        check_below_r(who, names[j], vec[j], n);
-    }
+    const uint32_t seg = seg_in_effect(), log_n = cv.log_n;
+    const uint8_t *const *vec = cv.vec;
+    const uint64_t n = cv.n, m = 4 * n;
+    const bool lagrange = cv.lagrange;
     std::unique_ptr<zk_plonk_circuit> c(new zk_plonk_circuit());
-    c->log_n = v->log_n, c->n = n, c->m = m;
-    c->k1 = checked_one(who, "k1", v->k1);
-    c->k2 = checked_one(who, "k2", v->k2);
-    c->g = v->shift ? checked_one(who, "shift", v->shift) : fr_small(5);
-    if (c->g.is_zero()) throw std::invalid_argument(std::string(who) + ": shift is zero");
-    // g^(4n) = 1: the coset is the 4n-th roots of unity themselves and Z_H vanishes on a quarter of it
-    Fr gn = c->g;
-    for (uint32_t i = 0; i < v->log_n; i++) gn = Fr::sqr(gn);
-    if (Fr::sqr(Fr::sqr(gn)) == Fr::one()) throw std::invalid_argument(std::string(who) + ": shift^(4n) is 1: Z_H vanishes on the coset");
+    c->log_n = log_n, c->n = n, c->m = m;
+    c->k1 = cv.k1, c->k2 = cv.k2, c->g = sh.g;
     c->ginv = Fr::inv(c->g);
-    c->w_m = root_of_unity(v->log_n + 2);
+    c->w_m = root_of_unity(log_n + 2);
     const Fr w4 = root_of_unity(2);
-    Fr zh = gn;
+    Fr zh = sh.gn;
     for (int j = 0; j < 4; j++) {                      // Z_H(x_i) = g^n w_4^(i mod 4) - 1
         c->zh[j] = w29(Fr::inv(Fr::sub(zh, Fr::one())));
         zh = Fr::mul(zh, w4);
@@ -456,12 +426,12 @@ zk_plonk_circuit *circuit_create(const zk_plonk_circuit_view *v, int32_t device)
     c->device = resolve_device(device);
     DeviceGuard dg(c->device);
     // while it is made the object holds the nine vectors twice (a transform works out of place), later once beside a call's
-    const uint64_t making = 2 * RES_VECS * m * sizeof(Fr) + Xform::bytes_of(v->log_n + 2) + Xform::bytes_of(v->log_n) + CosetWork::bytes_of(m);
-    need_hbm(who, making > steady_bytes(v->log_n) ? making : steady_bytes(v->log_n));
+    const uint64_t making = 2 * RES_VECS * m * sizeof(Fr) + Xform::bytes_of(log_n + 2) + Xform::bytes_of(log_n) + CosetWork::bytes_of(m);
+    need_hbm(who, making > steady_bytes(log_n) ? making : steady_bytes(log_n));
     c->st.reset(new Stream());
     hipStream_t s = c->st->s;
-    LaunchCount lc(c.get());
-    c->xf.build(v->log_n + 2, s);
+    LaunchCount lc(c->last_launches);
+    c->xf.build(log_n + 2, s);
     c->kq.alloc(1);
     c->kl.alloc(1);
     c->cw.size(m);
@@ -471,7 +441,7 @@ zk_plonk_circuit *circuit_create(const zk_plonk_circuit_view *v, int32_t device)
     fill.alloc(1);
     for (int j = 0; j < 8; j++) HIP_TRY(hipMemcpyAsync(p.p + j * n, vec[j], n * sizeof(Fr), hipMemcpyHostToDevice, s));
     // L1's coefficients, n times 1 / n, in the form of the rows the load reads: standard, or the transforms' after the inverse transform
-    const Fr ninv = v->basis == ZK_KZG_LAGRANGE ? w29(Fr::inv(fr_small(n))) : Fr::from_mont(Fr::inv(fr_small(n)));
+    const Fr ninv = lagrange ? w29(Fr::inv(fr_small(n))) : Fr::from_mont(Fr::inv(fr_small(n)));
     HIP_TRY(hipMemcpyAsync(fill.p, &ninv, sizeof ninv, hipMemcpyHostToDevice, s));
     const uint32_t blocks = blocks_of(m, seg);
     PowConsts hk[2];
@@ -482,10 +452,9 @@ zk_plonk_circuit *circuit_create(const zk_plonk_circuit_view *v, int32_t device)
     const Fr *rows = p.p;
     Fr *ext = q.p, *other = p.p;
     std::unique_ptr<Xform> small;
-    const bool lagrange = v->basis == ZK_KZG_LAGRANGE;
     if (lagrange) {
         small.reset(new Xform());
-        small->build(v->log_n, s);
+        small->build(log_n, s);
         hk[0] = pow_consts(POW_LOAD_STD, Fr::one(), (uint64_t)blocks_of(n, seg) * QT_WG);
         HIP_TRY(hipMemcpyAsync(dk.p, &hk[0], sizeof(PowConsts), hipMemcpyHostToDevice, s));
         LoadArgs U{};
@@ -513,6 +482,14 @@ zk_plonk_circuit *circuit_create(const zk_plonk_circuit_view *v, int32_t device)
     c->x.alloc(EXT_VECS * m);
     c->y.alloc(EXT_VECS * m);
     return c.release();
+}
+
+zk_plonk_circuit *circuit_create(const zk_plonk_circuit_view *v, int32_t device) {
+    const char *who = "zk_plonk_circuit_create";
+    if (!v) throw std::invalid_argument("null argument");
+    CheckedView cv = checked_view_dims(who, v, 1);
+    checked_view_rows(who, v, cv);
+    return circuit_make(cv, checked_shift(who, v->shift, cv.log_n), device);
 }
 
 // t's 4n coefficients and its length from the proof's polynomials, over device pointers and a stream: c.y holds the standard
@@ -579,7 +556,7 @@ void plonk_quotient(zk_plonk_circuit *c, uint8_t *t, uint64_t *t_len, const uint
     const Fr al = checked_one(who, "alpha", alpha), be = checked_one(who, "beta", beta), ga = checked_one(who, "gamma", gamma);
     std::lock_guard<std::mutex> lock(c->mu);
     DeviceGuard dg(c->device);
-    LaunchCount lc(c);
+    LaunchCount lc(c->last_launches);
     hipStream_t s = c->st->s;
     uint64_t at = 0;
     for (uint32_t j = 0; j < vecs; j++) {
@@ -595,6 +572,8 @@ void plonk_quotient(zk_plonk_circuit *c, uint8_t *t, uint64_t *t_len, const uint
 
 // ---------------------------------------------------------------- what plonkprove.hip chains (plonk_internal.hpp)
 uint32_t plonk_quot_seg() { return seg_in_effect(); }
+
+zk_plonk_circuit *plonk_circuit_make(const CheckedView &cv, const CheckedShift &shift, int32_t device) { return circuit_make(cv, shift, device); }
 
 uint64_t plonk_circuit_need_bytes(uint32_t log_n) {
     const uint64_t m = 4ull << log_n;
@@ -658,28 +637,19 @@ int zk_plonk_circuit_create(zk_plonk_circuit **out, const zk_plonk_circuit_view 
     });
 }
 
-void zk_plonk_circuit_destroy(zk_plonk_circuit *c) {
-    if (!c) return;
-    int prev = -1;
-    const bool switched = hipGetDevice(&prev) == hipSuccess && hipSetDevice(c->device) == hipSuccess;
-    delete c;
-    if (switched) (void)hipSetDevice(prev);
-}
+void zk_plonk_circuit_destroy(zk_plonk_circuit *c) { destroy_on_device(c); }
 
 int zk_plonk_circuit_info(zk_plonk_circuit *c, zk_plonk_circuit_plan *plan) {
     return guarded([&] {
         if (!c || !plan) throw std::invalid_argument("null argument");
-        if (plan->size < 4) throw std::invalid_argument("zk_plonk_circuit_info: plan->size is not set");
-        zk_plonk_circuit_plan p;
-        const uint32_t seg = seg_in_effect();
-        std::lock_guard<std::mutex> lock(c->mu);
-        p.size = plan->size < sizeof p ? plan->size : (uint32_t)sizeof p;
-        p.log_n = c->log_n;
-        p.points = c->m;
-        p.device_bytes = c->bytes();
-        p.seg = seg;
-        p.last_launches = c->last_launches;
-        memcpy(plan, &p, p.size);
+        info_into("zk_plonk_circuit_info", plan, [&](zk_plonk_circuit_plan &p) {
+            p.seg = seg_in_effect();
+            std::lock_guard<std::mutex> lock(c->mu);
+            p.log_n = c->log_n;
+            p.points = c->m;
+            p.device_bytes = c->bytes();
+            p.last_launches = c->last_launches;
+        });
     });
 }
 

@@ -428,7 +428,6 @@ __global__ __launch_bounds__(WG) void k_ext_apply(Fr *w, const uint32_t *agg_f, 
 }
 
 // ---------------------------------------------------------------- host
-uint64_t launches_now() { return g_kernel_launches.load(std::memory_order_relaxed); }
 uint64_t scan_blocks(uint64_t len, uint32_t seg) { return (len + (uint64_t)WG * seg - 1) / ((uint64_t)WG * seg); }
 
 // x[0, len] <- the exclusive sums of x[0, len) and, at x[len], their total: three launches
@@ -663,25 +662,17 @@ int zk_plonk_r1cs_create(zk_plonk_r1cs **out, const zk_r1cs_view *view, const ui
     });
 }
 
-void zk_plonk_r1cs_destroy(zk_plonk_r1cs *c) {
-    if (!c) return;
-    int prev = -1;
-    const bool switched = hipGetDevice(&prev) == hipSuccess && hipSetDevice(c->device) == hipSuccess;
-    delete c;
-    if (switched) (void)hipSetDevice(prev);
-}
+void zk_plonk_r1cs_destroy(zk_plonk_r1cs *c) { destroy_on_device(c); }
 
 int zk_plonk_r1cs_info(zk_plonk_r1cs *c, zk_plonk_r1cs_plan *plan) {
     return guarded([&] {
         if (!c || !plan) throw std::invalid_argument("null argument");
-        if (plan->size < 4) throw std::invalid_argument("zk_plonk_r1cs_info: plan->size is not set");
-        zk_plonk_r1cs_plan q{};
-        q.seg = seg_in_effect();
-        std::lock_guard<std::mutex> lock(c->mu);
-        q.size = plan->size < sizeof q ? plan->size : (uint32_t)sizeof q;
-        q.log_n = c->log_n, q.rows = c->rows, q.n_public = c->nPublic, q.n_wires = c->nWires, q.n_additions = c->n_add, q.n_witness = c->n_witness;
-        q.terms = c->terms, q.device_bytes = c->bytes(), q.sort_passes = c->passes, q.last_launches = c->last_launches;
-        memcpy(plan, &q, q.size);
+        info_into("zk_plonk_r1cs_info", plan, [&](zk_plonk_r1cs_plan &q) {
+            q.seg = seg_in_effect();
+            std::lock_guard<std::mutex> lock(c->mu);
+            q.log_n = c->log_n, q.rows = c->rows, q.n_public = c->nPublic, q.n_wires = c->nWires, q.n_additions = c->n_add, q.n_witness = c->n_witness;
+            q.terms = c->terms, q.device_bytes = c->bytes(), q.sort_passes = c->passes, q.last_launches = c->last_launches;
+        });
     });
 }
 

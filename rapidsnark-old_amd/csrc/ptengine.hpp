@@ -152,6 +152,12 @@ inline Fr checked_scalar(const uint8_t s32[32], const std::string &what) {
     if (!below(s32, FrParams::P)) throw std::invalid_argument(what + " is not below r");
     return fr_from_std(s32);
 }
+// the two as an entry `who` words them: "<who>: <what> <index> is not below r", "<who>: <what> is not below r"
+inline void check_below_r(const char *who, const char *what, const uint8_t *v, uint64_t n) {
+    const uint64_t bad = first_not_below_r(v, n);
+    if (bad < n) throw std::invalid_argument(std::string(who) + ": " + what + " " + std::to_string(bad) + " is not below r");
+}
+inline Fr checked_one(const char *who, const char *what, const uint8_t *v) { return checked_scalar(v, std::string(who) + ": " + what); }
 
 inline bool plain_subgroup() { return env_switch("ZKHIP_SUBGROUP_PLAIN"); }
 

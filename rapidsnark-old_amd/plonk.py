@@ -65,6 +65,76 @@ def _circuit_rows(vectors):
     return vecs, n, log_n
 
 
+def _view(vectors, k1, k2, basis, shift=None, min_log_n=MIN_LOG_N):
+    """(view, keep, n, log_n): a zk_plonk_circuit_view over the checked arguments, and the arrays it points into, which the
+    caller holds while the library reads it"""
+    if basis not in _BASES:
+        raise ValueError("basis %r is unknown: 'monomial' or 'lagrange'" % (basis,))
+    vecs, n, log_n = _circuit_rows(vectors)
+    if log_n < min_log_n:
+        raise ValueError("log_n %d is outside %d .. %d" % (log_n, min_log_n, MAX_LOG_N))
+    kb1, kb2 = _one(k1, "k1"), _one(k2, "k2")
+    g = _shift(shift)
+    if g is not None and pow(int.from_bytes(g.tobytes(), "little") % R_MOD, 4 * n, R_MOD) == 1:
+        raise ValueError("shift^(4n) is 1: Z_H vanishes on the coset")
+    v = L.zk_plonk_circuit_view()
+    v.log_n, v.basis = log_n, _BASES[basis]
+    for name, a in zip(_CIRCUIT, vecs):
+        setattr(v, name, a.ctypes.data)
+    C.memmove(v.k1, kb1.ctypes.data, 32)
+    C.memmove(v.k2, kb2.ctypes.data, 32)
+    v.shift = g.ctypes.data if g is not None else None
+    return v, (vecs, g), n, log_n
+
+
+class _Object:
+    """A library object behind a handle: closed by close(), by leaving a with block or by the collector.  A class names
+    itself (_name), its destroy and info entries, its plan type and the plan's fields its info() leaves out."""
+    _h = None
+    _owned = ()                                         # objects made for this one, closed with it
+    _drop = ("size", "reserved")
+
+    def _handle(self):
+        if not self._h:
+            raise L.ZkHipError("the %s object is closed" % self._name)
+        return self._h
+
+    def _plan_dict(self):
+        h = self._handle()
+        plan = self._plan()
+        plan.size = C.sizeof(plan)
+        L.check(getattr(L.load_library(), self._info)(h, C.byref(plan)))
+        return plan, {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name not in self._drop}
+
+    def close(self):
+        if self._h:
+            getattr(L.load_library(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+        for o in self._owned:
+            o.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _KzgObject(_Object):
+    """.. on a Kzg's device, whose points it uses"""
+
+    def _handle(self):
+        h = super()._handle()
+        self.kzg._handle()                              # a closed Kzg: its points are gone
+        return h
+
+
 def fr_poly_eval(coeffs, zs, device=-1):
     """a list of m ints p_k(z_k) (zk_fr_poly_eval): coeffs one polynomial (ints, or a flat byte array) or several of one
     length (a sequence of int sequences, or a 2-d uint8 array), zs one point each.  Nothing is committed to."""
@@ -79,39 +149,24 @@ def fr_poly_eval(coeffs, zs, device=-1):
     return [int.from_bytes(yb[i * 32:(i + 1) * 32], "little") for i in range(m)]
 
 
-class PlonkOpening:
+class PlonkOpening(_KzgObject):
     """Rounds 4 and 5 of a three-column PLONK proof on a Kzg's device (zk_plonk_opening): the eight circuit polynomials by
     coefficients, resident, and room for a proof's vectors.  basis "lagrange": values at w^j, converted once.  The object
     keeps a reference to the Kzg, whose points and multiplication it uses.  It is NOT checked that 1, k1, k2 name disjoint
     cosets."""
+    _name, _destroy, _info, _plan = "PlonkOpening", "zk_plonk_opening_destroy", "zk_plonk_opening_info", L.zk_plonk_opening_plan
 
     def __init__(self, kzg, ql, qr, qm, qo, qc, s1, s2, s3, k1, k2, basis="monomial"):
         from .kzg import Kzg
         if not isinstance(kzg, Kzg):
             raise TypeError("a Kzg expected")
-        if basis not in _BASES:
-            raise ValueError("basis %r is unknown: 'monomial' or 'lagrange'" % (basis,))
-        vecs, n, log_n = _circuit_rows((ql, qr, qm, qo, qc, s1, s2, s3))
-        kb1, kb2 = _one(k1, "k1"), _one(k2, "k2")
+        v, keep, n, log_n = _view((ql, qr, qm, qo, qc, s1, s2, s3), k1, k2, basis)
         if n + 6 > kzg.max_coeffs:
             raise ValueError("n + 6 = %d exceeds the kzg's max_coeffs = %d" % (n + 6, kzg.max_coeffs))
         self._h = C.c_void_p()
         self.kzg, self.n, self.log_n, self.max_coeffs, self.device = kzg, n, log_n, kzg.max_coeffs, kzg.device
         kh = kzg._handle()
-        v = L.zk_plonk_circuit_view()
-        v.log_n, v.basis = log_n, _BASES[basis]
-        for name, a in zip(_CIRCUIT, vecs):
-            setattr(v, name, a.ctypes.data)
-        C.memmove(v.k1, kb1.ctypes.data, 32)
-        C.memmove(v.k2, kb2.ctypes.data, 32)
-        v.shift = None
         L.check(L.load_library().zk_plonk_opening_create(C.byref(self._h), kh, C.byref(v), -1))
-
-    def _handle(self):
-        if not self._h:
-            raise L.ZkHipError("the PlonkOpening object is closed")
-        self.kzg._handle()                              # a closed Kzg: its points are gone
-        return self._h
 
     def _vectors(self, names, lens, vectors):
         rows = [_scalars(v, name) for name, v in zip(names, vectors)]
@@ -154,58 +209,20 @@ class PlonkOpening:
 
     def info(self):
         """zk_plonk_opening_info -> dict: log_n, device_bytes, seg (ZKHIP_OPEN_SEG in effect), last_launches, pending"""
-        h = self._handle()
-        plan = L.zk_plonk_opening_plan()
-        plan.size = C.sizeof(plan)
-        L.check(L.load_library().zk_plonk_opening_info(h, C.byref(plan)))
-        return {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name not in ("size", "reserved")}
-
-    def close(self):
-        if self._h:
-            L.load_library().zk_plonk_opening_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._plan_dict()[1]
 
 
-class PlonkCircuit:
+class PlonkCircuit(_Object):
     """What does not change from proof to proof of a three-column PLONK circuit, on a device (zk_plonk_circuit): the eight
     polynomials extended to the coset shift * (4n-th roots of unity).  basis "monomial": coefficients; "lagrange": values at
     w^j, what plonk_permutation_product takes.  It is NOT checked that 1, k1, k2 name disjoint cosets."""
+    _name, _destroy, _info, _plan = "PlonkCircuit", "zk_plonk_circuit_destroy", "zk_plonk_circuit_info", L.zk_plonk_circuit_plan
 
     def __init__(self, ql, qr, qm, qo, qc, s1, s2, s3, k1, k2, basis="monomial", shift=None, device=-1):
-        if basis not in _BASES:
-            raise ValueError("basis %r is unknown: 'monomial' or 'lagrange'" % (basis,))
-        vecs, n, log_n = _circuit_rows((ql, qr, qm, qo, qc, s1, s2, s3))
-        kb1, kb2 = _one(k1, "k1"), _one(k2, "k2")
-        g = _shift(shift)
-        if g is not None and pow(int.from_bytes(g.tobytes(), "little") % R_MOD, 4 * n, R_MOD) == 1:
-            raise ValueError("shift^(4n) is 1: Z_H vanishes on the coset")
+        v, keep, n, log_n = _view((ql, qr, qm, qo, qc, s1, s2, s3), k1, k2, basis, shift)
         self.n, self.log_n, self.device = n, log_n, int(device)
         self._h = C.c_void_p()
-        v = L.zk_plonk_circuit_view()
-        v.log_n, v.basis = log_n, _BASES[basis]
-        for name, a in zip(_CIRCUIT, vecs):
-            setattr(v, name, a.ctypes.data)
-        C.memmove(v.k1, kb1.ctypes.data, 32)
-        C.memmove(v.k2, kb2.ctypes.data, 32)
-        v.shift = g.ctypes.data if g is not None else None
         L.check(L.load_library().zk_plonk_circuit_create(C.byref(self._h), C.byref(v), device))
-
-    def _handle(self):
-        if not self._h:
-            raise L.ZkHipError("the PlonkCircuit object is closed")
-        return self._h
 
     def quotient(self, a, b, c, z, alpha, beta, gamma, pi=None):
         """(t, t_len): t a numpy uint8 array of 4n rows, the coefficients of t = num / Z_H with zeros from t_len on; t_len one
@@ -235,27 +252,7 @@ class PlonkCircuit:
 
     def info(self):
         """zk_plonk_circuit_info -> dict: log_n, points (4n), device_bytes, seg (ZKHIP_QUOT_SEG in effect), last_launches"""
-        plan = L.zk_plonk_circuit_plan()
-        plan.size = C.sizeof(plan)
-        L.check(L.load_library().zk_plonk_circuit_info(self._handle(), C.byref(plan)))
-        return {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name != "size"}
-
-    def close(self):
-        if self._h:
-            L.load_library().zk_plonk_circuit_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._plan_dict()[1]
 
 
 # ---------------------------------------------------------------- the prover and the verifier
@@ -355,24 +352,18 @@ def _maps(maps, n, n_witness):
     return out
 
 
-class PlonkProver:
+class PlonkProver(_KzgObject):
     """A three-column PLONK prover for one circuit on a Kzg's device (zk_plonk_prover): everything that does not change from
     proof to proof stays resident, a proof uploads the witness and nothing else per row.  Row i's wires are
     witness[a_map[i]], witness[b_map[i]], witness[c_map[i]].  The object keeps a reference to the Kzg."""
+    _name, _destroy, _info, _plan = "PlonkProver", "zk_plonk_prover_destroy", "zk_plonk_prover_info", L.zk_plonk_prover_plan
+    _drop = ("size", "round_launches")
 
     def __init__(self, kzg, ql, qr, qm, qo, qc, s1, s2, s3, k1, k2, a_map, b_map, c_map, n_witness, n_public=0, basis="monomial", shift=None):
         from .kzg import Kzg
         if not isinstance(kzg, Kzg):
             raise TypeError("a Kzg expected")
-        if basis not in _BASES:
-            raise ValueError("basis %r is unknown: 'monomial' or 'lagrange'" % (basis,))
-        vecs, n, log_n = _circuit_rows((ql, qr, qm, qo, qc, s1, s2, s3))
-        if log_n < MIN_PROVER_LOG_N:
-            raise ValueError("log_n %d is outside %d .. %d" % (log_n, MIN_PROVER_LOG_N, MAX_LOG_N))
-        kb1, kb2 = _one(k1, "k1"), _one(k2, "k2")
-        g = _shift(shift)
-        if g is not None and pow(int.from_bytes(g.tobytes(), "little") % R_MOD, 4 * n, R_MOD) == 1:
-            raise ValueError("shift^(4n) is 1: Z_H vanishes on the coset")
+        v, keep, n, log_n = _view((ql, qr, qm, qo, qc, s1, s2, s3), k1, k2, basis, shift, MIN_PROVER_LOG_N)
         if n + 6 > kzg.max_coeffs:
             raise ValueError("n + 6 = %d exceeds the kzg's max_coeffs = %d" % (n + 6, kzg.max_coeffs))
         n_witness, n_public = int(n_witness), int(n_public)
@@ -384,13 +375,6 @@ class PlonkProver:
         self._h = C.c_void_p()
         self.kzg, self.n, self.log_n, self.n_witness, self.n_public, self.device = kzg, n, log_n, n_witness, n_public, kzg.device
         kh = kzg._handle()
-        v = L.zk_plonk_circuit_view()
-        v.log_n, v.basis = log_n, _BASES[basis]
-        for name, a in zip(_CIRCUIT, vecs):
-            setattr(v, name, a.ctypes.data)
-        C.memmove(v.k1, kb1.ctypes.data, 32)
-        C.memmove(v.k2, kb2.ctypes.data, 32)
-        v.shift = g.ctypes.data if g is not None else None
         L.check(L.load_library().zk_plonk_prover_create(C.byref(self._h), kh, C.byref(v), L._ptr(maps[0]), L._ptr(maps[1]), L._ptr(maps[2]), n_witness,
                                                         n_public, -1))
 
@@ -412,7 +396,7 @@ class PlonkProver:
             self = cls.__new__(cls)
             self._h = C.c_void_p()
             self.kzg, self.n, self.log_n, self.n_witness, self.n_public, self.device = kzg, c.n, c.log_n, c.n_witness, c.n_public, kzg.device
-            self.r1cs, self._own_r1cs = c, own
+            self.r1cs, self._owned = c, (c,) if own else ()
             L.check(L.load_library().zk_plonk_prover_create_r1cs(C.byref(self._h), kzg._handle(), c._handle(), L._ptr(g) if g is not None else None, -1))
         except Exception:
             if own:
@@ -446,12 +430,6 @@ class PlonkProver:
             if verdict != 0:
                 raise L.ZkHipError("ZKHIP_SELFVERIFY: the proof does not verify (verdict %d)" % verdict)
         return proof
-
-    def _handle(self):
-        if not self._h:
-            raise L.ZkHipError("the PlonkProver object is closed")
-        self.kzg._handle()                              # a closed Kzg: its points are gone
-        return self._h
 
     def prove(self, witness, publics=None, blind=None):
         """-> PlonkProof (zk_plonk_prove).  publics None: witness[1 : 1 + n_public], circom's layout.  blind None: eleven
@@ -495,39 +473,17 @@ class PlonkProver:
     def info(self):
         """zk_plonk_prover_info -> dict: log_n, n_witness, n_public, device_bytes, the four knobs in effect, last_launches and
         round_launches (a list of five)"""
-        h = self._handle()
-        plan = L.zk_plonk_prover_plan()
-        plan.size = C.sizeof(plan)
-        L.check(L.load_library().zk_plonk_prover_info(h, C.byref(plan)))
-        d = {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name not in ("size", "round_launches")}
+        plan, d = self._plan_dict()
         d["round_launches"] = [int(x) for x in plan.round_launches]
         return d
 
-    def close(self):
-        if self._h:
-            L.load_library().zk_plonk_prover_destroy(self._h)
-            self._h = C.c_void_p()
-        if self.r1cs is not None and getattr(self, "_own_r1cs", False):
-            self.r1cs.close()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PlonkR1cs:
+class PlonkR1cs(_Object):
     """A circom .r1cs compiled on a device to a three-column PLONK circuit (zk_plonk_r1cs; include/zkhip.h, section "PLONK
     from an R1CS", states the layout): .vectors, the eight vectors ql qr qm qo qc s1 s2 s3 as values over the domain (a list of
     numpy uint8 [n * 32]), .maps (three numpy uint32 [n]), and extend(wtns), the witness a proof needs.  Custom gates are
     refused as by R1cs.  k1, k2 must name, with 1, three different cosets of the n-th roots of unity."""
+    _name, _destroy, _info, _plan = "PlonkR1cs", "zk_plonk_r1cs_destroy", "zk_plonk_r1cs_info", L.zk_plonk_r1cs_plan
 
     def __init__(self, path_or_bytes, k1=2, k2=3, device=-1):
         from .r1cs import open_r1cs
@@ -543,11 +499,6 @@ class PlonkR1cs:
         d = self.info()
         self.log_n, self.n, self.rows = d["log_n"], 1 << d["log_n"], d["rows"]
         self.n_public, self.n_wires, self.n_additions, self.n_witness = d["n_public"], d["n_wires"], d["n_additions"], d["n_witness"]
-
-    def _handle(self):
-        if not self._h:
-            raise L.ZkHipError("the PlonkR1cs object is closed")
-        return self._h
 
     def _fetch(self):
         if self._circuit is None:
@@ -578,28 +529,7 @@ class PlonkR1cs:
     def info(self):
         """zk_plonk_r1cs_info -> dict: log_n, rows (N), n_public, n_wires, n_additions, n_witness, terms, device_bytes, seg
         (ZKHIP_R1CS_SEG in effect), sort_passes, last_launches"""
-        h = self._handle()
-        plan = L.zk_plonk_r1cs_plan()
-        plan.size = C.sizeof(plan)
-        L.check(L.load_library().zk_plonk_r1cs_info(h, C.byref(plan)))
-        return {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name not in ("size", "reserved")}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.load_library().zk_plonk_r1cs_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._plan_dict()[1]
 
 
 def plonk_verify(vkey, proof, publics=(), kzg=None):
