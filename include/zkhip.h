@@ -1210,6 +1210,53 @@ int zk_plonk_prove(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], cons
  * "zk_plonk_verify: a commitment of the key is not a point of the curve". */
 int zk_plonk_verify(zk_kzg *kzg, const zk_plonk_vkey *vk, const uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *publics, uint8_t *verdict);
 
+/* A verifier made from the KEY ALONE, for many proofs a call: no zk_kzg and no .ptau, since a verifier needs the eight
+ * commitments and [tau]G2 and the key holds both.  On its device the object keeps the line tables of the G2 generator and of
+ * [tau]G2, the eight commitments and the generator of G1, the Keccak state after the key's commitments (the 512 bytes every
+ * round-1 message begins with: three blocks permuted, 13 words of the fourth absorbed), and, from the first call on, the
+ * buffers of one chunk of proofs.  A bad key is refused as zk_plonk_verify refuses it, before a device is touched:
+ *   "zk_plonk_verifier_create: vk->size is not sizeof(zk_plonk_vkey)", "zk_plonk_verifier_create: log_n 2 is outside 3 .. 25",
+ *   "zk_plonk_verifier_create: n_public 9 exceeds n = 8", "zk_plonk_verifier_create: k1 is not below r" (k2 alike),
+ *   "zk_plonk_verifier_create: a commitment of the key is not a point of the curve";
+ * and, on the device, as zk_ptau_check judges section 3 (coordinates below q, the twist, the subgroup; infinity is refused):
+ *   "zk_plonk_verifier_create: the key's [tau]G2 is not a point of the twist in the subgroup".
+ * Free HBM is checked before anything is allocated.  Calls on one object are serialised.
+ *
+ * THE KEY FILE (host/vkjson.hpp, PlonkVKey.to_json / from_json, the programs plonkvkey and plonkverifier) has the field names of
+ * snarkjs's verification_key.json for PLONK: protocol "plonk", curve "bn128", nPublic, power, k1, k2, Qm Ql Qr Qo Qc S1 S2 S3,
+ * X_2, w; points as decimal strings, projective with z = 1 (infinity: 0 1 0).  It names a key of THIS project's compile and
+ * transcript: parity with snarkjs is UNPINNED, so a key made by snarkjs parses (when its w is this library's root for its
+ * power), but proofs made by snarkjs are not promised to verify. */
+typedef struct zk_plonk_verifier zk_plonk_verifier;
+int zk_plonk_verifier_create(zk_plonk_verifier **out, const zk_plonk_vkey *vk, int32_t device);
+void zk_plonk_verifier_destroy(zk_plonk_verifier *v);
+/* Set plan->size = sizeof(zk_plonk_verifier_plan) before the call (only `size` bytes are written). */
+typedef struct zk_plonk_verifier_plan {
+    uint32_t size;
+    uint32_t log_n;
+    uint64_t n_public;
+    uint64_t device_bytes;        /* HBM the object holds, the buffers of a chunk included once a call has made them */
+    uint64_t chunk;               /* ZKHIP_PLONK_VERIFY_CHUNK in effect */
+    uint32_t last_launches;       /* kernel launches of the last call on the object (of the creation before it) */
+    uint32_t last_chunks;         /* chunks of the last call with m > 0: ceil(m / min(m, chunk)) */
+} zk_plonk_verifier_plan;
+int zk_plonk_verifier_info(zk_plonk_verifier *v, zk_plonk_verifier_plan *plan);
+/* verdict[i] = what zk_plonk_verify gives proof i (proofs: m x ZK_PLONK_PROOF_BYTES) with publics[i] (m x n_public x 32 bytes,
+ * proof-major; NULL when n_public = 0): ZK_VERIFY_OK / ZK_VERIFY_INVALID / ZK_VERIFY_MALFORMED, with the same malformed
+ * conditions; the point at infinity is a point, so a proof that holds one is judged by the equation.  Everything per proof
+ * runs on the device, four launches a chunk: the checks, the transcript and the scalars (a lane per proof); the nineteen
+ * products (a lane per product); L and W (a lane per proof); zk_kzg_verify's pairing kernel over the object's tables.  A
+ * malformed proof does not disturb its neighbours.  m = 0 is legal and does nothing; "zk_plonk_verifier_verify: m is not below
+ * 2^31".  ZKHIP_PLONK_VERIFY_CHUNK=<proofs a chunk> (decimal, 1 to 2^20, read at every call, 65536 otherwise; anything else is
+ * an error of the call, "ZKHIP_PLONK_VERIFY_CHUNK: a number of proofs from 1 to 2^20 expected") bounds the HBM of a call, about
+ * 4.2 KB + 32 n_public bytes a proof, and changes no verdict. */
+int zk_plonk_verifier_verify(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publics, uint64_t m, uint8_t *verdict);
+/* The first kernel alone, for tests of the device transcript on inputs that are no valid proofs and for whoever looks for
+ * the first difference against another implementation's transcript: challenges[i] = beta gamma alpha zeta v u of proof i, 6 x
+ * 32 bytes little-endian in standard form; status[i] = 0, or ZK_VERIFY_MALFORMED with the row left all zero.  "m is not
+ * below 2^31" and the knob as above, under this entry's name. */
+int zk_plonk_verifier_challenges(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publics, uint64_t m, uint8_t *challenges, uint8_t *status);
+
 /* ---- PLONK from an R1CS ---------------------------------------------------------------------- */
 /* A circom .r1cs compiled on the device to what zk_plonk_prover_create takes: the five selectors, the three wire maps and the
  * permutation s1 s2 s3; the extension of a circom witness by the wires the compile introduces; and a prover made from the

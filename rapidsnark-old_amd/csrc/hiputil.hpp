@@ -253,17 +253,6 @@ inline uint32_t ilog2_exact(uint64_t n) {
     return l;
 }
 
-// w_(2^28), standard form (ntt.hip and nttpair.hip keep the device's copies), and the 2^log_n-th root zk_fr_ntt uses
-// (log_n <= 28, Montgomery): the host's, for ptau_prepare.hip, ptau_check.hip and frscan.hip
-constexpr uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
-inline Fr root_of_unity(uint32_t log_n) {
-    Fr w;
-    for (int i = 0; i < 8; i++) w.v[i] = ROOT_2_28_STD[i];
-    w = Fr::to_mont(w);
-    for (uint32_t i = log_n; i < 28; i++) w = Fr::sqr(w);
-    return w;
-}
-
 inline uint32_t nblocks(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 
 // XYZZ -> affine of n points by synth.hip's batched inversion, G1 or G2 by the argument types

@@ -10,6 +10,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "field.hpp"
+
 namespace zk {
 
 // Decimal, from min to max; unset or empty: dflt; anything else: "<name>: <what> expected".  Strict (the group switches,
@@ -48,6 +50,18 @@ inline BadPoint lowest_bad(const uint32_t h[4]) {
     return b;
 }
 constexpr const char *KIND_TEXT[5] = {"", "has a coordinate that is not below q", "is not on the curve", "is not in the subgroup", "is the point at infinity"};
+
+// w_(2^28), standard form (ntt.hip and nttpair.hip keep the device's copies), and the 2^log_n-th root zk_fr_ntt uses
+// (log_n <= 28, Montgomery): the host's, for ptau_prepare.hip, ptau_check.hip, frscan.hip and the PLONK units, and for the
+// programs that read or write a PLONK key file, whose `w` it is
+constexpr uint32_t ROOT_2_28_STD[8] = {0x725b19f0u, 0x9bd61b6eu, 0x41112ed4u, 0x402d111eu, 0x8ef62abcu, 0x00e0a7ebu, 0xa58a7e85u, 0x2a3c09f0u};
+inline Fr root_of_unity(uint32_t log_n) {
+    Fr w;
+    for (int i = 0; i < 8; i++) w.v[i] = ROOT_2_28_STD[i];
+    w = Fr::to_mont(w);
+    for (uint32_t i = log_n; i < 28; i++) w = Fr::sqr(w);
+    return w;
+}
 
 // a 32-byte little-endian scalar is 0 or 1: no check scalar
 inline bool is_0_or_1(const uint8_t s32[32]) {

@@ -523,6 +523,18 @@ void kzg_verify_batch(zk_kzg *k, const uint8_t *commitments, const uint8_t *zs, 
 
 }   // namespace
 
+// The two kernels of the pairing check over tables of another object's making (kzg_internal.hpp: plonkverify_dev.hip's
+// verifier has its own [tau]G2 and no zk_kzg).  Q: the generator of G2, then [tau]G2; tab: 2 * MILLER_LINES lines
+void launch_kzg_line_tables(Line *tab, const G2Affine *Q, const PairConsts *k, hipStream_t s) {
+    ZK_LAUNCH(k_kzg_line_tables, dim3(1), dim3(64), 0, s, tab, Q, 2u, k);
+    ZK_LAUNCH_OK("line tables");
+}
+void launch_kzg_pair(uint8_t *verdict, const uint32_t *status, const G1Affine *L, const G1Affine *pi, const Line *tab, uint64_t m, const PairConsts *k,
+                     hipStream_t s) {
+    ZK_LAUNCH(k_kzg_pair, dim3(nblocks(m, 64)), dim3(64), 0, s, verdict, status, L, pi, tab, m, k);
+    ZK_LAUNCH_OK("pairing check");
+}
+
 // ZK_VERIFY_OK iff e(L, G2) = e(pi, [tau]G2), one lane of k_kzg_pair over the object's line tables (plonk_internal.hpp: the
 // last step of zk_plonk_verify).  L and pi are points of the curve in the file's form: the caller's check
 uint8_t kzg_pair_one(zk_kzg *k, const uint8_t L[64], const uint8_t pi[64]) {

@@ -48,6 +48,13 @@ struct DivWork {
 // q[0, n - 1) and *y from c[0, n), n >= 1, all on the device, standard form; z in Montgomery form (kzg.hip)
 void launch_divide(Fr *q, Fr *y, const Fr *c, uint64_t n, const Fr &z, uint32_t seg, DivWork &w, hipStream_t s);
 
+// kzg.hip's two kernels of the pairing check e(L_i, G2) = e(pi_i, [tau]G2) for a caller with tables of its own: the lines of Q[0]
+// (the generator of G2) and Q[1] ([tau]G2) into tab[0, 2 * MILLER_LINES); verdict[i] for m openings, MALFORMED where
+// status[i] is not ST_OK (such a lane reads neither L nor pi).  All pointers on the device
+void launch_kzg_line_tables(Line *tab, const G2Affine *Q, const PairConsts *k, hipStream_t s);
+void launch_kzg_pair(uint8_t *verdict, const uint32_t *status, const G1Affine *L, const G1Affine *pi, const Line *tab, uint64_t m, const PairConsts *k,
+                     hipStream_t s);
+
 // ---------------------------------------------------------------- host: the multiplication over resident bases
 // operators.hip's msm_generic without the upload and the conversion of the bases: pts is already in the kernels' own form
 inline void msm_resident(DevMsm<Fq> &e, uint8_t out[64], const G1Affine *pts, const Fr *sc, uint64_t n, hipStream_t s) {

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "ptengine.hpp"
+#include "plonk_verify_dev.hpp"
 
 namespace zkp {
 
@@ -14,12 +15,12 @@ enum { P_A, P_B, P_C, P_Z, P_TLO, P_TMID, P_THI, P_WZ, P_WZW };     // the proof
 static_assert(ZK_PLONK_PROOF_BYTES == PLONK_POINTS * 64 + PLONK_EVALS * 32, "layout");
 
 // ---------------------------------------------------------------- Keccak-256
+inline constexpr uint64_t KECCAK_RC[24] = {0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull,
+                                             0x0000000080000001ull, 0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull,
+                                             0x0000000080008009ull, 0x000000008000000aull, 0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull,
+                                             0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull, 0x000000000000800aull, 0x800000008000000aull,
+                                             0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
 inline void keccak_f(uint64_t st[25]) {
-    static const uint64_t RC[24] = {0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808aull, 0x8000000080008000ull, 0x000000000000808bull,
-                                    0x0000000080000001ull, 0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008aull, 0x0000000000000088ull,
-                                    0x0000000080008009ull, 0x000000008000000aull, 0x000000008000808bull, 0x800000000000008bull, 0x8000000000008089ull,
-                                    0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull, 0x000000000000800aull, 0x800000008000000aull,
-                                    0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
     static const int ROT[24] = {1, 3, 6, 10, 15, 21, 28, 36, 45, 55, 2, 14, 27, 41, 56, 8, 25, 43, 62, 18, 39, 61, 20, 44};
     static const int PIL[24] = {10, 7, 11, 17, 18, 3, 5, 16, 8, 21, 24, 4, 15, 23, 19, 13, 12, 2, 20, 14, 22, 9, 6, 1};
     auto rotl64 = [](uint64_t x, int k) { return (x << k) | (x >> (64 - k)); };
@@ -41,7 +42,7 @@ inline void keccak_f(uint64_t st[25]) {
             for (int i = 0; i < 5; i++) bc[i] = st[j + i];
             for (int i = 0; i < 5; i++) st[j + i] ^= (~bc[(i + 1) % 5]) & bc[(i + 2) % 5];
         }
-        st[0] ^= RC[round];
+        st[0] ^= KECCAK_RC[round];
     }
 }
 
@@ -119,6 +120,41 @@ struct Transcript {
 struct Challenges {
     Fr beta, gamma, alpha, zeta, v, u;                // Montgomery
 };
+
+// a point of the curve in the file's form (or infinity), both coordinates below q
+inline bool g1_well_formed(const uint8_t p[64]) {
+    static const uint8_t zero[64] = {0};
+    if (memcmp(p, zero, 64) == 0) return true;
+    if (!below(p, FqParams::P) || !below(p + 32, FqParams::P)) return false;
+    Fq x, y;
+    memcpy(x.v, p, 32);
+    memcpy(y.v, p + 32, 32);
+    return Fq::sqr(y) == Fq::add(Fq::mul(Fq::sqr(x), x), curve_b<Fq>());
+}
+
+// What a lane of the device verifier needs of a checked key (plonk_verify_dev.hpp): the sponge after the 512 bytes every
+// round-1 message of the key begins with, three blocks permuted and the 13 words of the fourth absorbed
+inline PlonkVerifyConsts plonk_verify_consts(const zk_plonk_vkey &vk, const Fr &k1, const Fr &k2) {
+    PlonkVerifyConsts K{};
+    Transcript t;
+    const uint8_t *vkp[8] = {vk.qm, vk.ql, vk.qr, vk.qo, vk.qc, vk.s1, vk.s2, vk.s3};
+    for (uint32_t j = 0; j < 8; j++) t.point(vkp[j]);
+    for (uint32_t i = 0; i < 64; i++) {
+        uint64_t w = 0;
+        for (int b = 7; b >= 0; b--) w = (w << 8) | t.buf[i * 8 + b];
+        K.st[i % PV_RATE_WORDS] ^= w;
+        if (i % PV_RATE_WORDS == PV_RATE_WORDS - 1) keccak_f(K.st);
+    }
+    static_assert(64 % PV_RATE_WORDS == PV_KEY_WORDS, "the key's 512 bytes end 13 words into a block");
+    for (int i = 0; i < 24; i++) K.rc[i] = KECCAK_RC[i];
+    K.n_public = vk.n_public;
+    K.log_n = vk.log_n;
+    K.k1 = k1, K.k2 = k2;
+    K.w = root_of_unity(vk.log_n);
+    K.n = fr_small(1ull << vk.log_n);
+    K.b = curve_b<Fq>();
+    return K;
+}
 
 inline void round1_challenges(Challenges &c, const zk_plonk_vkey &vk, const uint8_t *publics, const uint8_t *pts) {
     Transcript t;

@@ -9,17 +9,6 @@ namespace {
 
 typedef Pt<Fq> P1;
 
-// a point of the curve in the file's form (or infinity), both coordinates below q
-bool g1_well_formed(const uint8_t p[64]) {
-    static const uint8_t zero[64] = {0};
-    if (memcmp(p, zero, 64) == 0) return true;
-    if (!below(p, FqParams::P) || !below(p + 32, FqParams::P)) return false;
-    Fq x, y;
-    memcpy(x.v, p, 32);
-    memcpy(y.v, p + 32, 32);
-    return Fq::sqr(y) == Fq::add(Fq::mul(Fq::sqr(x), x), curve_b<Fq>());
-}
-
 void plonk_verify(zk_kzg *kzg, const zk_plonk_vkey *vk, const uint8_t *proof, const uint8_t *publics, uint8_t *verdict) {
     const char *who = "zk_plonk_verify";
     if (!kzg || !vk || !proof || !verdict || (vk->n_public && !publics)) throw std::invalid_argument("null argument");

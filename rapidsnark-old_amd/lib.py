@@ -199,6 +199,11 @@ class zk_plonk_prover_plan(C.Structure):
                 ("round_launches", C.c_uint32 * 5)]
 
 
+class zk_plonk_verifier_plan(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("log_n", C.c_uint32), ("n_public", C.c_uint64), ("device_bytes", C.c_uint64), ("chunk", C.c_uint64),
+                ("last_launches", C.c_uint32), ("last_chunks", C.c_uint32)]
+
+
 class zk_plonk_r1cs_plan(C.Structure):
     _fields_ = [("size", C.c_uint32), ("log_n", C.c_uint32), ("rows", C.c_uint64), ("n_public", C.c_uint64), ("n_wires", C.c_uint64),
                 ("n_additions", C.c_uint64), ("n_witness", C.c_uint64), ("terms", C.c_uint64), ("device_bytes", C.c_uint64), ("seg", C.c_uint32),
@@ -267,7 +272,8 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_keccak256", "zk_plonk_prover_create", "zk_plonk_prover_destroy", "zk_plonk_prover_vkey", "zk_plonk_prover_info", "zk_plonk_prove",
            "zk_plonk_verify",
            "zk_plonk_r1cs_create", "zk_plonk_r1cs_destroy", "zk_plonk_r1cs_info", "zk_plonk_r1cs_circuit", "zk_plonk_r1cs_extend",
-           "zk_plonk_prover_create_r1cs", "zk_plonk_prove_r1cs"]
+           "zk_plonk_prover_create_r1cs", "zk_plonk_prove_r1cs",
+           "zk_plonk_verifier_create", "zk_plonk_verifier_destroy", "zk_plonk_verifier_info", "zk_plonk_verifier_verify", "zk_plonk_verifier_challenges"]
 ZK_SCAN_EXCLUSIVE = 1
 ZK_KZG_MONOMIAL, ZK_KZG_LAGRANGE, ZK_KZG_NO_LAGRANGE = 0, 1, 0xffffffff
 ZK_SCALE_PLAN_MAX = 130
@@ -465,6 +471,13 @@ def load_library():
         lib.zk_plonk_r1cs_extend.argtypes = [C.c_void_p, u8p, u8p, C.c_uint32]
         lib.zk_plonk_prover_create_r1cs.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, u8p, C.c_int32]
         lib.zk_plonk_prove_r1cs.argtypes = [C.c_void_p, u8p, u8p, C.c_uint32, u8p]
+    if hasattr(lib, "zk_plonk_verifier_create"):
+        lib.zk_plonk_verifier_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(zk_plonk_vkey), C.c_int32]
+        lib.zk_plonk_verifier_destroy.argtypes = [C.c_void_p]
+        lib.zk_plonk_verifier_destroy.restype = None
+        lib.zk_plonk_verifier_info.argtypes = [C.c_void_p, C.POINTER(zk_plonk_verifier_plan)]
+        lib.zk_plonk_verifier_verify.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p]
+        lib.zk_plonk_verifier_challenges.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p, u8p]
     _LIB = lib
     return lib
 

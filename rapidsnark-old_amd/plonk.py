@@ -320,11 +320,166 @@ class PlonkProof:
         return hash(self._b)
 
 
+_COMMITMENTS = ("qm", "ql", "qr", "qo", "qc", "s1", "s2", "s3")          # the transcript's order
+_KEY_POINTS = ("Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3")           # snarkjs's names for them
+
+
+def root_of_unity(power):
+    """zk_fr_ntt's root for 2^power (the `w` of a key file): 5^((r - 1) / 2^28) squared 28 - power times"""
+    return pow(pow(5, (R_MOD - 1) >> 28, R_MOD), 1 << (28 - power), R_MOD)
+
+
+def _coords_to_bytes(coords, what):
+    """standard coordinates below 2^256 -> the .ptau encoding; one that is not below q goes as written, for the library to refuse"""
+    out = b""
+    for x in coords:
+        if not 0 <= x < 1 << 256:
+            raise ValueError("%s: a coordinate is not in 0 .. 2^256 - 1" % what)
+        out += (x * (1 << 256) % Q_MOD if x < Q_MOD else x).to_bytes(32, "little")
+    return out
+
+
+def _g1_bytes(p, what):
+    """64 bytes in the .ptau encoding, or (x, y) standard ints, or None (infinity) -> 64 bytes"""
+    if p is None:
+        return bytes(64)
+    if isinstance(p, (bytes, bytearray, memoryview, np.ndarray)):
+        b = bytes(p)
+        if len(b) != 64:
+            raise ValueError("%s: a point of 64 bytes expected, got %d" % (what, len(b)))
+        return b
+    x, y = p
+    return _coords_to_bytes((int(x), int(y)), what)
+
+
+def _g2_bytes(p, what):
+    """128 bytes, or ((xa, xb), (ya, yb)), or None -> 128 bytes"""
+    if p is None:
+        return bytes(128)
+    if isinstance(p, (bytes, bytearray, memoryview, np.ndarray)):
+        b = bytes(p)
+        if len(b) != 128:
+            raise ValueError("%s: a point of 128 bytes expected, got %d" % (what, len(b)))
+        return b
+    (xa, xb), (ya, yb) = p
+    return _coords_to_bytes((int(xa), int(xb), int(ya), int(yb)), what)
+
+
+def _dec(v, what):
+    if isinstance(v, bool) or not isinstance(v, (str, int)) or (isinstance(v, str) and not v.isdigit()):
+        raise ValueError("%s is not a decimal integer below 2^256" % what)
+    x = int(v)
+    if not 0 <= x < 1 << 256:
+        raise ValueError("%s is not a decimal integer below 2^256" % what)
+    return x
+
+
+def _json_g1(v, what):
+    """[x, y] or [x, y, z] -> 64 bytes; z = 0 is infinity, any other z divides x and y (as `verifier` reads a point)"""
+    if not isinstance(v, list) or len(v) < 2:
+        raise ValueError("%s is not an array of at least 2 elements" % what)
+    c = [_dec(t, "%s[%d]" % (what, i)) for i, t in enumerate(v[:3])]
+    if len(c) == 3 and all(t < Q_MOD for t in c):
+        if c[2] == 0:
+            return bytes(64)
+        zi = pow(c[2], -1, Q_MOD)
+        c = [c[0] * zi % Q_MOD, c[1] * zi % Q_MOD]
+    return _coords_to_bytes(c[:2], what)
+
+
+def _json_g2(v, what):
+    if not isinstance(v, list) or len(v) < 2 or not all(isinstance(t, list) and len(t) >= 2 for t in v[:3]):
+        raise ValueError("%s is not an array of at least 2 pairs" % what)
+    c = [[_dec(t, "%s[%d][%d]" % (what, i, j)) for j, t in enumerate(pair[:2])] for i, pair in enumerate(v[:3])]
+    if len(c) == 3 and all(t < Q_MOD for pair in c for t in pair):
+        za, zb = c[2]
+        if za == 0 and zb == 0:
+            return bytes(128)
+        d = pow(za * za + zb * zb, -1, Q_MOD)                       # 1 / (za + zb u) = (za - zb u) / (za^2 + zb^2)
+        ia, ib = za * d % Q_MOD, -zb * d % Q_MOD
+        c = [[(a * ia - b * ib) % Q_MOD, (a * ib + b * ia) % Q_MOD] for a, b in c[:2]]
+    return _coords_to_bytes(c[0] + c[1], what)
+
+
 class PlonkVKey:
-    """What plonk_verify needs (zk_plonk_vkey) and the Kzg whose [tau]G2 it names."""
+    """What a verifier needs (zk_plonk_vkey): log_n, n_public, k1, k2, the eight commitments and [tau]G2.  A key a prover
+    made keeps the Kzg whose [tau]G2 it names, for plonk_verify; one read from a key file or made from parts has kzg = None
+    and is what a PlonkVerifier takes.  The key file has snarkjs's field names (to_json); it names a key of THIS project's
+    compile and transcript: parity with snarkjs is unpinned."""
 
     def __init__(self, kzg, c):
         self.kzg, self._c = kzg, c
+
+    @classmethod
+    def from_parts(cls, log_n, n_public, k1, k2, commitments, tau_g2):
+        """commitments: eight points in the transcript's order qm ql qr qo qc s1 s2 s3 (or a dict by those names), each 64
+        bytes in the .ptau encoding, (x, y) standard ints or None for infinity; tau_g2: 128 bytes or ((xa, xb), (ya, yb)).
+        Nothing is judged here but the shapes: a bad key is zk_plonk_verifier_create's to refuse."""
+        if isinstance(commitments, dict):
+            commitments = [commitments[name] for name in _COMMITMENTS]
+        commitments = list(commitments)
+        if len(commitments) != 8:
+            raise ValueError("commitments: %d points, 8 expected" % len(commitments))
+        c = L.zk_plonk_vkey()
+        c.size = C.sizeof(c)
+        log_n, n_public = int(log_n), int(n_public)
+        if not 0 <= log_n < 1 << 32 or not 0 <= n_public < 1 << 64:
+            raise ValueError("log_n or n_public is out of range")
+        c.log_n, c.n_public = log_n, n_public
+        for name, v in (("k1", k1), ("k2", k2)):
+            v = int(v)
+            if not 0 <= v < 1 << 256:
+                raise ValueError("%s is not in 0 .. 2^256 - 1" % name)
+            C.memmove(getattr(c, name), v.to_bytes(32, "little"), 32)
+        for name, p in zip(_COMMITMENTS, commitments):
+            C.memmove(getattr(c, name), _g1_bytes(p, name), 64)
+        C.memmove(c.tau_g2, _g2_bytes(tau_g2, "tau_g2"), 128)
+        return cls(None, c)
+
+    def to_json(self):
+        """verification_key.json with snarkjs's field names for PLONK: protocol, curve, nPublic, power, k1, k2, Qm Ql Qr Qo Qc
+        S1 S2 S3, X_2, w; decimal strings, projective points with z = 1 (infinity: 0 1 0)"""
+        import json
+        d = {"protocol": "plonk", "curve": "bn128", "nPublic": self.n_public, "power": self.log_n, "k1": str(self.k1), "k2": str(self.k2)}
+        for key, name in zip(_KEY_POINTS, _COMMITMENTS):
+            xy = _affine(bytes(getattr(self._c, name)))
+            d[key] = ["0", "1", "0"] if xy is None else [str(xy[0]), str(xy[1]), "1"]
+        t = self.tau_g2
+        if not any(t):
+            d["X_2"] = [["0", "0"], ["1", "0"], ["0", "0"]]
+        else:
+            v = [str(int.from_bytes(t[i * 32:(i + 1) * 32], "little") * _Q_RINV % Q_MOD) for i in range(4)]
+            d["X_2"] = [v[0:2], v[2:4], ["1", "0"]]
+        d["w"] = str(root_of_unity(self.log_n)) if 0 <= self.log_n <= 28 else "0"
+        return json.dumps(d, indent=1)
+
+    @classmethod
+    def from_json(cls, text):
+        """The key of to_json, of the program plonkvkey, or of snarkjs (third coordinates honoured as `verifier` does).
+        Refused by name: another protocol or curve, a power outside 0 .. 28, a w that is not this library's root for the
+        power."""
+        import json
+        try:
+            d = json.loads(text)
+        except ValueError as e:
+            raise ValueError("the key is not JSON (%s)" % e)
+        if not isinstance(d, dict):
+            raise ValueError("the key is not a JSON object")
+        if d.get("protocol") != "plonk":
+            raise ValueError("protocol \"%s\" is not plonk" % d.get("protocol"))
+        if d.get("curve") not in ("bn128", "bn254"):
+            raise ValueError("curve \"%s\" is not bn128" % d.get("curve"))
+        for key in ("nPublic", "power", "k1", "k2", "X_2", "w") + _KEY_POINTS:
+            if key not in d:
+                raise ValueError("the key has no \"%s\"" % key)
+        power, n_public = _dec(d["power"], "power"), _dec(d["nPublic"], "nPublic")
+        if power > 28:
+            raise ValueError("power %d is outside 0 .. 28" % power)
+        if _dec(d["w"], "w") != root_of_unity(power):
+            raise ValueError("w is not this library's root of unity for power %d" % power)
+        if n_public >= 1 << 64:
+            raise ValueError("nPublic is not below 2^64")
+        return cls.from_parts(power, n_public, _dec(d["k1"], "k1"), _dec(d["k2"], "k2"), [_json_g1(d[k], k) for k in _KEY_POINTS], _json_g2(d["X_2"], "X_2"))
 
     log_n = property(lambda self: int(self._c.log_n))
     n = property(lambda self: 1 << int(self._c.log_n))
@@ -543,8 +698,89 @@ def plonk_verify(vkey, proof, publics=(), kzg=None):
     if pb.size != vkey.n_public * 32:
         raise ValueError("publics: %d values, n_public = %d expected" % (pb.size // 32, vkey.n_public))
     k = kzg if kzg is not None else vkey.kzg
+    if k is None:
+        raise ValueError("the key names no Kzg (it was read from a key file or made from parts): pass kzg=, or verify with PlonkVerifier(vkey), "
+                         "which needs the key alone")
     h = k._handle()
     a = L._buf(pr.to_bytes())
     verdict = np.full(1, 255, dtype=np.uint8)
     L.check(L.load_library().zk_plonk_verify(h, C.byref(vkey._c), L._ptr(a), L._ptr(pb) if vkey.n_public else None, L._ptr(verdict)))
     return int(verdict[0])
+
+
+class PlonkVerifier(_Object):
+    """A verifier for one key, made from the key alone (zk_plonk_verifier): no Kzg and no .ptau.  verify() judges m proofs a
+    call, each with its own verdict, and everything per proof (the checks, the Keccak transcript, the scalars, the nineteen
+    products, the pairing) runs on the device.  ZKHIP_PLONK_VERIFY_CHUNK bounds the memory of a call and changes no
+    verdict."""
+    _name, _destroy, _info, _plan = "PlonkVerifier", "zk_plonk_verifier_destroy", "zk_plonk_verifier_info", L.zk_plonk_verifier_plan
+    _drop = ("size",)
+
+    def __init__(self, vkey, device=-1):
+        if not isinstance(vkey, PlonkVKey):
+            raise TypeError("a PlonkVKey expected (PlonkProver.vkey(), PlonkVKey.from_json or PlonkVKey.from_parts)")
+        self._h = C.c_void_p()
+        self.vkey, self.log_n, self.n_public, self.device = vkey, vkey.log_n, vkey.n_public, int(device)
+        L.check(L.load_library().zk_plonk_verifier_create(C.byref(self._h), C.byref(vkey._c), device))
+
+    def _inputs(self, proofs, publics):
+        """-> (proof bytes, public bytes or None, m)"""
+        if isinstance(proofs, np.ndarray):
+            if proofs.dtype != np.uint8 or proofs.ndim != 2 or proofs.shape[1] != PROOF_BYTES:
+                raise ValueError("proofs: a uint8 array of m rows of %d bytes expected" % PROOF_BYTES)
+            a = np.ascontiguousarray(proofs).reshape(-1)
+        else:
+            rows = [p.to_bytes() if isinstance(p, PlonkProof) else PlonkProof(p).to_bytes() for p in proofs]
+            a = np.frombuffer(b"".join(rows), dtype=np.uint8)
+        m = a.size // PROOF_BYTES
+        if self.n_public == 0:
+            if publics is not None and any(len(row) for row in publics):
+                raise ValueError("publics: the key has no public inputs")
+            return a, None, m
+        if publics is None:
+            raise ValueError("publics: %d rows of n_public = %d values expected" % (m, self.n_public))
+        # values that are not below r are the library's to call MALFORMED: they must only fit 32 bytes
+        if isinstance(publics, np.ndarray) and publics.dtype == np.uint8:
+            pb = np.ascontiguousarray(publics).reshape(-1)
+            if pb.size != m * self.n_public * 32:
+                raise ValueError("publics: %d bytes, %d rows of n_public = %d values expected" % (pb.size, m, self.n_public))
+            return a, pb, m
+        publics = list(publics)
+        if len(publics) != m:
+            raise ValueError("publics: %d rows for %d proofs" % (len(publics), m))
+        rows = []
+        for i, row in enumerate(publics):
+            r = _scalars(row, "publics[%d]" % i, below_r=False)
+            if r.size != self.n_public * 32:
+                raise ValueError("publics[%d]: %d values, n_public = %d expected" % (i, r.size // 32, self.n_public))
+            rows.append(r)
+        return a, (np.concatenate(rows) if rows else np.zeros(0, dtype=np.uint8)), m
+
+    def verify(self, proofs, publics=None):
+        """numpy uint8 [m]: VERIFY_OK (0) / VERIFY_INVALID (1) / VERIFY_MALFORMED (2) a proof, what plonk_verify gives it
+        (zk_plonk_verifier_verify).  proofs: a list of PlonkProof or of 768 bytes each, or a uint8 array (m, 768).  publics: m
+        rows of n_public ints (or a uint8 array of m x n_public x 32 bytes); None when the key has no public inputs."""
+        a, pb, m = self._inputs(proofs, publics)
+        h = self._handle()
+        verdict = np.full(m, 255, dtype=np.uint8)
+        L.check(L.load_library().zk_plonk_verifier_verify(h, L._ptr(a) if m else None, L._ptr(pb) if pb is not None and m else None, m,
+                                                          L._ptr(verdict) if m else None))
+        return verdict
+
+    def challenges(self, proofs, publics=None):
+        """(m lists of six ints beta gamma alpha zeta v u, numpy uint8 [m] status): the first kernel alone
+        (zk_plonk_verifier_challenges).  status 0: well-formed; 2: malformed, and the row is all zero.  For tests of the device
+        transcript on inputs that are no valid proofs, and for finding the first difference against another implementation."""
+        a, pb, m = self._inputs(proofs, publics)
+        h = self._handle()
+        ch = np.zeros(m * 6 * 32, dtype=np.uint8)
+        status = np.full(m, 255, dtype=np.uint8)
+        L.check(L.load_library().zk_plonk_verifier_challenges(h, L._ptr(a) if m else None, L._ptr(pb) if pb is not None and m else None, m,
+                                                              L._ptr(ch) if m else None, L._ptr(status) if m else None))
+        raw = ch.tobytes()
+        return [[int.from_bytes(raw[(i * 6 + j) * 32:(i * 6 + j + 1) * 32], "little") for j in range(6)] for i in range(m)], status
+
+    def info(self):
+        """zk_plonk_verifier_info -> dict: log_n, n_public, device_bytes, chunk (ZKHIP_PLONK_VERIFY_CHUNK in effect),
+        last_launches, last_chunks"""
+        return self._plan_dict()[1]
