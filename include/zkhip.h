@@ -1257,6 +1257,53 @@ int zk_plonk_verifier_verify(zk_plonk_verifier *v, const uint8_t *proofs, const 
  * below 2^31" and the knob as above, under this entry's name. */
 int zk_plonk_verifier_challenges(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publics, uint64_t m, uint8_t *challenges, uint8_t *status);
 
+/* Batch verification by random linear combination, every proof's own verdict kept.  Arguments, layouts, verdict codes, m = 0,
+ * "zk_plonk_verifier_verify_batch: m is not below 2^31" and ZKHIP_PLONK_VERIFY_CHUNK are zk_plonk_verifier_verify's.  Inside a
+ * chunk, consecutive proofs form groups of ZKHIP_PLONK_VERIFY_GROUP (decimal, 1 to 2^20, read at every call, 65536 otherwise;
+ * anything else is an error of the call, "ZKHIP_PLONK_VERIFY_GROUP: a number of proofs from 1 to 2^20 expected"; a group never
+ * straddles a chunk and a chunk's last group may be short).  Malformed proofs are found first, by the transcript kernel's own
+ * checks, get MALFORMED and take no part in any sum; a group of malformed proofs alone evaluates no equation.  Every
+ * well-formed proof i asks e(L_i, G2) = e(W_i, [tau]G2) with L_i = sum_(t < 18) s_it B_it and W_i = W_zeta,i + u_i
+ * W_zeta_omega,i: nine bases F_t that all proofs share (the key's eight commitments and the generator) and the proof's own
+ * nine points P_ij.  With a scalar r_i per proof, over a group's well-formed proofs
+ *     S_t = sum_i r_i s_it (t < 9, in Fr),   L = sum_t S_t F_t + sum_i sum_j (r_i s_i,9+j) P_ij,
+ *     W = sum_i r_i W_zeta,i + (r_i u_i) W_zeta_omega,i,
+ * and the group passes iff e(L, G2) e(-W, [tau]G2) = 1: no pairing per proof, eleven points per proof in two bucket
+ * multiplications per group, the scalars made and folded on the device, one cooperative pairing product per group.  A
+ * passing group gives OK to its well-formed proofs.  The well-formed proofs of a failing group are verified one by one by
+ * zk_plonk_verifier_verify's own kernels from the status and scalars already on the device (all failed groups of a chunk
+ * before the chunk's verdicts leave), which gives each OK or INVALID.  So a valid proof always gets OK, and an INVALID one
+ * gets OK only if its group passes, which at most one of the 2^128 - 1 values of its scalar allows: with scalars the prover
+ * cannot foresee, a probability of at most 1 / (2^128 - 1) per group.  A batch with many invalid proofs pays the
+ * combination and then the per-proof code for every failing group: use zk_plonk_verifier_verify, or a smaller group
+ * (profiles/plonk_verify_batch_timing.txt, 65536 proofs: 21 ms all valid against zk_plonk_verifier_verify's 89 ms; with ONE
+ * invalid proof 107 ms in one group of 65536 and 78 ms in groups of 16384; with 1 % invalid every group fails at every size).
+ * scalars16 is FOR TESTS ONLY: m x 16 bytes little-endian, r_i of proof i; a zero scalar is an error of the call,
+ * "zk_plonk_verifier_verify_batch: scalar 3 is zero".  NULL: the library draws them with getrandom() after the call has its
+ * inputs, 16 bytes each, redrawn while zero.  Scalars an adversary knows or can predict before fixing the proofs are unsound:
+ * two wrong proofs whose errors cancel under those scalars (r_i d_i + r_j d_j = 0) pass as a group and both get OK.  Never
+ * pass constants, counters or a seeded generator.
+ * report (may be NULL; set report->size = sizeof first, as for zk_vkey_batch_report): group is the group size the call used,
+ * min(the knob, the chunk's capacity); groups counts the groups with at least one well-formed proof, the ones whose equation
+ * was evaluated; proofs_rechecked the well-formed proofs sent through the per-proof kernels; launches every kernel launch of
+ * the call.  After a batch call zk_plonk_verifier_info reports last_launches = report->launches and the call's chunks.  The
+ * batch buffers (about 1.4 KB a proof, the two multiplications' workspaces, and the nine fixed bases in the bucket kernels'
+ * form) are made by the object's first batch call, after the free HBM has been checked, and count in device_bytes. */
+typedef struct {
+    uint32_t size;              /* sizeof, set by the caller */
+    uint32_t group;             /* the group size the call used */
+    uint64_t groups, groups_failed;
+    uint64_t proofs_rechecked, malformed;
+    uint32_t launches, chunks;
+} zk_plonk_batch_report;
+int zk_plonk_verifier_verify_batch(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publics, uint64_t m, const uint8_t *scalars16, uint8_t *verdict,
+                                   zk_plonk_batch_report *report /* may be NULL */);
+/* FOR TESTS: sums[g] = L | W of group g (128 bytes, the file's form; 128 zero bytes for a group with no well-formed proof),
+ * in the order the groups are formed; n_groups = the number written.  No pairing is run.  scalars16 must be given;
+ * "zk_plonk_verifier_batch_sums: sums_cap 2 is below the call's 3 groups". */
+int zk_plonk_verifier_batch_sums(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publics, uint64_t m, const uint8_t *scalars16, uint8_t *sums,
+                                 uint64_t sums_cap, uint64_t *n_groups);
+
 /* ---- PLONK from an R1CS ---------------------------------------------------------------------- */
 /* A circom .r1cs compiled on the device to what zk_plonk_prover_create takes: the five selectors, the three wire maps and the
  * permutation s1 s2 s3; the extension of a circom witness by the wires the compile introduces; and a prover made from the

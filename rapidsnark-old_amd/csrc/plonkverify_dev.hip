@@ -12,13 +12,10 @@
 //   k_kzg_pair          kzg.hip's, over the object's own line tables: e(L, G2) = e(W, [tau]G2)
 // Every addition is curve.hpp's complete one: a zero scalar, a base at infinity, a term that cancels the running sum and
 // L or W at infinity take no special path here.  A malformed proof's lanes return at once in every kernel.
-#include "plonk_internal.hpp"
+#include "plonk_verifier_internal.hpp"
 #include "plonk_transcript.hpp"
 
 namespace {
-
-constexpr uint64_t DEFAULT_CHUNK = 65536, MAX_CHUNK = 1ull << 20;       // 65536: a wave of pairing lanes on every SIMD (profiles/plonk_verifier_timing.txt)
-uint64_t chunk_in_effect() { return env_number("ZKHIP_PLONK_VERIFY_CHUNK", DEFAULT_CHUNK, 1, MAX_CHUNK, "a number of proofs from 1 to 2^20"); }
 
 // ---------------------------------------------------------------- device
 __global__ __launch_bounds__(64) void k_plonk_transcript(uint32_t *status, uint8_t *ch, Fr *sc, const uint8_t *__restrict__ proofs,
@@ -61,55 +58,7 @@ __global__ __launch_bounds__(64) void k_plonk_sum(G1Affine *L, G1Affine *W, cons
     store_el(&W[i].y, w.y);
 }
 
-}   // namespace
-
-// ---------------------------------------------------------------- the object
-struct zk_plonk_verifier {
-    int device = 0;
-    uint32_t log_n = 0;
-    uint64_t n_public = 0;
-    std::mutex mu;                                    // calls on one object are serialised
-    std::unique_ptr<Stream> st;
-    Consts kc;
-    DevBuf<Line> tab;                                 // the G2 generator's lines, then [tau]G2's
-    DevBuf<G1Affine> fixed;                           // the key's eight commitments and the generator, the file's form
-    DevBuf<PlonkVerifyConsts> kv;
-    Fq endo;
-    // a chunk of proofs; grown, never shrunk
-    uint64_t cap = 0;
-    DevBuf<uint8_t> proofs, publics, ch, verdict;
-    DevBuf<uint32_t> status;
-    DevBuf<Fr> sc;                                    // PV_TERMS rows of cap
-    DevBuf<G1XYZZ> part;
-    DevBuf<G1Affine> L, W;
-    uint32_t last_launches = 0, last_chunks = 0;
-    static uint64_t chunk_bytes(uint64_t cap_, uint64_t n_public_) {
-        return cap_ * (PV_PROOF_BYTES + (n_public_ ? n_public_ : 1) * 32 + PV_CHALLENGES * 32 + 1 + 4 + PV_TERMS * (sizeof(Fr) + sizeof(G1XYZZ)) +
-                       2 * sizeof(G1Affine));
-    }
-    size_t bytes() const {
-        return tab.bytes() + fixed.bytes() + kv.bytes() + sizeof(PairConsts) + proofs.bytes() + publics.bytes() + ch.bytes() + verdict.bytes() +
-               status.bytes() + sc.bytes() + part.bytes() + L.bytes() + W.bytes();
-    }
-    void size(const char *who, uint64_t cap_) {
-        if (cap_ <= cap) return;
-        need_hbm(who, chunk_bytes(cap_, n_public));
-        cap = 0;
-        proofs.alloc(cap_ * PV_PROOF_BYTES);
-        publics.alloc(cap_ * (n_public ? n_public : 1) * 32);
-        ch.alloc(cap_ * PV_CHALLENGES * 32);
-        verdict.alloc(cap_);
-        status.alloc(cap_);
-        sc.alloc(cap_ * PV_TERMS);
-        part.alloc(cap_ * PV_TERMS);
-        L.alloc(cap_);
-        W.alloc(cap_);
-        cap = cap_;
-    }
-};
-
-namespace {
-
+// ---------------------------------------------------------------- the object (plonk_verifier_internal.hpp)
 zk_plonk_verifier *verifier_create(const zk_plonk_vkey *vk, int32_t device) {
     const char *who = "zk_plonk_verifier_create";
     if (!vk) throw std::invalid_argument("null argument");
@@ -136,6 +85,7 @@ zk_plonk_verifier *verifier_create(const zk_plonk_vkey *vk, int32_t device) {
     v->log_n = vk->log_n;
     v->n_public = vk->n_public;
     v->endo = endo_const<Fq>();
+    memcpy(v->q2, q2, sizeof q2);
     DeviceGuard g(v->device);
     need_hbm(who, 2 * MILLER_LINES * sizeof(Line) + sizeof fixed + sizeof q2 + sizeof K + sizeof(PairConsts) + 65536);
     v->st.reset(new Stream);
@@ -161,42 +111,10 @@ zk_plonk_verifier *verifier_create(const zk_plonk_vkey *vk, int32_t device) {
     return v.release();
 }
 
-// the checks both calls make, then run(off, cnt) for every chunk with the chunk's proofs and publics on the device
-template <class Run>
-void over_chunks(zk_plonk_verifier *v, const char *who, const uint8_t *proofs, const uint8_t *publics, uint64_t m, const void *out1, const void *out2, Run run) {
-    if (!v) throw std::invalid_argument("null argument");
-    if (!m) return;
-    if (m >= (1ull << 31)) throw std::invalid_argument(std::string(who) + ": m is not below 2^31");
-    if (!proofs || !out1 || !out2 || (v->n_public && !publics)) throw std::invalid_argument("null argument");
-    const uint64_t chunk = chunk_in_effect(), cap = m < chunk ? m : chunk;
-    std::lock_guard<std::mutex> lock(v->mu);
-    DeviceGuard g(v->device);
-    LaunchCount lc(v->last_launches);
-    v->last_chunks = 0;
-    v->size(who, cap);
-    hipStream_t s = v->st->s;
-    for (uint64_t off = 0; off < m; off += cap) {
-        const uint64_t cnt = m - off < cap ? m - off : cap;
-        HIP_TRY(hipMemcpyAsync(v->proofs.p, proofs + off * PV_PROOF_BYTES, cnt * PV_PROOF_BYTES, hipMemcpyHostToDevice, s));
-        if (v->n_public) HIP_TRY(hipMemcpyAsync(v->publics.p, publics + off * v->n_public * 32, cnt * v->n_public * 32, hipMemcpyHostToDevice, s));
-        run(off, cnt, s);
-        v->last_chunks++;
-    }
-}
-
-void launch_transcript(zk_plonk_verifier *v, uint64_t cnt, bool want_scalars, hipStream_t s) {
-    ZK_LAUNCH(k_plonk_transcript, dim3(nblocks(cnt, 64)), dim3(64), 0, s, v->status.p, v->ch.p, v->sc.p, v->proofs.p, v->publics.p, cnt, v->cap, v->kv.p,
-              want_scalars ? 1u : 0u);
-}
-
 void verifier_verify(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publics, uint64_t m, uint8_t *verdict) {
     over_chunks(v, "zk_plonk_verifier_verify", proofs, publics, m, verdict, verdict, [&](uint64_t off, uint64_t cnt, hipStream_t s) {
         launch_transcript(v, cnt, true, s);
-        ZK_LAUNCH(k_plonk_combine, dim3(nblocks(cnt * PV_TERMS, 64)), dim3(64), 0, s, v->part.p, v->status.p, v->sc.p, v->proofs.p, v->fixed.p, cnt, v->cap,
-                  v->endo);
-        ZK_LAUNCH(k_plonk_sum, dim3(nblocks(cnt, 64)), dim3(64), 0, s, v->L.p, v->W.p, v->status.p, v->part.p, v->proofs.p, cnt, v->cap);
-        ZK_LAUNCH_OK("plonk verification");
-        launch_kzg_pair(v->verdict.p, v->status.p, v->L.p, v->W.p, v->tab.p, cnt, v->kc.k.p, s);
+        launch_per_proof(v, 0, cnt, s);
         HIP_TRY(hipMemcpyAsync(verdict + off, v->verdict.p, cnt, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     });
@@ -216,6 +134,21 @@ void verifier_challenges(zk_plonk_verifier *v, const uint8_t *proofs, const uint
 }
 
 }   // namespace
+
+// ---------------------------------------------------------------- what plonkverify_batch.hip launches too (plonk_verifier_internal.hpp)
+void launch_transcript(zk_plonk_verifier *v, uint64_t cnt, bool want_scalars, hipStream_t s) {
+    ZK_LAUNCH(k_plonk_transcript, dim3(nblocks(cnt, 64)), dim3(64), 0, s, v->status.p, v->ch.p, v->sc.p, v->proofs.p, v->publics.p, cnt, v->cap, v->kv.p,
+              want_scalars ? 1u : 0u);
+}
+
+void launch_per_proof(zk_plonk_verifier *v, uint64_t lo, uint64_t cnt, hipStream_t s) {
+    const uint8_t *proofs = v->proofs.p + lo * PV_PROOF_BYTES;
+    ZK_LAUNCH(k_plonk_combine, dim3(nblocks(cnt * PV_TERMS, 64)), dim3(64), 0, s, v->part.p + lo, v->status.p + lo, v->sc.p + lo, proofs, v->fixed.p, cnt, v->cap,
+              v->endo);
+    ZK_LAUNCH(k_plonk_sum, dim3(nblocks(cnt, 64)), dim3(64), 0, s, v->L.p + lo, v->W.p + lo, v->status.p + lo, v->part.p + lo, proofs, cnt, v->cap);
+    ZK_LAUNCH_OK("plonk verification");
+    launch_kzg_pair(v->verdict.p + lo, v->status.p + lo, v->L.p + lo, v->W.p + lo, v->tab.p, cnt, v->kc.k.p, s);
+}
 
 extern "C" {
 
@@ -237,7 +170,7 @@ int zk_plonk_verifier_info(zk_plonk_verifier *v, zk_plonk_verifier_plan *plan) {
             p.log_n = v->log_n;
             p.n_public = v->n_public;
             p.device_bytes = v->bytes();
-            p.chunk = chunk_in_effect();
+            p.chunk = plonk_verify_chunk_in_effect();
             p.last_launches = v->last_launches;
             p.last_chunks = v->last_chunks;
         });

@@ -712,7 +712,8 @@ class PlonkVerifier(_Object):
     """A verifier for one key, made from the key alone (zk_plonk_verifier): no Kzg and no .ptau.  verify() judges m proofs a
     call, each with its own verdict, and everything per proof (the checks, the Keccak transcript, the scalars, the nineteen
     products, the pairing) runs on the device.  ZKHIP_PLONK_VERIFY_CHUNK bounds the memory of a call and changes no
-    verdict."""
+    verdict.  verify_batch() gives the same verdicts from one pairing equation a group of proofs (a random combination with
+    scalars the library draws), several times faster when invalid proofs are rare."""
     _name, _destroy, _info, _plan = "PlonkVerifier", "zk_plonk_verifier_destroy", "zk_plonk_verifier_info", L.zk_plonk_verifier_plan
     _drop = ("size",)
 
@@ -766,6 +767,61 @@ class PlonkVerifier(_Object):
         L.check(L.load_library().zk_plonk_verifier_verify(h, L._ptr(a) if m else None, L._ptr(pb) if pb is not None and m else None, m,
                                                           L._ptr(verdict) if m else None))
         return verdict
+
+    @staticmethod
+    def _batch_scalars(scalars, m):
+        """-> m x 16 bytes little-endian (uint8 array), or None when the library is to draw them"""
+        if scalars is None:
+            return None
+        if isinstance(scalars, (bytes, bytearray, np.ndarray)):
+            sc = L._buf(scalars)
+            if sc.size != m * 16:
+                raise ValueError("scalars: %d bytes, %d scalars of 16 bytes expected" % (sc.size, m))
+            values = [int.from_bytes(sc[i * 16:(i + 1) * 16].tobytes(), "little") for i in range(m)]
+        else:
+            values = [int(x) for x in scalars]
+            if len(values) != m:
+                raise ValueError("scalars: %d values for %d proofs" % (len(values), m))
+            for i, x in enumerate(values):
+                if not 0 <= x < 1 << 128:
+                    raise ValueError("scalars[%d] is not below 2^128" % i)
+            sc = np.frombuffer(b"".join(x.to_bytes(16, "little") for x in values), dtype=np.uint8)
+        for i, x in enumerate(values):
+            if x == 0:
+                raise ValueError("scalars[%d] is zero" % i)
+        return sc
+
+    def verify_batch(self, proofs, publics=None, scalars=None):
+        """(numpy uint8 [m] verdicts, report dict): verify()'s verdicts by random combination (zk_plonk_verifier_verify_batch):
+        one equation a group of ZKHIP_PLONK_VERIFY_GROUP proofs, the proofs of a failing group one by one.  proofs and
+        publics as verify() takes them.  scalars is FOR TESTS ONLY (m ints below 2^128, none zero, or m x 16 bytes
+        little-endian); None: the library draws them.  Scalars a prover can predict are unsound.  report: group, groups,
+        groups_failed, proofs_rechecked, malformed, launches, chunks."""
+        a, pb, m = self._inputs(proofs, publics)
+        sc = self._batch_scalars(scalars, m)
+        h = self._handle()
+        verdict = np.full(m, 255, dtype=np.uint8)
+        rep = L.zk_plonk_batch_report()
+        rep.size = C.sizeof(rep)
+        L.check(L.load_library().zk_plonk_verifier_verify_batch(h, L._ptr(a) if m else None, L._ptr(pb) if pb is not None and m else None, m,
+                                                                L._ptr(sc) if sc is not None and m else None, L._ptr(verdict) if m else None, C.byref(rep)))
+        return verdict, {name: int(getattr(rep, name)) for name, _ in rep._fields_ if name != "size"}
+
+    def batch_sums(self, proofs, publics, scalars):
+        """list of (L, W), a pair of 64 bytes a group in the order the groups are formed (64 zero bytes each for a group with
+        no well-formed proof): the two sums of verify_batch()'s equation, no pairing run (zk_plonk_verifier_batch_sums).  For
+        tests; scalars must be given."""
+        a, pb, m = self._inputs(proofs, publics)
+        if scalars is None:
+            raise ValueError("scalars: %d values expected" % m)
+        sc = self._batch_scalars(scalars, m)
+        h = self._handle()
+        sums = np.zeros(max(m, 1) * 128, dtype=np.uint8)             # a group holds a proof at least
+        n = C.c_uint64(0)
+        L.check(L.load_library().zk_plonk_verifier_batch_sums(h, L._ptr(a) if m else None, L._ptr(pb) if pb is not None and m else None, m,
+                                                              L._ptr(sc) if m else None, L._ptr(sums), max(m, 1), C.byref(n)))
+        raw = sums.tobytes()
+        return [(raw[g * 128:g * 128 + 64], raw[g * 128 + 64:g * 128 + 128]) for g in range(n.value)]
 
     def challenges(self, proofs, publics=None):
         """(m lists of six ints beta gamma alpha zeta v u, numpy uint8 [m] status): the first kernel alone
