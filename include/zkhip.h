@@ -1304,6 +1304,83 @@ int zk_plonk_verifier_verify_batch(zk_plonk_verifier *v, const uint8_t *proofs, 
 int zk_plonk_verifier_batch_sums(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publics, uint64_t m, const uint8_t *scalars16, uint8_t *sums,
                                  uint64_t sums_cap, uint64_t *n_groups);
 
+/* A verifier over a KEY SET: proofs under many keys in one call, proof i under key key_of[i].  PLONK's setup is universal, so
+ * the keys of a service share one [tau]G2, and a group of proofs under any number of keys is still ONE equation
+ * e(L, G2) e(-W, [tau]G2) = 1.  The set keeps on its device one pair of line tables and the generator of G1 once, and per key a
+ * record of what the transcript needs and the eight commitments; from the first call on, the buffers of one chunk.
+ * zk_plonk_verifier_set_create COPIES the keys and borrows nothing.  n_keys is 1 to 65536 ("zk_plonk_verifier_set_create: n_keys
+ * 0 is outside 1 .. 65536"; "zk_plonk_verifier_set_create: key 2 is null"); a key may appear twice; keys may differ in log_n,
+ * n_public, k1, k2 and their commitments.  Every key is checked as zk_plonk_verifier_create checks it, with the same texts
+ * under this entry's name and the key's index, before a device is touched:
+ *   "zk_plonk_verifier_set_create: key 3: vk->size is not sizeof(zk_plonk_vkey)", "zk_plonk_verifier_set_create: key 3: log_n 2 is
+ *   outside 3 .. 25", "zk_plonk_verifier_set_create: key 3: n_public 9 exceeds n = 8", "zk_plonk_verifier_set_create: key 3: k1 is
+ *   not below r" (k2 alike), "zk_plonk_verifier_set_create: key 3: a commitment of the key is not a point of the curve";
+ * all keys must carry the same tau_g2 bytes, "zk_plonk_verifier_set_create: key 3's [tau]G2 is not key 0's"; and [tau]G2 is
+ * classified on the device once: "zk_plonk_verifier_set_create: the keys' [tau]G2 is not a point of the twist in the subgroup".
+ * Free HBM is checked before anything is allocated.  Calls on one set are serialised. */
+typedef struct zk_plonk_verifier_set zk_plonk_verifier_set;
+int zk_plonk_verifier_set_create(zk_plonk_verifier_set **out, const zk_plonk_vkey *const *vks, uint32_t n_keys, int32_t device);
+void zk_plonk_verifier_set_destroy(zk_plonk_verifier_set *set);
+/* Set plan->size = sizeof(zk_plonk_verifier_set_plan) before the call (only `size` bytes are written). */
+typedef struct zk_plonk_verifier_set_plan {
+    uint32_t size;
+    uint32_t n_keys;
+    uint64_t max_n_public;        /* the largest n_public of the set's keys */
+    uint64_t device_bytes;        /* HBM the set holds, the buffers of a chunk and of a batch call included once made */
+    uint64_t chunk;               /* ZKHIP_PLONK_VERIFY_CHUNK in effect */
+    uint32_t last_launches;       /* kernel launches of the last call on the set */
+    uint32_t last_chunks;         /* chunks of the last call with m > 0 */
+} zk_plonk_verifier_set_plan;
+int zk_plonk_verifier_set_info(zk_plonk_verifier_set *set, zk_plonk_verifier_set_plan *plan);
+/* verdict[i] = what zk_plonk_verifier_verify gives proof i under key key_of[i]: the same checks, equation and codes, so a proof
+ * under the wrong key of the same n_public is INVALID, not an error.  publics is RAGGED, as for zk_vkey_set_verify: proof i
+ * contributes n_public(key_of[i]) x 32 bytes, back to back in the proofs' order; publics_bytes must be their total and publics
+ * may be NULL when that is 0.  Found before any launch: "zk_plonk_verifier_set_verify: key_of[5] = 9, the set holds 4 keys" (the
+ * first such index), "zk_plonk_verifier_set_verify: publics_bytes: 640 expected (20 values of 32 bytes), 608 given",
+ * "zk_plonk_verifier_set_verify: m is not below 2^31", a null argument.  m = 0 is legal and does nothing.
+ * ZKHIP_PLONK_VERIFY_CHUNK keeps its meaning and its error.  Inside a chunk the proofs are ORDERED BY KEY, keys rising and a
+ * key's proofs in the caller's order, through an index array the kernels read (proofs and publics are uploaded as the caller
+ * holds them): the lanes of a wave then mostly share a key, and with it the transcript's loop over the publics and the base of
+ * a fixed term.  Verdicts return to the caller's positions.  Four launches a chunk, whatever n_keys is and however the proofs
+ * spread over the keys. */
+int zk_plonk_verifier_set_verify(zk_plonk_verifier_set *set, const uint8_t *proofs, const uint32_t *key_of, const uint8_t *publics, uint64_t publics_bytes, uint64_t m,
+                                 uint8_t *verdict);
+/* zk_plonk_verifier_verify_batch over the set: in the key-ordered chunk, consecutive proofs form groups of
+ * ZKHIP_PLONK_VERIFY_GROUP (the knob, default and error of that entry); there is NO limit on the keys of a group.  A SEGMENT is the
+ * proofs of one key inside one group; a key's run may straddle groups and chunks, a group never straddles a chunk.  Malformed
+ * proofs get MALFORMED and take no part in any sum.  With a scalar r_i per proof, over a group's well-formed proofs
+ *     S_G   = sum_i r_i s_i,G                                  (the generator's term, the whole group)
+ *     S_s,t = sum_(i in segment s) r_i s_it,  t < 8            (the eight commitments F_k(s),t of the segment's key)
+ *     L = S_G G + sum_s sum_(t < 8) S_s,t F_k(s),t + sum_i sum_(j < 9) (r_i s_i,9+j) P_ij,
+ *     W = sum_i r_i W_zeta,i + (r_i u_i) W_zeta_omega,i,
+ * and the group passes iff e(L, G2) e(-W, [tau]G2) = 1: a further key in a group costs eight more points of the bucket
+ * multiplication.  A passing group gives OK to its well-formed proofs; the well-formed proofs of all failing groups of a chunk
+ * go through the set's per-proof kernels from the status and scalars already on the device, before the chunk's verdicts
+ * leave.  So a valid proof always gets OK, and an invalid one gets OK with probability at most 1 / (2^128 - 1) a group, whatever
+ * keys the group holds.  scalars16 is FOR TESTS ONLY (m x 16 bytes, r_i of proof i in the caller's order); a zero scalar is
+ * an error, "zk_plonk_verifier_set_verify_batch: scalar 3 is zero"; NULL: the library draws them with getrandom() after the call
+ * has its inputs.  Scalars an adversary knows or can predict before fixing the proofs are unsound: two wrong proofs whose
+ * errors cancel under those scalars pass as a group and both get OK, AND THE TWO MAY STAND UNDER TWO DIFFERENT KEYS of one
+ * group, since the group is one equation.  Never pass constants, counters or a seeded generator.
+ * report (may be NULL; set report->size = sizeof first): groups and segments count those with at least one well-formed proof.
+ * The batch buffers and the keys' commitments in the bucket kernels' form are made by the set's first batch call, after the
+ * free HBM has been checked, and count in device_bytes. */
+typedef struct {
+    uint32_t size;              /* sizeof, set by the caller */
+    uint32_t group;             /* the group size the call used: min(the knob, the chunk's capacity) */
+    uint32_t launches, chunks;
+    uint64_t groups, groups_failed;
+    uint64_t segments;
+    uint64_t proofs_rechecked, malformed;
+} zk_plonk_set_batch_report;
+int zk_plonk_verifier_set_verify_batch(zk_plonk_verifier_set *set, const uint8_t *proofs, const uint32_t *key_of, const uint8_t *publics, uint64_t publics_bytes,
+                                       uint64_t m, const uint8_t *scalars16, uint8_t *verdict, zk_plonk_set_batch_report *report /* may be NULL */);
+/* FOR TESTS: sums[g] = L | W of group g (128 bytes, the file's form; 128 zero bytes for a group with no well-formed proof), in
+ * the order the groups are formed; n_groups = the number written.  No pairing is run.  scalars16 must be given;
+ * "zk_plonk_verifier_set_batch_sums: sums_cap 2 is below the call's 3 groups". */
+int zk_plonk_verifier_set_batch_sums(zk_plonk_verifier_set *set, const uint8_t *proofs, const uint32_t *key_of, const uint8_t *publics, uint64_t publics_bytes, uint64_t m,
+                                     const uint8_t *scalars16, uint8_t *sums, uint64_t sums_cap, uint64_t *n_groups);
+
 /* ---- PLONK from an R1CS ---------------------------------------------------------------------- */
 /* A circom .r1cs compiled on the device to what zk_plonk_prover_create takes: the five selectors, the three wire maps and the
  * permutation s1 s2 s3; the extension of a circom witness by the wires the compile introduces; and a prover made from the

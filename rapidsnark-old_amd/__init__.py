@@ -22,6 +22,6 @@ from .verify import VerificationKey, VerificationKeySet, pairing, pairing_last_p
 from .kzg import Kzg, fr_poly_divide                                  # noqa: F401
 from .frscan import fr_batch_inverse, fr_prefix_product, fr_grand_product, plonk_permutation_product      # noqa: F401
 from .plonk import PlonkCircuit, PlonkOpening, fr_coset_ntt, fr_poly_eval        # noqa: F401
-from .plonk import PlonkProver, PlonkProof, PlonkVKey, PlonkR1cs, PlonkVerifier, plonk_verify, keccak256        # noqa: F401
+from .plonk import PlonkProver, PlonkProof, PlonkVKey, PlonkR1cs, PlonkVerifier, PlonkVerifierSet, plonk_verify, keccak256        # noqa: F401
 from . import synth                                     # noqa: F401
 from .dist import gather_partials, ShardedChain                        # noqa: F401

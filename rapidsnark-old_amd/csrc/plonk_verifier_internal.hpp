@@ -11,6 +11,12 @@ inline uint64_t plonk_verify_chunk_in_effect() {
     return env_number("ZKHIP_PLONK_VERIFY_CHUNK", PLONK_VERIFY_DEFAULT_CHUNK, 1, PLONK_VERIFY_MAX_CHUNK, "a number of proofs from 1 to 2^20");
 }
 
+// ZKHIP_PLONK_VERIFY_GROUP, read at every batch call of an object or of a key set (plonkverify_set.hip)
+constexpr uint64_t PLONK_DEFAULT_GROUP = 65536, PLONK_MAX_GROUP = 1ull << 20;   // 65536: the lowest all-valid median at 65536 proofs (profiles/plonk_verify_batch_timing.txt)
+inline uint64_t plonk_verify_group_in_effect() {
+    return env_number("ZKHIP_PLONK_VERIFY_GROUP", PLONK_DEFAULT_GROUP, 1, PLONK_MAX_GROUP, "a number of proofs from 1 to 2^20");
+}
+
 // zk_plonk_verifier_verify_batch's own: made by the object's first batch call, re-made when the chunk's capacity or the
 // group changes.  Group g of a chunk has slots of `group` proofs whatever it holds: a short group's tail and a malformed
 // proof take zero scalars
@@ -123,3 +129,16 @@ void launch_transcript(zk_plonk_verifier *v, uint64_t cnt, bool want_scalars, hi
 // k_plonk_combine, k_plonk_sum and k_kzg_pair for proofs [lo, lo + cnt) of the chunk, from status and sc as the transcript
 // left them: v->verdict[lo, lo + cnt)
 void launch_per_proof(zk_plonk_verifier *v, uint64_t lo, uint64_t cnt, hipStream_t s);
+
+// plonkverify_batch.hip's pairing step over the buffers of its caller (the object's batch buffers, or a key set's,
+// plonkverify_set.hip): pass[q] = e(L, G2) e(-W, [tau]G2) = 1 for the groups at[q] of sums, L | W a group in the file's form.
+// p1, lines, skip: 2 PLONK_BATCH_SLICE entries (lines: times MILLER_LINES); p2: G2, [tau]G2 PLONK_BATCH_SLICE times; out:
+// PLONK_BATCH_SLICE Fq12; err: three words, all ones.  The stream is drained inside
+struct PlonkPairBufs {
+    G1Affine *p1;
+    const G2Affine *p2;
+    Line *lines;
+    uint8_t *skip, *out;
+    uint32_t *err;
+};
+void plonk_group_equations(const PlonkPairBufs &b, const PairConsts *k, std::vector<uint8_t> &pass, const uint8_t *sums, const std::vector<uint64_t> &at, hipStream_t s);

@@ -31,9 +31,6 @@
 
 namespace {
 
-constexpr uint64_t PLONK_DEFAULT_GROUP = 65536, PLONK_MAX_GROUP = 1ull << 20;   // 65536: the lowest all-valid median at 65536 proofs (profiles/plonk_verify_batch_timing.txt)
-uint64_t group_in_effect() { return env_number("ZKHIP_PLONK_VERIFY_GROUP", PLONK_DEFAULT_GROUP, 1, PLONK_MAX_GROUP, "a number of proofs from 1 to 2^20"); }
-
 constexpr uint32_t FOLD_WG = 256, FOLD_WAVES = FOLD_WG / 64;
 
 // ---------------------------------------------------------------- device
@@ -213,26 +210,9 @@ void chunk_sums(zk_plonk_verifier *v, const char *who, ChunkSums &c, uint64_t cn
     }
 }
 
-// pass[q] for the groups at[q] of the chunk: e(L, G2) e(-W, [tau]G2) = 1.  A pair with a point at infinity contributes 1
-// in k_pairing_coop (its `skip`), which is the value of that pairing, so L or W at infinity needs no path of its own
 void group_equations(zk_plonk_verifier *v, std::vector<uint8_t> &pass, const ChunkSums &c, const std::vector<uint64_t> &at, hipStream_t s) {
     PlonkBatchBufs &b = v->batch;
-    uint8_t one[sizeof(Fq12)] = {1};
-    std::vector<uint8_t> pairs(2 * PLONK_BATCH_SLICE * 64), out(PLONK_BATCH_SLICE * sizeof(Fq12));
-    pass.assign(at.size(), 0);
-    for (uint64_t lo = 0; lo < at.size(); lo += PLONK_BATCH_SLICE) {
-        const uint64_t n = at.size() - lo < PLONK_BATCH_SLICE ? at.size() - lo : PLONK_BATCH_SLICE;
-        for (uint64_t q = 0; q < n; q++) {
-            const uint8_t *lw = c.sums.data() + at[lo + q] * 128;
-            memcpy(pairs.data() + q * 128, lw, 64);
-            memcpy(pairs.data() + q * 128 + 64, Pt<Fq>(lw + 64).neg().b, 64);
-        }
-        HIP_TRY(hipMemcpyAsync(b.p1.p, pairs.data(), n * 128, hipMemcpyHostToDevice, s));
-        launch_pairing_coop(b.out.p, b.p1.p, b.p2.p, b.lines.p, b.skip.p, b.err.p, 2 * n, 2, COOP_FINAL, v->kc.k.p, s);
-        HIP_TRY(hipMemcpyAsync(out.data(), b.out.p, n * sizeof(Fq12), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        for (uint64_t q = 0; q < n; q++) pass[lo + q] = memcmp(out.data() + q * sizeof(Fq12), one, sizeof one) == 0;
-    }
+    plonk_group_equations(PlonkPairBufs{b.p1.p, b.p2.p, b.lines.p, b.skip.p, b.out.p, b.err.p}, v->kc.k.p, pass, c.sums.data(), at, s);
 }
 
 // what both entries check before a device is touched; false: m = 0
@@ -250,7 +230,7 @@ void verify_batch(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *pu
     const uint32_t rep_size = report_size(report);
     zk_plonk_batch_report rep;
     memset(&rep, 0, sizeof rep);
-    const uint64_t knob = group_in_effect();
+    const uint64_t knob = plonk_verify_group_in_effect();
     rep.size = rep_size;
     rep.group = (uint32_t)knob;
     auto leave = [&]() {
@@ -307,7 +287,7 @@ void batch_sums(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publ
                 uint64_t *n_groups) {
     if (!n_groups) throw std::invalid_argument("null argument");
     *n_groups = 0;
-    const uint64_t knob = group_in_effect();
+    const uint64_t knob = plonk_verify_group_in_effect();
     if (!batch_checks(v, WHO_SUMS, proofs, publics, m, scalars16, sums)) return;
     if (!scalars16) throw std::invalid_argument("null argument");
     const uint64_t want = pb_groups_of_call(m, plonk_verify_chunk_in_effect(), knob);
@@ -326,6 +306,28 @@ void batch_sums(zk_plonk_verifier *v, const uint8_t *proofs, const uint8_t *publ
 }
 
 }   // namespace
+
+// ---------------------------------------------------------------- what plonkverify_set.hip runs too (plonk_verifier_internal.hpp)
+// pass[q] for the groups at[q] of sums (L | W a group): e(L, G2) e(-W, [tau]G2) = 1.  A pair with a point at infinity contributes 1
+// in k_pairing_coop (its `skip`), which is the value of that pairing, so L or W at infinity needs no path of its own
+void plonk_group_equations(const PlonkPairBufs &b, const PairConsts *k, std::vector<uint8_t> &pass, const uint8_t *sums, const std::vector<uint64_t> &at, hipStream_t s) {
+    uint8_t one[sizeof(Fq12)] = {1};
+    std::vector<uint8_t> pairs(2 * PLONK_BATCH_SLICE * 64), out(PLONK_BATCH_SLICE * sizeof(Fq12));
+    pass.assign(at.size(), 0);
+    for (uint64_t lo = 0; lo < at.size(); lo += PLONK_BATCH_SLICE) {
+        const uint64_t n = at.size() - lo < PLONK_BATCH_SLICE ? at.size() - lo : PLONK_BATCH_SLICE;
+        for (uint64_t q = 0; q < n; q++) {
+            const uint8_t *lw = sums + at[lo + q] * 128;
+            memcpy(pairs.data() + q * 128, lw, 64);
+            memcpy(pairs.data() + q * 128 + 64, Pt<Fq>(lw + 64).neg().b, 64);
+        }
+        HIP_TRY(hipMemcpyAsync(b.p1, pairs.data(), n * 128, hipMemcpyHostToDevice, s));
+        launch_pairing_coop(b.out, b.p1, b.p2, b.lines, b.skip, b.err, 2 * n, 2, COOP_FINAL, k, s);
+        HIP_TRY(hipMemcpyAsync(out.data(), b.out, n * sizeof(Fq12), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint64_t q = 0; q < n; q++) pass[lo + q] = memcmp(out.data() + q * sizeof(Fq12), one, sizeof one) == 0;
+    }
+}
 
 extern "C" {
 

@@ -209,6 +209,16 @@ class zk_plonk_batch_report(C.Structure):
                 ("malformed", C.c_uint64), ("launches", C.c_uint32), ("chunks", C.c_uint32)]
 
 
+class zk_plonk_verifier_set_plan(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("n_keys", C.c_uint32), ("max_n_public", C.c_uint64), ("device_bytes", C.c_uint64), ("chunk", C.c_uint64),
+                ("last_launches", C.c_uint32), ("last_chunks", C.c_uint32)]
+
+
+class zk_plonk_set_batch_report(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("group", C.c_uint32), ("launches", C.c_uint32), ("chunks", C.c_uint32), ("groups", C.c_uint64),
+                ("groups_failed", C.c_uint64), ("segments", C.c_uint64), ("proofs_rechecked", C.c_uint64), ("malformed", C.c_uint64)]
+
+
 class zk_plonk_r1cs_plan(C.Structure):
     _fields_ = [("size", C.c_uint32), ("log_n", C.c_uint32), ("rows", C.c_uint64), ("n_public", C.c_uint64), ("n_wires", C.c_uint64),
                 ("n_additions", C.c_uint64), ("n_witness", C.c_uint64), ("terms", C.c_uint64), ("device_bytes", C.c_uint64), ("seg", C.c_uint32),
@@ -279,7 +289,9 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_plonk_r1cs_create", "zk_plonk_r1cs_destroy", "zk_plonk_r1cs_info", "zk_plonk_r1cs_circuit", "zk_plonk_r1cs_extend",
            "zk_plonk_prover_create_r1cs", "zk_plonk_prove_r1cs",
            "zk_plonk_verifier_create", "zk_plonk_verifier_destroy", "zk_plonk_verifier_info", "zk_plonk_verifier_verify", "zk_plonk_verifier_challenges",
-           "zk_plonk_verifier_verify_batch", "zk_plonk_verifier_batch_sums"]
+           "zk_plonk_verifier_verify_batch", "zk_plonk_verifier_batch_sums",
+           "zk_plonk_verifier_set_create", "zk_plonk_verifier_set_destroy", "zk_plonk_verifier_set_info", "zk_plonk_verifier_set_verify",
+           "zk_plonk_verifier_set_verify_batch", "zk_plonk_verifier_set_batch_sums"]
 ZK_SCAN_EXCLUSIVE = 1
 ZK_KZG_MONOMIAL, ZK_KZG_LAGRANGE, ZK_KZG_NO_LAGRANGE = 0, 1, 0xffffffff
 ZK_SCALE_PLAN_MAX = 130
@@ -487,6 +499,16 @@ def load_library():
     if hasattr(lib, "zk_plonk_verifier_verify_batch"):
         lib.zk_plonk_verifier_verify_batch.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p, u8p, C.POINTER(zk_plonk_batch_report)]
         lib.zk_plonk_verifier_batch_sums.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64, u8p, u8p, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "zk_plonk_verifier_set_create"):
+        lib.zk_plonk_verifier_set_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.POINTER(zk_plonk_vkey)), C.c_uint32, C.c_int32]
+        lib.zk_plonk_verifier_set_destroy.argtypes = [C.c_void_p]
+        lib.zk_plonk_verifier_set_destroy.restype = None
+        lib.zk_plonk_verifier_set_info.argtypes = [C.c_void_p, C.POINTER(zk_plonk_verifier_set_plan)]
+        lib.zk_plonk_verifier_set_verify.argtypes = [C.c_void_p, u8p, C.c_void_p, u8p, C.c_uint64, C.c_uint64, u8p]
+        lib.zk_plonk_verifier_set_verify_batch.argtypes = [C.c_void_p, u8p, C.c_void_p, u8p, C.c_uint64, C.c_uint64, u8p, u8p,
+                                                           C.POINTER(zk_plonk_set_batch_report)]
+        lib.zk_plonk_verifier_set_batch_sums.argtypes = [C.c_void_p, u8p, C.c_void_p, u8p, C.c_uint64, C.c_uint64, u8p, u8p, C.c_uint64,
+                                                         C.POINTER(C.c_uint64)]
     _LIB = lib
     return lib
 

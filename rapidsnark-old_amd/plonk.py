@@ -840,3 +840,113 @@ class PlonkVerifier(_Object):
         """zk_plonk_verifier_info -> dict: log_n, n_public, device_bytes, chunk (ZKHIP_PLONK_VERIFY_CHUNK in effect),
         last_launches, last_chunks"""
         return self._plan_dict()[1]
+
+
+class PlonkVerifierSet(_Object):
+    """A verifier over a key set (zk_plonk_verifier_set): proofs under many keys that share one [tau]G2, proof i under key
+    key_of[i], in one call.  The set copies the keys; on its device it keeps one pair of line tables and the generator once,
+    and a record and the eight commitments a key.  verify() gives every proof the verdict PlonkVerifier(vkeys[key_of[i]])
+    gives it, four launches a chunk whatever the keys; verify_batch() the same verdicts from one pairing equation a group of
+    proofs, whatever keys the group holds."""
+    _name, _destroy, _info, _plan = "PlonkVerifierSet", "zk_plonk_verifier_set_destroy", "zk_plonk_verifier_set_info", L.zk_plonk_verifier_set_plan
+    _drop = ("size",)
+
+    def __init__(self, vkeys, device=-1):
+        vkeys = list(vkeys)
+        for i, vk in enumerate(vkeys):
+            if not isinstance(vk, PlonkVKey):
+                raise TypeError("vkeys[%d]: a PlonkVKey expected (PlonkProver.vkey(), PlonkVKey.from_json or PlonkVKey.from_parts)" % i)
+        if not 1 <= len(vkeys) <= 65536:
+            raise ValueError("vkeys: %d keys, 1 to 65536 expected" % len(vkeys))
+        self._h = C.c_void_p()
+        self.vkeys, self.n_public, self.device = vkeys, [vk.n_public for vk in vkeys], int(device)
+        ptrs = (C.POINTER(L.zk_plonk_vkey) * len(vkeys))(*[C.pointer(vk._c) for vk in vkeys])
+        L.check(L.load_library().zk_plonk_verifier_set_create(C.byref(self._h), ptrs, len(vkeys), device))
+
+    def _inputs(self, proofs, key_of, publics):
+        """-> (proof bytes, key_of as uint32, the ragged public bytes, m): every shape is checked here, before any call"""
+        if isinstance(proofs, np.ndarray):
+            if proofs.dtype != np.uint8 or proofs.ndim != 2 or proofs.shape[1] != PROOF_BYTES:
+                raise ValueError("proofs: a uint8 array of m rows of %d bytes expected" % PROOF_BYTES)
+            a = np.ascontiguousarray(proofs).reshape(-1)
+        else:
+            rows = [p.to_bytes() if isinstance(p, PlonkProof) else PlonkProof(p).to_bytes() for p in proofs]
+            a = np.frombuffer(b"".join(rows), dtype=np.uint8)
+        m = a.size // PROOF_BYTES
+        keys = np.asarray(key_of if isinstance(key_of, np.ndarray) else [int(k) for k in key_of], dtype=np.int64).reshape(-1)
+        if keys.size != m:
+            raise ValueError("key_of: %d entries for %d proofs" % (keys.size, m))
+        out = np.nonzero((keys < 0) | (keys >= len(self.n_public)))[0]
+        if out.size:
+            raise ValueError("key_of[%d] = %d, the set holds %d keys" % (out[0], keys[out[0]], len(self.n_public)))
+        widths = np.asarray(self.n_public, dtype=np.int64)[keys]
+        total = int(widths.sum()) * 32
+        if publics is None:
+            if total:
+                raise ValueError("publics: %d rows expected, proof i's of n_public(key_of[i]) values" % m)
+            pb = np.zeros(0, dtype=np.uint8)
+        elif isinstance(publics, (bytes, bytearray)) or (isinstance(publics, np.ndarray) and publics.dtype == np.uint8):
+            pb = L._buf(publics)
+            if pb.size != total:
+                raise ValueError("publics: %d bytes, %d expected (%d values of 32 bytes)" % (pb.size, total, total // 32))
+        else:
+            publics = list(publics)
+            if len(publics) != m:
+                raise ValueError("publics: %d rows for %d proofs" % (len(publics), m))
+            rows = []
+            for i, row in enumerate(publics):
+                # values that are not below r are the library's to call MALFORMED: they must only fit 32 bytes
+                r = _scalars(row, "publics[%d]" % i, below_r=False)
+                if r.size != widths[i] * 32:
+                    raise ValueError("publics[%d]: %d values, n_public = %d expected for key %d" % (i, r.size // 32, widths[i], keys[i]))
+                rows.append(r)
+            pb = np.concatenate(rows) if rows else np.zeros(0, dtype=np.uint8)
+        return a, keys.astype(np.uint32), np.ascontiguousarray(pb, dtype=np.uint8), m
+
+    def verify(self, proofs, key_of, publics=None):
+        """numpy uint8 [m]: what PlonkVerifier(vkeys[key_of[i]]).verify gives proof i (zk_plonk_verifier_set_verify).  proofs: as
+        PlonkVerifier.verify takes them; key_of: m indices into the set; publics: m rows, row i of n_public(key_of[i]) ints
+        (empty for a key without public inputs), or the flat ragged bytes; None when no proof has public inputs."""
+        a, ko, pb, m = self._inputs(proofs, key_of, publics)
+        h = self._handle()
+        verdict = np.full(m, 255, dtype=np.uint8)
+        L.check(L.load_library().zk_plonk_verifier_set_verify(h, L._ptr(a) if m else None, L._ptr(ko) if m else None, L._ptr(pb) if pb.size else None, pb.size, m,
+                                                              L._ptr(verdict) if m else None))
+        return verdict
+
+    def verify_batch(self, proofs, key_of, publics=None, scalars=None):
+        """(numpy uint8 [m] verdicts, report dict): verify()'s verdicts by random combination
+        (zk_plonk_verifier_set_verify_batch): one equation a group of ZKHIP_PLONK_VERIFY_GROUP proofs of the key-ordered chunk,
+        the proofs of a failing group one by one.  scalars is FOR TESTS ONLY, as PlonkVerifier.verify_batch's, in the caller's
+        order; None: the library draws them.  Scalars a prover can predict are unsound, across keys too.  report: group,
+        launches, chunks, groups, groups_failed, segments, proofs_rechecked, malformed."""
+        a, ko, pb, m = self._inputs(proofs, key_of, publics)
+        sc = PlonkVerifier._batch_scalars(scalars, m)
+        h = self._handle()
+        verdict = np.full(m, 255, dtype=np.uint8)
+        rep = L.zk_plonk_set_batch_report()
+        rep.size = C.sizeof(rep)
+        L.check(L.load_library().zk_plonk_verifier_set_verify_batch(h, L._ptr(a) if m else None, L._ptr(ko) if m else None, L._ptr(pb) if pb.size else None, pb.size,
+                                                                    m, L._ptr(sc) if sc is not None and m else None, L._ptr(verdict) if m else None, C.byref(rep)))
+        return verdict, {name: int(getattr(rep, name)) for name, _ in rep._fields_ if name != "size"}
+
+    def batch_sums(self, proofs, key_of, publics, scalars):
+        """list of (L, W), a pair of 64 bytes a group in the order the groups are formed (64 zero bytes each for a group with
+        no well-formed proof): the two sums of verify_batch()'s equation, no pairing run (zk_plonk_verifier_set_batch_sums).
+        For tests; scalars must be given."""
+        a, ko, pb, m = self._inputs(proofs, key_of, publics)
+        if scalars is None:
+            raise ValueError("scalars: %d values expected" % m)
+        sc = PlonkVerifier._batch_scalars(scalars, m)
+        h = self._handle()
+        sums = np.zeros(max(m, 1) * 128, dtype=np.uint8)             # a group holds a proof at least
+        n = C.c_uint64(0)
+        L.check(L.load_library().zk_plonk_verifier_set_batch_sums(h, L._ptr(a) if m else None, L._ptr(ko) if m else None, L._ptr(pb) if pb.size else None, pb.size, m,
+                                                                  L._ptr(sc) if m else None, L._ptr(sums), max(m, 1), C.byref(n)))
+        raw = sums.tobytes()
+        return [(raw[g * 128:g * 128 + 64], raw[g * 128 + 64:g * 128 + 128]) for g in range(n.value)]
+
+    def info(self):
+        """zk_plonk_verifier_set_info -> dict: n_keys, max_n_public, device_bytes, chunk (ZKHIP_PLONK_VERIFY_CHUNK in effect),
+        last_launches, last_chunks"""
+        return self._plan_dict()[1]
