@@ -1193,6 +1193,69 @@ int zk_plonk_prover_info(zk_plonk_prover *p, zk_plonk_prover_plan *plan);
  * "zk_plonk_prove: a denominator of the permutation product is zero" (probability about 3n / r over beta, gamma). */
 int zk_plonk_prove(zk_plonk_prover *p, uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *witness, const uint8_t *publics, const uint8_t *blind);
 
+/* MANY WITNESSES A CALL.  m witnesses of the prover's circuit give m proofs, proof i byte for byte what zk_plonk_prove gives
+ * witness i with blinds i.  The proofs of a CHUNK of B advance through the five rounds in lock-step and every round's
+ * commitments for the whole chunk are ONE multiplication: four multiplications a chunk whatever it holds, against nine a proof.
+ * B is ZKHIP_PLONK_PROVE_BATCH, 1 .. ZK_PLONK_MANY_MAX_BATCH ("ZKHIP_PLONK_PROVE_BATCH: a number of proofs from 1 to 64
+ * expected" is an error of the call before any work); unset, the default for the circuit's size, which DESIGN.md section 36
+ * states with its measurement.  m proofs take ceil(m / B) chunks.  With B = 1 the call is a loop of zk_plonk_prove's own five
+ * rounds and keeps nothing more on the device.
+ * Layout: proofs m x ZK_PLONK_PROOF_BYTES; status m words; witnesses m x n_witness scalars back to back; publics m x n_public
+ * scalars back to back (NULL with n_public = 0); blinds NULL (drawn from the OS generator and wiped from the host and the
+ * device when the call leaves) or m x ZK_PLONK_BLINDS scalars, FOR TESTS as zk_plonk_prove's.  m = 0 is accepted and touches
+ * no device.
+ * A proof that cannot be made does not take the others with it: status[i] is ZK_PLONK_MANY_MADE or why proof i was refused,
+ * the 768 bytes of a refused proof are left untouched, its vectors are zeros in every later multiplication of its chunk, and
+ * the call still returns 0.  zk_last_error() then holds the refusal of the LOWEST refused index with that index:
+ *   "zk_plonk_prove_many: proof 3: the copy constraints do not hold", "zk_plonk_prove_many: proof 3: witness 5 is not below r"
+ *   (publics, blind alike).
+ * The entry returns non-zero only for errors of the call: "null argument", a bad knob, out of memory, "zk_plonk_prove_many: m is
+ * not below 2^31", and a chunk width the multiplication cannot take, checked before anything is allocated and naming the
+ * width that would fit:
+ *   "zk_plonk_prove_many: a chunk of 64 proofs is too large: 3 x 64 x 1048582 scalars x 13 windows = 2617260672 >= 2^31 table
+ *   rows; ZKHIP_PLONK_PROVE_BATCH=52 would fit" (>= 2^32 sort entries alike),
+ *   "zk_plonk_prove_many: out of memory (a chunk of 16 proofs needs 301234 MiB of HBM, 250000 MiB free);
+ *   ZKHIP_PLONK_PROVE_BATCH=12 would fit".
+ * On the device the first call with B > 1 makes, and the object keeps: a table with a row per window over the kzg's first
+ * n + 6 points (the kzg's mutex is held only while its points are copied), B slots (a proof's witness, publics, blinds, wire
+ * values, z, PI, t and its nine committed rows of n + 6) and the multiplication's buffers for 3 B vectors.  A call with another
+ * B makes them again.  The call holds the object's mutex throughout and does not use the kzg's multiplication. */
+#define ZK_PLONK_MANY_MAX_BATCH 64
+#define ZK_PLONK_MANY_MADE 0
+#define ZK_PLONK_MANY_ZERO_DENOMINATOR 1   /* a denominator of the permutation product is zero */
+#define ZK_PLONK_MANY_COPIES 2             /* the copy constraints do not hold */
+#define ZK_PLONK_MANY_GATES 3              /* the witness does not satisfy the gates (t's length, or r(zeta) != 0) */
+#define ZK_PLONK_MANY_NOT_BELOW_R 4        /* a value of the witness, the publics or the blinds is not below r */
+int zk_plonk_prove_many(zk_plonk_prover *p, uint64_t m, uint8_t *proofs, uint32_t *status, const uint8_t *witnesses, const uint8_t *publics,
+                        const uint8_t *blinds);
+/* The same from m circom witnesses of nVars = nWires values each, back to back: each is checked as zk_plonk_prove_r1cs checks
+ * its one and extended on its slot; its publics are its values 1 .. n_public.  "witness has 5 values, the r1cs 7 wires" and
+ * "zk_plonk_prove_r1cs_many: the prover was not made from an r1cs (zk_plonk_prover_create_r1cs)" are errors of the call. */
+int zk_plonk_prove_r1cs_many(zk_plonk_prover *p, uint64_t m, uint8_t *proofs, uint32_t *status, const uint8_t *wtns, uint32_t nVars, const uint8_t *blinds);
+/* The multiplication's own entry: k >= 1 polynomials of n + 6 coefficients each, back to back (shorter ones padded with
+ * zeros), give k commitments, out k x 64 bytes in the .ptau encoding, each what zk_kzg_commit gives.  3 B vectors a
+ * multiplication, B as above (the table and the buffers are made for B = 1 too).  A polynomial of zeros gives infinity.
+ * "zk_plonk_prover_commit_many: vector 2 coefficient 5 is not below r", "zk_plonk_prover_commit_many: k is 0". */
+int zk_plonk_prover_commit_many(zk_plonk_prover *p, uint8_t *out, const uint8_t *coeffs, uint64_t k);
+/* Set plan->size = sizeof(zk_plonk_prover_many_plan) before the call (only `size` bytes are written). */
+typedef struct zk_plonk_prover_many_plan {
+    uint32_t size;
+    uint32_t batch;               /* B in effect for the next call */
+    uint32_t table_batch;         /* the B the table, the slots and the buffers were made for; 0: not made */
+    uint32_t window_bits;         /* of the table: what make_msm_plan chooses for a batch of 3 B vectors of n + 6 */
+    uint32_t table_rows;          /* rows of n + 6 points, one a window */
+    uint32_t reserved;
+    uint64_t table_bytes, slot_bytes, msm_bytes;   /* HBM of the table, the slots, the multiplication's buffers */
+    uint32_t last_chunks;         /* of the last zk_plonk_prove_many, _r1cs_many or _commit_many on the object */
+    uint32_t last_multiplications;   /* 4 a chunk with B > 1; 9 a proof made with B = 1 */
+    uint32_t last_launches;       /* kernel launches, a difference of the process-wide counter as every last_launches */
+    uint32_t last_drains;         /* times the host waited for the stream: 4 a chunk and, a proof, the looped cores' (the scan, t's
+                                   * length, the six values, F(zeta)) */
+    uint32_t last_refused;        /* proofs of the call whose status is not 0 */
+    uint32_t reserved2;
+} zk_plonk_prover_many_plan;
+int zk_plonk_prover_many_info(zk_plonk_prover *p, zk_plonk_prover_many_plan *plan);
+
 /* *verdict = ZK_VERIFY_OK / ZK_VERIFY_INVALID / ZK_VERIFY_MALFORMED for one proof under vk with n_public = vk->n_public
  * publics.  MALFORMED: a point of the proof that is not on the curve (or a coordinate not below q), or one of the six values
  * or a public input not below r.  Otherwise the transcript is recomputed, u included, and with

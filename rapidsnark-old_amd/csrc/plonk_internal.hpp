@@ -106,6 +106,11 @@ void plonk_opening_clear(zk_plonk_opening *o, hipStream_t s);    // zeros in eve
 void plonk_opening_evaluate_dev(zk_plonk_opening *o, uint8_t evals[6 * 32], const uint64_t len[4], const Fr &zeta, hipStream_t s);
 void plonk_opening_open_dev(zk_plonk_opening *o, uint8_t w_zeta[64], uint8_t w_zeta_omega[64], uint8_t r_zeta[32], uint8_t *f, uint64_t *f_len,
                             const uint64_t tlen[3], const Fr &pi_zeta, const Fr &alpha, const Fr &beta, const Fr &gamma, const Fr &v, hipStream_t s);
+// The same without the two multiplications, for a prover that multiplies many proofs' quotients at once: the quotients are
+// divided straight into the caller's rows (on the object's device, as many rows each as the polynomial divided: its
+// quotient and, zeroed here, the one row above it).  The stream is drained once inside, for F(zeta)
+void plonk_opening_open_rows_dev(zk_plonk_opening *o, Fr *q_zeta, Fr *q_zeta_omega, uint8_t r_zeta[32], const uint64_t tlen[3], const Fr &pi_zeta,
+                                 const Fr &alpha, const Fr &beta, const Fr &gamma, const Fr &v, hipStream_t s);
 
 // ---------------------------------------------------------------- plonkr1cs.hip
 struct zk_plonk_r1cs;

@@ -363,7 +363,8 @@ LinConsts lin_consts(const zk_plonk_opening &o, Fr pi_zeta, Fr alpha, Fr beta, F
 // Round 5 over the parts of t already in o->tp, tlen[] rows each, and the pending evaluation's rows and values (the caller
 // has consumed `pending`): the linearisation, the two divisions and the two multiplications.  Held as evaluate_dev
 void open_dev(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uint8_t *r_zeta, uint8_t *f, uint64_t *f_len, const uint64_t tlen[T_VECS],
-              const Fr &pz, const Fr &al, const Fr &be, const Fr &ga, const Fr &vv, uint32_t seg, uint32_t dseg, hipStream_t s, bool pad = false) {
+              const Fr &pz, const Fr &al, const Fr &be, const Fr &ga, const Fr &vv, uint32_t seg, uint32_t dseg, hipStream_t s, bool pad = false,
+              Fr *const *qrows = nullptr) {
     zk_kzg *k = o->kzg;
     const uint64_t n = o->n, cap = o->cap;
     Fr E;
@@ -393,9 +394,14 @@ void open_dev(zk_plonk_opening *o, uint8_t *w_zeta, uint8_t *w_zeta_omega, uint8
     const Fr at[2] = {o->zeta, zw};
     uint8_t *out[2] = {w_zeta, w_zeta_omega};
     for (int j = 0; j < 2; j++) {
-        launch_divide(o->quot.p, o->yv.p + j, src[j], cnt[j], at[j], dseg, o->div, s);
+        launch_divide(qrows ? qrows[j] : o->quot.p, o->yv.p + j, src[j], cnt[j], at[j], dseg, o->div, s);
         if (j == 0) HIP_TRY(hipMemcpyAsync(&fz, o->yv.p, sizeof fz, hipMemcpyDeviceToHost, s));
-        if (cnt[j] > 1) {
+        if (qrows) {
+            // the caller's rows (a prover that multiplies many proofs' quotients at once): the quotient stays where it was
+            // divided to, the one row above it zeroed as `pad` zeroes it, and nothing is multiplied here
+            HIP_TRY(hipMemsetAsync(qrows[j] + (cnt[j] - 1), 0, sizeof(Fr), s));
+            if (j == 1) HIP_TRY(hipStreamSynchronize(s));       // F(zeta) is on the host
+        } else if (cnt[j] > 1) {
             std::lock_guard<std::mutex> kl(k->mu);     // the kzg's points and the work buffers of its multiplication
             // pad (the chained prover's): the multiplication runs over one row more than the quotient has, zeroed here after the
             // division (stream order), so that it has the size of the prover's seven others and the kzg's buffers are not made
@@ -457,6 +463,13 @@ void plonk_opening_open_dev(zk_plonk_opening *o, uint8_t w_zeta[64], uint8_t w_z
     if (!o->pending) throw std::invalid_argument("zk_plonk_open: no evaluation is pending: call zk_plonk_evaluate first");
     o->pending = false;
     open_dev(o, w_zeta, w_zeta_omega, r_zeta, f, f_len, tlen, pi_zeta, alpha, beta, gamma, v, seg_in_effect(), kzg_seg_in_effect(), s, /*pad=*/true);
+}
+void plonk_opening_open_rows_dev(zk_plonk_opening *o, Fr *q_zeta, Fr *q_zeta_omega, uint8_t r_zeta[32], const uint64_t tlen[3], const Fr &pi_zeta,
+                                 const Fr &alpha, const Fr &beta, const Fr &gamma, const Fr &v, hipStream_t s) {
+    if (!o->pending) throw std::invalid_argument("zk_plonk_open: no evaluation is pending: call zk_plonk_evaluate first");
+    o->pending = false;
+    Fr *const qrows[2] = {q_zeta, q_zeta_omega};
+    open_dev(o, nullptr, nullptr, r_zeta, nullptr, nullptr, tlen, pi_zeta, alpha, beta, gamma, v, seg_in_effect(), kzg_seg_in_effect(), s, /*pad=*/true, qrows);
 }
 
 extern "C" {

@@ -19,15 +19,14 @@
 // Which element goes where depends on indices only: no byte depends on seg or on scheduling.  No LDS, no atomics.
 #include <sys/random.h>
 
-#include "plonk_internal.hpp"
-#include "plonk_transcript.hpp"
+#include "plonk_prover_internal.hpp"
 
 namespace {
 
 constexpr uint32_t PV_WG = 256;
 constexpr uint32_t MIN_LOG_N = 3;
 constexpr uint32_t CIRC_VECS = PLONK_CIRC_VECS, POINTS = PLONK_POINTS, BLINDS = ZK_PLONK_BLINDS;
-constexpr uint32_t ROUNDS = 5;
+constexpr uint32_t ROUNDS = PLONK_ROUNDS;
 enum { C_QL, C_QR, C_QM, C_QO, C_QC, C_S1, C_S2, C_S3 };           // the view's order
 
 // ---------------------------------------------------------------- device
@@ -105,35 +104,7 @@ uint32_t blocks_of(uint64_t n, uint32_t seg) { return nblocks(n, PV_WG * seg); }
 
 }   // namespace
 
-// ---------------------------------------------------------------- the object
-struct zk_plonk_prover {
-    zk_kzg *kzg = nullptr;                            // borrowed: it outlives the object
-    zk_plonk_r1cs *r1cs = nullptr;                    // borrowed too: the compiled circuit of a prover made by zk_plonk_prover_create_r1cs
-    int device = 0;
-    uint32_t log_n = 0;
-    uint64_t n = 0, cap = 0, n_witness = 0, n_public = 0;
-    std::mutex mu;                                    // calls on one object are serialised
-    std::unique_ptr<Stream> st;
-    zk_plonk_circuit *circ = nullptr;                 // round 3's extensions and work vectors: owned
-    zk_plonk_opening *open = nullptr;                 // rounds 4 and 5's coefficients and a proof's rows: owned
-    PlonkPerm *perm = nullptr;                        // round 2's work buffers: owned
-    DevBuf<uint32_t> maps;                            // 3 x n
-    DevBuf<Fr> sig, shifts;                           // s1 .. s3 by values, 3 x n; 1, k1, k2
-    DevBuf<Fr> wit, pub, blind;                       // a call's witness, publics and blinds
-    DevBuf<Fr> vals;                                  // 4 x n: a, b, c and PI by values
-    DevBuf<Fr> zval, pic;                             // z by values; PI by coefficients
-    zk_plonk_vkey vk;
-    uint32_t last_launches = 0, round_launches[ROUNDS] = {0, 0, 0, 0, 0};
-    size_t own_bytes() const {
-        return maps.bytes() + sig.bytes() + shifts.bytes() + wit.bytes() + pub.bytes() + blind.bytes() + vals.bytes() + zval.bytes() + pic.bytes();
-    }
-    ~zk_plonk_prover() {
-        if (perm) plonk_perm_free(perm);
-        if (open) zk_plonk_opening_destroy(open);
-        if (circ) zk_plonk_circuit_destroy(circ);
-    }
-};
-
+// ---------------------------------------------------------------- the object: plonk_prover_internal.hpp
 namespace {
 
 uint64_t own_need_bytes(uint64_t n, uint64_t n_witness, uint64_t n_public) {
@@ -274,8 +245,8 @@ void plonk_prove_core(zk_plonk_prover *p, const char *who, uint8_t *proof, const
     fr_to_std(beta, ch.beta);
     fr_to_std(gamma, ch.gamma);
     if (!plonk_perm_dev(p->perm, p->zval.p, last, p->vals.p, p->sig.p, p->shifts.p, log_n, beta, gamma, s))
-        throw std::invalid_argument(std::string(who) + ": a denominator of the permutation product is zero");
-    if (!(fr_from_std(last) == Fr::one())) throw std::invalid_argument(std::string(who) + ": the copy constraints do not hold");
+        throw PlonkRefusal(PM_ZERO_DENOMINATOR, std::string(who) + ": a denominator of the permutation product is zero");
+    if (!(fr_from_std(last) == Fr::one())) throw PlonkRefusal(PM_COPIES, std::string(who) + ": the copy constraints do not hold");
     Fr *const out2[1] = {rows[3]};
     plonk_circuit_interpolate_dev(p->circ, out2, p->zval.p, 1, s);
     BlindArgs BZ{{rows[3], nullptr, nullptr}, {6, 0, 0}, p->blind.p, n, 3};
@@ -295,7 +266,7 @@ void plonk_prove_core(zk_plonk_prover *p, const char *who, uint8_t *proof, const
     }
     uint64_t t_len = 0;
     const Fr *t = plonk_circuit_quotient_dev(p->circ, lens, vecs + 1, ch.alpha, ch.beta, ch.gamma, &t_len, s);
-    if (t_len > 3 * n + 6) throw std::invalid_argument(std::string(who) + ": the witness does not satisfy the gates");
+    if (t_len > 3 * n + 6) throw PlonkRefusal(PM_GATES, std::string(who) + ": the witness does not satisfy the gates");
     Fr *parts[3] = {plonk_opening_part(p->open, 0), plonk_opening_part(p->open, 1), plonk_opening_part(p->open, 2)};
     SplitArgs S{t, parts[0], parts[1], parts[2], p->blind.p + 9, n, seg};
     ZK_LAUNCH(k_plonk_split, dim3(blocks_of(n + 6, seg)), dim3(PV_WG), 0, s, S);
@@ -316,7 +287,7 @@ void plonk_prove_core(zk_plonk_prover *p, const char *who, uint8_t *proof, const
     uint8_t r_zeta[32];
     static const uint8_t zero[32] = {0};
     plonk_opening_open_dev(p->open, pts + P_WZ * 64, pts + P_WZW * 64, r_zeta, nullptr, nullptr, tlen, z.pi, ch.alpha, ch.beta, ch.gamma, ch.v, s);
-    if (memcmp(r_zeta, zero, 32) != 0) throw std::invalid_argument(std::string(who) + ": the witness does not satisfy the gates");
+    if (memcmp(r_zeta, zero, 32) != 0) throw PlonkRefusal(PM_GATES, std::string(who) + ": the witness does not satisfy the gates");
     end_round(4);
     HIP_TRY(hipMemsetAsync(p->blind.p, 0, p->blind.bytes(), s));      // and from the device: the next call uploads its own
     HIP_TRY(hipStreamSynchronize(s));
@@ -374,6 +345,10 @@ zk_plonk_prover *prover_create_r1cs(zk_kzg *kzg, zk_plonk_r1cs *c, const uint8_t
 
 }   // namespace
 
+void plonk_prover_core(zk_plonk_prover *p, const char *who, uint8_t *proof, const uint8_t *publics, uint32_t seg, uint64_t first) {
+    plonk_prove_core(p, who, proof, publics, seg, first);
+}
+
 extern "C" {
 
 int zk_plonk_prover_create(zk_plonk_prover **out, zk_kzg *kzg, const zk_plonk_circuit_view *view, const uint32_t *a_map, const uint32_t *b_map,
@@ -403,7 +378,7 @@ int zk_plonk_prover_info(zk_plonk_prover *p, zk_plonk_prover_plan *plan) {
             std::lock_guard<std::mutex> lock(p->mu);
             q.log_n = p->log_n;
             q.n_witness = p->n_witness, q.n_public = p->n_public;
-            q.device_bytes = p->own_bytes() + plonk_circuit_bytes(p->circ) + plonk_opening_bytes(p->open) + plonk_perm_bytes(p->perm);
+            q.device_bytes = p->own_bytes() + plonk_circuit_bytes(p->circ) + plonk_opening_bytes(p->open) + plonk_perm_bytes(p->perm) + plonk_many_bytes(p->many);
             q.last_launches = p->last_launches;
             for (uint32_t r = 0; r < ROUNDS; r++) q.round_launches[r] = p->round_launches[r];
         });

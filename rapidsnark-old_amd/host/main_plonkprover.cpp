@@ -12,10 +12,17 @@
 // on stdout, no file written); 255 with a message on stderr for anything else: usage, an unreadable or ill-formed file, a
 // witness of another circuit, a .ptau too small for the circuit, no device.  All three files are read and matched before the
 // device is touched.  ZKHIP_SELFVERIFY=1 verifies the proof before anything is written; ZKHIP_DEVICE=<n> picks the device.
+//
+// plonkprover <circuit.r1cs> <pot.ptau> <w1.wtns> <p1.json> <pub1.json> <w2.wtns> <p2.json> <pub2.json> ..
+//
+// Several witnesses of the one circuit, a triple each, in ONE zk_plonk_prove_r1cs_many (ZKHIP_PLONK_PROVE_BATCH proofs share a
+// round's multiplication).  Every file is read and matched before the device is touched.  A witness the prover refuses is named
+// on stderr ("INVALID: <w.wtns>: <why>") and its two files are not written; the others' are, and the exit code is then 1.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -70,23 +77,35 @@ void must(int rc) {
     if (rc != 0) throw std::runtime_error(zk_last_error());
 }
 
-int run(const std::string &r1csPath, const std::string &ptauPath, const std::string &wtnsPath, const std::string &proofPath, const std::string &publicPath) {
-    // the three files are read and matched before the device is touched
-    auto r1cs = BinFileUtils::openExisting(r1csPath, "r1cs", 1);
-    auto rh = R1csUtils::loadHeader(r1cs.get());
-    auto ptau = BinFileUtils::openExisting(ptauPath, "ptau", 1);
-    auto ph = PtauUtils::loadHeader(ptau.get());
-    auto wtns = BinFileUtils::openExisting(wtnsPath, "wtns", 2);
-    auto wh = WtnsUtils::loadHeader(wtns.get());
-    if (!U256::is_bn254_r(wh->prime)) throw std::invalid_argument("different wtns curve");
-    if (wh->nVars != rh->nWires || wtns->getSectionSize(2) < uint64_t(wh->nVars) * 32)
-        throw std::invalid_argument("witness does not match the r1cs (nVars " + std::to_string(wh->nVars) + ", nWires " + std::to_string(rh->nWires) + ")");
+// What every form of the program does first: the files are read and matched before the device is touched, then the circuit is
+// compiled, the kzg made over the .ptau's points and the prover over both
+struct Job {
+    std::unique_ptr<BinFileUtils::BinFile> r1cs, ptau;
+    std::vector<std::unique_ptr<BinFileUtils::BinFile>> wtns;
+    std::vector<const uint8_t *> values;                // a witness's values, nVars of them
+    uint32_t nVars = 0, nPublic = 0;
+    Handles h;
+};
+
+void open_job(Job &j, const std::string &r1csPath, const std::string &ptauPath, const std::vector<std::string> &wtnsPaths) {
+    j.r1cs = BinFileUtils::openExisting(r1csPath, "r1cs", 1);
+    auto rh = R1csUtils::loadHeader(j.r1cs.get());
+    j.ptau = BinFileUtils::openExisting(ptauPath, "ptau", 1);
+    auto ph = PtauUtils::loadHeader(j.ptau.get());
+    for (const std::string &path : wtnsPaths) {
+        j.wtns.push_back(BinFileUtils::openExisting(path, "wtns", 2));
+        auto wh = WtnsUtils::loadHeader(j.wtns.back().get());
+        if (!U256::is_bn254_r(wh->prime)) throw std::invalid_argument("different wtns curve");
+        if (wh->nVars != rh->nWires || j.wtns.back()->getSectionSize(2) < uint64_t(wh->nVars) * 32)
+            throw std::invalid_argument("witness does not match the r1cs (nVars " + std::to_string(wh->nVars) + ", nWires " + std::to_string(rh->nWires) + ")");
+        j.values.push_back(static_cast<const uint8_t *>(j.wtns.back()->getSectionData(2)));
+        j.nVars = wh->nVars;
+    }
     if (!ph->powers[0] || !ph->powers[1]) throw std::invalid_argument("the ptau has no section 2 or 3");
-    const uint8_t *values = static_cast<const uint8_t *>(wtns->getSectionData(2));
-    const uint32_t nPublic = rh->nPubOut + rh->nPubIn;
+    j.nPublic = rh->nPubOut + rh->nPubIn;
 
     const int32_t device = device_from_env();
-    Handles h;
+    Handles &h = j.h;
     uint8_t k1[32] = {2}, k2[32] = {3};
     const zk_r1cs_view view = rh->view();
     must(zk_plonk_r1cs_create(&h.circuit, &view, k1, k2, device));
@@ -105,9 +124,28 @@ int run(const std::string &r1csPath, const std::string &ptauPath, const std::str
     kv.tau_g2 = ph->powers[1], kv.tau_g2_bytes = ph->powersBytes[1];
     must(zk_kzg_create(&h.kzg, &kv, n + 6, ZK_KZG_NO_LAGRANGE, device));
     must(zk_plonk_prover_create_r1cs(&h.prover, h.kzg, h.circuit, nullptr, -1));
+}
+
+void write_files(const uint8_t proof[ZK_PLONK_PROOF_BYTES], const uint8_t *values, uint32_t nPublic, const std::string &proofPath, const std::string &publicPath) {
+    const std::string pj = proof_json(proof);
+    std::vector<char> pub(zk_public_to_json(values, nPublic, nullptr, 0) + 1);
+    zk_public_to_json(values, nPublic, pub.data(), pub.size());
+    OutFile fp(proofPath), fq(publicPath);
+    fp.write(pj.data(), pj.size());
+    fq.write(pub.data(), strlen(pub.data()));
+    fp.commit();
+    fq.commit();
+}
+
+int run(const std::string &r1csPath, const std::string &ptauPath, const std::string &wtnsPath, const std::string &proofPath, const std::string &publicPath) {
+    Job j;
+    open_job(j, r1csPath, ptauPath, {wtnsPath});
+    Handles &h = j.h;
+    const uint8_t *values = j.values[0];
+    const uint32_t nPublic = j.nPublic;
 
     uint8_t proof[ZK_PLONK_PROOF_BYTES];
-    if (zk_plonk_prove_r1cs(h.prover, proof, values, wh->nVars, nullptr) != 0) {
+    if (zk_plonk_prove_r1cs(h.prover, proof, values, j.nVars, nullptr) != 0) {
         const std::string err = zk_last_error();
         if (err.find("the witness does not satisfy the gates") != std::string::npos || err.find("the copy constraints do not hold") != std::string::npos) {
             std::cout << "INVALID: " << err << "\n";
@@ -125,20 +163,55 @@ int run(const std::string &r1csPath, const std::string &ptauPath, const std::str
         must(zk_plonk_verify(h.kzg, &vk, proof, nPublic ? values + 32 : nullptr, &verdict));
         if (verdict != ZK_VERIFY_OK) throw std::runtime_error("ZKHIP_SELFVERIFY: the proof does not verify (verdict " + std::to_string(verdict) + ")");
     }
-    const std::string pj = proof_json(proof);
-    std::vector<char> pub(zk_public_to_json(values, nPublic, nullptr, 0) + 1);
-    zk_public_to_json(values, nPublic, pub.data(), pub.size());
-    OutFile fp(proofPath), fq(publicPath);
-    fp.write(pj.data(), pj.size());
-    fq.write(pub.data(), strlen(pub.data()));
-    fp.commit();
-    fq.commit();
+    write_files(proof, values, nPublic, proofPath, publicPath);
     return 0;
+}
+
+// Several witnesses of one circuit: argv[3 ..] holds a triple <w.wtns> <proof.json> <public.json> a witness.  One
+// zk_plonk_prove_r1cs_many; a refused witness is named on stderr, its two files are not written, and once the others' are the
+// exit code is a refused witness's
+int run_many(int argc, char **argv) {
+    const uint32_t m = (uint32_t)(argc - 3) / 3;
+    std::vector<std::string> wtnsPaths;
+    for (uint32_t i = 0; i < m; i++) wtnsPaths.push_back(argv[3 + 3 * i]);
+    Job j;
+    open_job(j, argv[1], argv[2], wtnsPaths);
+    Handles &h = j.h;
+    std::vector<uint8_t> all((size_t)m * j.nVars * 32), proofs((size_t)m * ZK_PLONK_PROOF_BYTES);
+    for (uint32_t i = 0; i < m; i++) memcpy(all.data() + (size_t)i * j.nVars * 32, j.values[i], (size_t)j.nVars * 32);
+    std::vector<uint32_t> status(m, 0);
+    must(zk_plonk_prove_r1cs_many(h.prover, m, proofs.data(), status.data(), all.data(), j.nVars, nullptr));
+    const char *sv = getenv("ZKHIP_SELFVERIFY");
+    if (sv && strcmp(sv, "1") == 0) {
+        zk_plonk_vkey vk;
+        memset(&vk, 0, sizeof vk);
+        vk.size = sizeof vk;
+        must(zk_plonk_prover_vkey(h.prover, &vk));
+        for (uint32_t i = 0; i < m; i++) {
+            if (status[i] != ZK_PLONK_MANY_MADE) continue;
+            uint8_t verdict = ZK_VERIFY_MALFORMED;
+            must(zk_plonk_verify(h.kzg, &vk, proofs.data() + (size_t)i * ZK_PLONK_PROOF_BYTES, j.nPublic ? j.values[i] + 32 : nullptr, &verdict));
+            if (verdict != ZK_VERIFY_OK)
+                throw std::runtime_error("ZKHIP_SELFVERIFY: the proof of " + wtnsPaths[i] + " does not verify (verdict " + std::to_string(verdict) + ")");
+        }
+    }
+    static const char *const why[5] = {"", "a denominator of the permutation product is zero", "the copy constraints do not hold",
+                                       "the witness does not satisfy the gates", "a value is not below r"};
+    int rc = 0;
+    for (uint32_t i = 0; i < m; i++) {
+        if (status[i] != ZK_PLONK_MANY_MADE) {
+            std::cerr << "INVALID: " << wtnsPaths[i] << ": " << (status[i] < 5 ? why[status[i]] : "refused") << "\n";
+            rc = 1;
+            continue;
+        }
+        write_files(proofs.data() + (size_t)i * ZK_PLONK_PROOF_BYTES, j.values[i], j.nPublic, argv[4 + 3 * i], argv[5 + 3 * i]);
+    }
+    return rc;
 }
 
 }   // namespace
 
 int main(int argc, char **argv) {
-    return cli_main(argc == 6, "plonkprover <circuit.r1cs> <pot.ptau> <witness.wtns> <proof.json> <public.json>",
-                    [&] { return run(argv[1], argv[2], argv[3], argv[4], argv[5]); });
+    return cli_main(argc >= 6 && argc % 3 == 0, "plonkprover <circuit.r1cs> <pot.ptau> <witness.wtns> <proof.json> <public.json>",
+                    [&] { return argc == 6 ? run(argv[1], argv[2], argv[3], argv[4], argv[5]) : run_many(argc, argv); });
 }

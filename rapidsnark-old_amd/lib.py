@@ -199,6 +199,13 @@ class zk_plonk_prover_plan(C.Structure):
                 ("round_launches", C.c_uint32 * 5)]
 
 
+class zk_plonk_prover_many_plan(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("batch", C.c_uint32), ("table_batch", C.c_uint32), ("window_bits", C.c_uint32), ("table_rows", C.c_uint32),
+                ("reserved", C.c_uint32), ("table_bytes", C.c_uint64), ("slot_bytes", C.c_uint64), ("msm_bytes", C.c_uint64),
+                ("last_chunks", C.c_uint32), ("last_multiplications", C.c_uint32), ("last_launches", C.c_uint32), ("last_drains", C.c_uint32),
+                ("last_refused", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
 class zk_plonk_verifier_plan(C.Structure):
     _fields_ = [("size", C.c_uint32), ("log_n", C.c_uint32), ("n_public", C.c_uint64), ("device_bytes", C.c_uint64), ("chunk", C.c_uint64),
                 ("last_launches", C.c_uint32), ("last_chunks", C.c_uint32)]
@@ -288,6 +295,7 @@ EXPORTS = ["zk_last_error", "zk_device_count", "zk_prover_create", "zk_prover_de
            "zk_plonk_verify",
            "zk_plonk_r1cs_create", "zk_plonk_r1cs_destroy", "zk_plonk_r1cs_info", "zk_plonk_r1cs_circuit", "zk_plonk_r1cs_extend",
            "zk_plonk_prover_create_r1cs", "zk_plonk_prove_r1cs",
+           "zk_plonk_prove_many", "zk_plonk_prove_r1cs_many", "zk_plonk_prover_commit_many", "zk_plonk_prover_many_info",
            "zk_plonk_verifier_create", "zk_plonk_verifier_destroy", "zk_plonk_verifier_info", "zk_plonk_verifier_verify", "zk_plonk_verifier_challenges",
            "zk_plonk_verifier_verify_batch", "zk_plonk_verifier_batch_sums",
            "zk_plonk_verifier_set_create", "zk_plonk_verifier_set_destroy", "zk_plonk_verifier_set_info", "zk_plonk_verifier_set_verify",
@@ -489,6 +497,11 @@ def load_library():
         lib.zk_plonk_r1cs_extend.argtypes = [C.c_void_p, u8p, u8p, C.c_uint32]
         lib.zk_plonk_prover_create_r1cs.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, u8p, C.c_int32]
         lib.zk_plonk_prove_r1cs.argtypes = [C.c_void_p, u8p, u8p, C.c_uint32, u8p]
+    if hasattr(lib, "zk_plonk_prove_many"):
+        lib.zk_plonk_prove_many.argtypes = [C.c_void_p, C.c_uint64, u8p, C.c_void_p, u8p, u8p, u8p]
+        lib.zk_plonk_prove_r1cs_many.argtypes = [C.c_void_p, C.c_uint64, u8p, C.c_void_p, u8p, C.c_uint32, u8p]
+        lib.zk_plonk_prover_commit_many.argtypes = [C.c_void_p, u8p, u8p, C.c_uint64]
+        lib.zk_plonk_prover_many_info.argtypes = [C.c_void_p, C.POINTER(zk_plonk_prover_many_plan)]
     if hasattr(lib, "zk_plonk_verifier_create"):
         lib.zk_plonk_verifier_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(zk_plonk_vkey), C.c_int32]
         lib.zk_plonk_verifier_destroy.argtypes = [C.c_void_p]

@@ -617,6 +617,134 @@ class PlonkProver(_KzgObject):
                 raise L.ZkHipError("ZKHIP_SELFVERIFY: the proof does not verify (verdict %d)" % verdict)
         return proof
 
+    # ---- many witnesses a call (include/zkhip.h: zk_plonk_prove_many and its neighbours)
+    def _many_blinds(self, blinds, m):
+        """None, or m rows of eleven scalars (or their m x 11 x 32 bytes) -> bytes or None.  Values are the library's to judge"""
+        if blinds is None:
+            return None
+        if isinstance(blinds, (bytes, bytearray, memoryview)) or (isinstance(blinds, np.ndarray) and blinds.dtype == np.uint8):
+            bb = L._buf(blinds)
+            if bb.size != m * BLINDS * 32:
+                raise ValueError("blinds: %d bytes, %d rows of %d scalars expected" % (bb.size, m, BLINDS))
+            return bb
+        blinds = list(blinds)
+        if len(blinds) != m:
+            raise ValueError("blinds: %d rows for %d witnesses" % (len(blinds), m))
+        rows = []
+        for i, row in enumerate(blinds):
+            r = _scalars(row, "blinds[%d]" % i, below_r=False)
+            if r.size != BLINDS * 32:
+                raise ValueError("blinds[%d]: %d values, %d expected" % (i, r.size // 32, BLINDS))
+            rows.append(r)
+        return np.concatenate(rows) if rows else np.zeros(0, dtype=np.uint8)
+
+    def _many_result(self, out, status, publics_of):
+        """the call's bytes -> (list of PlonkProof or None, status); ZKHIP_SELFVERIFY=1: the proofs made go through ONE verify call"""
+        import os
+        m = status.size
+        proofs = [PlonkProof(out[i * PROOF_BYTES:(i + 1) * PROOF_BYTES].tobytes()) if status[i] == 0 else None for i in range(m)]
+        made = [i for i in range(m) if status[i] == 0]
+        if made and os.environ.get("ZKHIP_SELFVERIFY") == "1":
+            with PlonkVerifier(self.vkey(), device=self.device) as v:
+                verdicts = v.verify([proofs[i] for i in made], [publics_of(i) for i in made] if self.n_public else None)
+            bad = [j for j in range(len(made)) if verdicts[j] != 0]
+            if bad:
+                raise L.ZkHipError("ZKHIP_SELFVERIFY: proof %d does not verify (verdict %d)" % (made[bad[0]], int(verdicts[bad[0]])))
+        return proofs, status
+
+    def prove_many(self, witnesses, publics=None, blinds=None):
+        """-> (list of PlonkProof or None, numpy uint32 [m] status) (zk_plonk_prove_many): m witnesses of the circuit in one call,
+        proof i what prove(witnesses[i], publics[i], blinds[i]) gives.  A witness the prover refuses gives None and a status that
+        is not 0 (1: a zero denominator, 2: the copies, 3: the gates, 4: a value not below r) and does not take the others with
+        it.  publics None: each witness's values 1 .. n_public.  blinds None: drawn; given (FOR TESTS ONLY): m rows of eleven.
+        ZKHIP_PLONK_PROVE_BATCH sets how many proofs share a round's multiplication.  ZKHIP_SELFVERIFY=1: the proofs made are
+        verified, in ONE PlonkVerifier.verify call, before they are returned."""
+        witnesses = list(witnesses)
+        m = len(witnesses)
+        ws = []
+        for i, w in enumerate(witnesses):
+            a = _scalars(w, "witnesses[%d]" % i, below_r=False)
+            if a.size != self.n_witness * 32:
+                raise ValueError("witnesses[%d]: %d values, n_witness = %d expected" % (i, a.size // 32, self.n_witness))
+            ws.append(a)
+        if publics is None:
+            if 1 + self.n_public > self.n_witness:
+                raise ValueError("publics: a witness has no %d values after its first" % self.n_public)
+            ps = [w[32:32 * (1 + self.n_public)] for w in ws]
+        else:
+            publics = list(publics)
+            if len(publics) != m:
+                raise ValueError("publics: %d rows for %d witnesses" % (len(publics), m))
+            ps = []
+            for i, row in enumerate(publics):
+                a = _scalars(row, "publics[%d]" % i, below_r=False)
+                if a.size != self.n_public * 32:
+                    raise ValueError("publics[%d]: %d values, n_public = %d expected" % (i, a.size // 32, self.n_public))
+                ps.append(a)
+        bb = self._many_blinds(blinds, m)
+        h = self._handle()
+        wb = np.concatenate(ws) if ws else np.zeros(0, dtype=np.uint8)
+        pb = np.concatenate(ps) if ps and self.n_public else None
+        out = np.zeros(m * PROOF_BYTES, dtype=np.uint8)
+        status = np.full(m, 0xFFFFFFFF, dtype=np.uint32)
+        L.check(L.load_library().zk_plonk_prove_many(h, m, L._ptr(out) if m else None, L._ptr(status) if m else None, L._ptr(wb) if m else None,
+                                                     L._ptr(pb) if pb is not None and m else None, L._ptr(bb) if bb is not None and m else None))
+        return self._many_result(out, status, lambda i: ps[i])
+
+    def prove_r1cs_many(self, wtns, blinds=None):
+        """-> (list of PlonkProof or None, status) (zk_plonk_prove_r1cs_many) from m circom witnesses, each as prove_r1cs takes
+        its one; the device extends each.  blinds and ZKHIP_SELFVERIFY: as prove_many."""
+        if self.r1cs is None:
+            if not self._h:
+                raise L.ZkHipError("the PlonkProver object is closed")
+            raise L.ZkHipError("zk_plonk_prove_r1cs_many: the prover was not made from an r1cs (zk_plonk_prover_create_r1cs)")
+        vals = [self.r1cs._values(w) for w in wtns]
+        m = len(vals)
+        for i, (a, n_vars) in enumerate(vals):
+            if n_vars != vals[0][1]:
+                raise ValueError("wtns[%d] has %d values, wtns[0] has %d: the witnesses must have one length" % (i, n_vars, vals[0][1]))
+            if a.size < n_vars * 32:
+                raise ValueError("wtns[%d]: %d bytes for %d values" % (i, a.size, n_vars))
+        n_vars = vals[0][1] if m else self.r1cs.n_wires
+        bb = self._many_blinds(blinds, m)
+        h = self._handle()
+        self.r1cs._handle()
+        wb = np.concatenate([a[:n_vars * 32] for a, _ in vals]) if m else np.zeros(0, dtype=np.uint8)
+        out = np.zeros(m * PROOF_BYTES, dtype=np.uint8)
+        status = np.full(m, 0xFFFFFFFF, dtype=np.uint32)
+        L.check(L.load_library().zk_plonk_prove_r1cs_many(h, m, L._ptr(out) if m else None, L._ptr(status) if m else None, L._ptr(wb) if wb.size else None,
+                                                          n_vars, L._ptr(bb) if bb is not None and m else None))
+        return self._many_result(out, status, lambda i: np.array(vals[i][0][32:32 * (1 + self.n_public)]))
+
+    def commit_many(self, coeffs):
+        """list of k commitments, 64 bytes each (zk_plonk_prover_commit_many): k polynomials of at most n + 6 coefficients each
+        (sequences of ints, or uint8 rows), through the prover's table and its batched multiplication."""
+        n6 = self.n + 6
+        rows = []
+        for i, c in enumerate(coeffs):
+            a = _scalars(c, "coeffs[%d]" % i, below_r=False)
+            if not 1 <= a.size // 32 <= n6:
+                raise ValueError("coeffs[%d]: %d coefficients, 1 .. n + 6 = %d expected" % (i, a.size // 32, n6))
+            rows.append(np.concatenate([a, np.zeros(n6 * 32 - a.size, dtype=np.uint8)]))
+        if not rows:
+            raise ValueError("coeffs: at least one polynomial expected")
+        h = self._handle()
+        cb = np.concatenate(rows)
+        out = np.zeros(len(rows) * 64, dtype=np.uint8)
+        L.check(L.load_library().zk_plonk_prover_commit_many(h, L._ptr(out), L._ptr(cb), len(rows)))
+        ob = out.tobytes()
+        return [ob[i * 64:(i + 1) * 64] for i in range(len(rows))]
+
+    def many_info(self):
+        """zk_plonk_prover_many_info -> dict: batch (the chunk width in effect), table_batch, window_bits, table_rows,
+        table_bytes, slot_bytes, msm_bytes, and of the last many-call last_chunks, last_multiplications, last_launches,
+        last_drains, last_refused"""
+        h = self._handle()
+        plan = L.zk_plonk_prover_many_plan()
+        plan.size = C.sizeof(plan)
+        L.check(L.load_library().zk_plonk_prover_many_info(h, C.byref(plan)))
+        return {name: int(getattr(plan, name)) for name, _ in plan._fields_ if name not in ("size", "reserved", "reserved2")}
+
     def vkey(self):
         """-> PlonkVKey (zk_plonk_prover_vkey): log_n, n_public, k1, k2, the eight commitments and [tau]G2"""
         h = self._handle()
